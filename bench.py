@@ -12,13 +12,18 @@ with N > 1 the gradient exchange is one RCCL all-reduce of the flat 2.9 MB gradi
 buckets issued from backward hooks, or one all-reduce in step(): calibrated on the node, `rccl.exchange`).
 Rank 0 prints ONE JSON line.
 
-Protocol per leg: `--priming` untimed steps (allocator, lazy module loading, clock ramp), W untimed
+Protocol per leg: `--priming-seconds` of steps on a throwaway instance of the same configuration (sustained
+clocks), then on the measured instance `--priming` untimed steps (allocator, lazy module loading), W untimed
 warm-up steps, then EXACTLY K steps between barrier + synchronize (max over ranks) -> `value`,
-`ms_per_step` (nothing but the steps is in that region); the same K steps once more with one HIP event per step
-boundary on the launch stream -> `step_ms` median / p10 / p90.
-A third, event-instrumented pass (events around every ABI launch) prices every conv entry point of
-every layer against its roof -> `roofline` (the dominant entry point) and `layers`.
+`ms_per_step` (nothing but the steps is in that region).  The measured instance thus always takes
+priming + W + K steps from the same seeded state and batch: `--dump-outputs DIR` writes what its last timed
+step left (the loop's mean loss, parameters and buffers, the last step's gradients), the same from run to run.
+A plain run stops there: the line holds the headline figure and the configuration.
 
+`--full` adds everything else: the same K steps once more with one HIP event per step boundary on the
+launch stream -> `step_ms` median / p10 / p90; a third, event-instrumented pass (events around every ABI
+launch) that prices every conv entry point of every layer against its roof -> `roofline` (the dominant
+entry point) and `layers` (side file, `--detail`); for N > 1 the exchange checks.
 `also` carries the other configurations of BASELINE.json, each measured the same way with its own
 roofline: ECGMultimodal (configs[2]/[3]), the headline with the stock torch.optim.AdamW the reference
 scripts construct (scripts/03_train_ecg_baseline.py:130-133), and configs[4] (ECGCNN(1), 12x5000,
@@ -26,6 +31,7 @@ batch 256) in fp32 and in the opt-in bf16 mode.  The CPU baseline (oracle/ref_mo
 CPU ops: "port") runs LAST so that its thread pool cannot disturb a GPU leg.
 """
 import argparse
+import gc
 import json
 import os
 import socket
@@ -169,6 +175,29 @@ def percentiles(v):
     return {"median": round(float(np.median(a)), 4), "p10": round(float(np.percentile(a, 10)), 4),
             "p90": round(float(np.percentile(a, 90)), 4), "min": round(float(a.min()), 4),
             "max": round(float(a.max()), 4), "n": int(a.size)}
+
+
+def output_arrays(model, mean_loss):
+    """What a caller of the timed loop holds after its last step, as numpy arrays (float32, float64 for the loss and the
+    integer step counters of BatchNorm): "loss" = the epoch's mean loss the loop returns, "state.<key>" = model.state_dict()
+    (parameters and buffers), "grad.<name>" = the gradients of the last step.  About 6 MB for ECGCNN / ECGMultimodal."""
+    import numpy as np
+    import torch
+    out = {"loss": np.asarray(mean_loss, dtype=np.float64)}
+    for k, v in model.state_dict().items():
+        v = v.detach().cpu()
+        out[f"state.{k}"] = v.numpy().astype(np.float32 if v.is_floating_point() and v.dtype != torch.float64 else np.float64)
+    for k, p in model.named_parameters():
+        if p.grad is not None:
+            out[f"grad.{k}"] = p.grad.detach().float().cpu().numpy()
+    return out
+
+
+def write_outputs(directory, arrays):
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, f"{name}.npy"), a)
 
 
 def conv_flops_per_window(T):
@@ -509,7 +538,8 @@ def build_line(primary, also, cpu, rccl, *, n_gpus, steps, warmup, batch, length
     """(line, detail): the ONE JSON line rank 0 prints — at most LINE_BUDGET characters, everything the contract and
     the judge read (value, ms_per_step, config, step_ms, roofline, cpu_baseline, rccl, one summary row per other
     configuration) — and the full record (per-entry-point `layers` tables of every leg, the CPU thread sweep, the
-    gradient checksums) that goes to a side file whose path the line carries."""
+    gradient checksums) that goes to a side file whose path the line carries.  A plain run's primary record has only the
+    headline figures: the line then has no per-step, roofline or per-block blocks."""
     line = {
         "metric": f"ECG windows/s (train step) at 12x{length}, batch {batch}", "value": primary["value"], "unit": "windows/s",
         "n_gpus": n_gpus, "steps": steps, "warmup": warmup, "ms_per_step": primary["ms_per_step"],
@@ -517,12 +547,11 @@ def build_line(primary, also, cpu, rccl, *, n_gpus, steps, warmup, batch, length
         "config": {"workload": primary["workload"], "global_batch": batch * n_gpus, "parallelism": f"dp{n_gpus}",
                    "loop": primary["loop"], "optimizer": primary["optimizer"], "priming_steps": priming,
                    "priming_seconds": priming_seconds, "final_loss": primary["final_loss"]},
-        "step_ms": _short_step_ms(primary["step_ms"]), "value_at_median_step": primary["value_at_median_step"],
-        "step_conv_tflops": primary["step_conv_tflops"], "step_frac_of_mfma_peak": primary["step_frac_of_mfma_peak"],
-        "roofline": primary["roofline"], "frac_by_block": primary["frac_by_block"],
-        "pipe_frac_by_block": primary.get("pipe_frac_by_block"),
-        "instrumented_ms_per_step": primary["instrumented_ms_per_step"],
     }
+    for key in ("step_ms", "value_at_median_step", "step_conv_tflops", "step_frac_of_mfma_peak", "roofline", "frac_by_block",
+                "pipe_frac_by_block", "instrumented_ms_per_step"):
+        if key in primary:
+            line[key] = _short_step_ms(primary[key]) if key == "step_ms" else primary[key]
     if rccl is not None:
         line["rccl"] = _short_rccl(rccl, primary)
         if n1_value:
@@ -575,9 +604,16 @@ def main():
                     help="keep priming every leg until this much wall time has passed as well (sustained clocks instead "
                          "of the boost a cold chip shows for the first ~second; also gives an external busy probe "
                          "something to see)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline figure: per-step times, the instrumented pass (roofline, "
+                         "per-entry-point tables in the --detail side file), the other configurations, the reference "
+                         "batch sizes, the CPU baseline, and for N > 1 the exchange checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(the loop's mean loss, parameters and buffers, the last step's gradients; rank 0)")
     ap.add_argument("--detail", default=None,
-                    help="side file for the per-entry-point `layers` tables of every leg (default: "
-                         "gpurun_out/bench_detail_n<N>.json; the printed line carries its path only)")
+                    help="--full: side file for the per-entry-point `layers` tables of every leg (default: "
+                         "bench_out/bench_detail_n<N>.json; the printed line carries its path only)")
     ap.add_argument("--batch", type=int, default=256, help="windows per GPU")
     ap.add_argument("--length", type=int, default=1000)
     ap.add_argument("--model", choices=["multimodal", "cnn"], default="cnn",
@@ -586,7 +622,7 @@ def main():
     ap.add_argument("--optim", choices=["flat", "torch"], default="flat",
                     help="flat = ecg_hip.optim.FlatAdamW (one launch); torch = the stock torch.optim.AdamW the reference "
                          "scripts construct")
-    ap.add_argument("--no-also", action="store_true", help="skip the secondary legs")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip the secondary legs")
     ap.add_argument("--labels", type=int, default=5, help="output labels (1 = the AF-binary shape of BASELINE config 5)")
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32",
                     help="f32 (default, the parity path) or bf16 = opt-in mixed precision of BASELINE config 5: "
@@ -595,10 +631,12 @@ def main():
     ap.add_argument("--graph", action="store_true",
                     help="replay the whole step as one captured hipGraph (ecg_hip.graph.GraphedTrainStep); single GPU only")
     ap.add_argument("--cpu-seconds", type=float, default=14.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--n1-value", type=float, default=None,
                     help="windows/s of the N=1 run: adds efficiency_vs_n1 = value / (N * n1-value) to an N>1 line")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # ---- before ANY GPU call: a bare `--gpus N` starts its own ranks --------------------------------------
     if args.workload == "train" and args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -637,11 +675,11 @@ def main():
             dist.barrier(device_ids=[local]) if backend == "nccl" else dist.barrier()
         torch.cuda.synchronize()
 
-    def run_leg(spec):
-        """One configuration, measured by the protocol in the module docstring.  Every rank takes part."""
+    def make_leg(spec):
+        """Model, wrapper, optimizer, seeded batch and step runners of one configuration: the same state on every call."""
         B, T, labels, demo = spec["batch"], spec["length"], spec["labels"], spec["model"] == "multimodal"
-        bf16, graph, stock = spec["dtype"] == "bf16", spec.get("graph", False), spec.get("optim", "flat") == "torch"
-        hipF.set_conv_precision("bf16" if bf16 else "fp32")
+        graph, stock = spec.get("graph", False), spec.get("optim", "flat") == "torch"
+        hipF.set_conv_precision("bf16" if spec["dtype"] == "bf16" else "fp32")
         set_seed(42)
         model = (ECGMultimodal(num_labels=labels) if demo else ECGCNN(num_labels=labels)).to(dev)
         if world > 1:
@@ -670,10 +708,17 @@ def main():
                     gstep(*b)
                 return gstep.mean_loss_and_reset(len(loader))
 
-        if spec["priming"] > 0:
-            run(wrapped, ListLoader(batch, spec["priming"]), opt, dev)
+        return model, wrapped, opt, batch, run, run_eager
+
+    def run_leg(spec, full, dump_dir=None):
+        """One configuration, measured by the protocol in the module docstring.  Every rank takes part."""
+        B, T, labels, demo = spec["batch"], spec["length"], spec["labels"], spec["model"] == "multimodal"
+        bf16, graph, stock = spec["dtype"] == "bf16", spec.get("graph", False), spec.get("optim", "flat") == "torch"
         if spec.get("priming_seconds", 0) > 0:
-            # time-based part of the priming: the same on every rank (rank 0's clock decides), outside every timed region
+            # time-based part of the priming (sustained clocks): the same on every rank (rank 0's clock decides), outside
+            # every timed region, on a throwaway instance so that the number of steps it takes leaves no trace in the
+            # measured one
+            model, wrapped, opt, batch, run, _ = make_leg(spec)
             t_end, chunk = time.perf_counter() + spec["priming_seconds"], max(10, spec["priming"])
             while True:
                 run(wrapped, ListLoader(batch, chunk), opt, dev)
@@ -683,6 +728,11 @@ def main():
                     dist.broadcast(go, src=0)
                 if go.item() == 0.0:
                     break
+            del model, wrapped, opt, batch, run
+            gc.collect()         # its optimizer unregisters its gradient sinks before the next one registers its own
+        model, wrapped, opt, batch, run, run_eager = make_leg(spec)
+        if spec["priming"] > 0:
+            run(wrapped, ListLoader(batch, spec["priming"]), opt, dev)
         exchange_mode = None
         if world > 1 and not stock:
             # Calibrate the exchange on THIS node (outside the timed region): hooked two-bucket all-reduces under backward
@@ -693,7 +743,7 @@ def main():
         run(wrapped, ListLoader(batch, spec["warmup"]), opt, dev)
         # The timed region carries NO per-step events: an event record between two steps is a barrier packet with a
         # timestamp and costs 2-7 us of idle front end per step (A/B on one box: 1.6514 / 1.6552 ms with, 1.6498 / 1.6482
-        # without).  The per-step distribution comes from a second pass of the same K steps right after it.
+        # without).  With --full the per-step distribution comes from a second pass of the same K steps right after it.
         loader = ListLoader(batch, spec["steps"])
         barrier()
         t0 = time.perf_counter()
@@ -704,88 +754,93 @@ def main():
             t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = t.item()
-        loader = ListLoader(batch, spec["steps"], record=True)
-        run(wrapped, loader, opt, dev)
-        torch.cuda.synchronize()
-        step_ms = percentiles(loader.step_ms())
-
-        # instrumented pass (HIP events around every ABI launch on the launch stream); always eager
-        n_instr = 5
-        exch = []
-        if world > 1 and not stock:           # exposed exchange time: how long the compute stream waits in reduce_gradients
-            inner = opt.reduce_gradients
-
-            def timed_reduce():
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-                out = inner()
-                b.record()
-                exch.append((a, b))
-                return out
-            opt.reduce_gradients = timed_reduce
-        with _lib.kernel_timing() as kt:
-            run_eager(wrapped, ListLoader(batch, n_instr), opt, dev)
-        if exch:
-            opt.reduce_gradients = inner
-        rows, other_ms = layer_table(kt.result, leg_tag(spec["model"], labels, "bf16" if bf16 else "f32", T))
+        if dump_dir is not None and rank == 0:
+            write_outputs(dump_dir, output_arrays(model, last_loss))
         # did the loop API replay a captured step (ecg_hip.graph.LoopStepper: FlatAdamW, one rank, no hooks)?
         loop_replays = (not graph) and any(st.graphs for st in getattr(opt, "_ecg_loop_steppers", {}).values())
-        conv_ms = sum(r["avg_us"] * r["calls"] for r in rows) / 1e3
 
         value = world * B * spec["steps"] / elapsed
         fwd_f, step_f = conv_flops_per_window(T)
         peak = PEAK_BF16_TFLOPS if bf16 else PEAK_F32_TFLOPS
-        passes = sorted(OTHER_ROWS, key=lambda r: -r["avg_us"] * r["calls"])
-        bn_ms = sum(r["avg_us"] * r["calls"] for r in passes if r["group"] == "bn_pool") / 1e3
         res = {
             "workload": (f"{'ECGMultimodal (FiLM)' if demo else f'ECGCNN({labels})'} train step fwd+BCE+bwd+AdamW, 12x{T}, "
                          f"{'bf16 conv operands' if bf16 else 'fp32'}, batch {B}/GPU, global batch {B * world}"),
             "value": round(value, 1), "unit": "windows/s", "ms_per_step": round(1e3 * elapsed / spec["steps"], 4),
-            "step_ms": step_ms, "value_at_median_step": round(world * B / (step_ms["median"] * 1e-3), 1),
             "dtype": "f32" if not bf16 else ("bf16 conv operands (fwd, input-grad, weight-grad) and inter-kernel activation storage (y, p, dp) / "
                                              "f32 accumulate, BN arithmetic, parameters, tail, optimizer"),
             "dtype_short": "bf16" if bf16 else "f32",
             "workload_short": (f"{'ECGMultimodal' if demo else f'ECGCNN({labels})'} 12x{T} {'bf16' if bf16 else 'f32'} B={B}"
                                f"{' stockAdamW' if stock else ''}{' graph' if graph else ''}"),
-            "frac_by_block": frac_by_block(rows), "pipe_frac_by_block": frac_by_block(rows, "pipe_frac"),
             "optimizer": "torch.optim.AdamW (stock)" if stock else "FlatAdamW",
             "loop": ("hipGraph replay (GraphedTrainStep)" if graph else "train_one_epoch" + ("_demo" if demo else "") +
                      (" (hipGraph replay per batch shape)" if loop_replays else "")),
             "final_loss": round(float(last_loss), 6),
             "step_conv_tflops": round(value * step_f / 1e12, 2),
             "step_frac_of_mfma_peak": round(value * step_f / 1e12 / (peak * world), 4),
-            "roofline": roofline_of(rows), "layers": rows,
-            # everything_else = BatchNorm/pool passes (HBM-bound streams) + the rest (tail, loss, optimizer, weight packs);
-            # host_gap = step time the GPU spends on none of them (launch gaps: the eager loop is host-bound when > 0)
-            "instrumented_ms_per_step": {"conv_entry_points": round(conv_ms / n_instr, 4),
-                                         "everything_else": round(other_ms / n_instr, 4),
-                                         "bn_pool_passes": round(bn_ms / n_instr, 4),
-                                         "host_gap": round(max(0.0, 1e3 * elapsed / spec["steps"] - (conv_ms + other_ms) / n_instr), 4)},
-            "passes": passes,
         }
-        if exch:
-            torch.cuda.synchronize()
-            res["exchange_exposed_ms_per_step"] = percentiles([a.elapsed_time(b) for a, b in exch])
         if exchange_mode:
             res["exchange"] = exchange_mode
         extra = None
-        if world > 1 and not stock:
-            # RCCL sanity on real gradients: exchange once by hand and compare checksums
-            opt.zero_grad()
-            with opt.no_sync():
-                out = wrapped(*batch[:-1])
-                hipF.backward_from_loss(hipF.binary_cross_entropy_with_logits(out, batch[-1]))
-            opt._gather(0, len(opt._params))
-            local_sum = opt.flat_grad.double().sum()
-            total = local_sum.clone()
-            dist.all_reduce(total)
-            flat, _scale = opt.reduce_gradients()
-            after = flat.double().sum().item()
-            opt.zero_grad()
-            extra = {"grad_checksum_sum_of_ranks": total.item(), "grad_checksum_after_allreduce": after,
-                     "rel_diff": abs(after - total.item()) / max(abs(total.item()), 1e-30),
-                     "flat_gradient_bytes": int(opt.flat_grad.numel() * 4)}
-        del model, opt, wrapped, batch, x, y
+        if full:
+            loader = ListLoader(batch, spec["steps"], record=True)
+            run(wrapped, loader, opt, dev)
+            torch.cuda.synchronize()
+            step_ms = percentiles(loader.step_ms())
+
+            # instrumented pass (HIP events around every ABI launch on the launch stream); always eager
+            n_instr = 5
+            exch = []
+            if world > 1 and not stock:           # exposed exchange time: how long the compute stream waits in reduce_gradients
+                inner = opt.reduce_gradients
+
+                def timed_reduce():
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    out = inner()
+                    b.record()
+                    exch.append((a, b))
+                    return out
+                opt.reduce_gradients = timed_reduce
+            with _lib.kernel_timing() as kt:
+                run_eager(wrapped, ListLoader(batch, n_instr), opt, dev)
+            if exch:
+                opt.reduce_gradients = inner
+            rows, other_ms = layer_table(kt.result, leg_tag(spec["model"], labels, "bf16" if bf16 else "f32", T))
+            conv_ms = sum(r["avg_us"] * r["calls"] for r in rows) / 1e3
+            passes = sorted(OTHER_ROWS, key=lambda r: -r["avg_us"] * r["calls"])
+            bn_ms = sum(r["avg_us"] * r["calls"] for r in passes if r["group"] == "bn_pool") / 1e3
+            res.update({
+                "step_ms": step_ms, "value_at_median_step": round(world * B / (step_ms["median"] * 1e-3), 1),
+                "frac_by_block": frac_by_block(rows), "pipe_frac_by_block": frac_by_block(rows, "pipe_frac"),
+                "roofline": roofline_of(rows), "layers": rows,
+                # everything_else = BatchNorm/pool passes (HBM-bound streams) + the rest (tail, loss, optimizer, weight packs);
+                # host_gap = step time the GPU spends on none of them (launch gaps: the eager loop is host-bound when > 0)
+                "instrumented_ms_per_step": {"conv_entry_points": round(conv_ms / n_instr, 4),
+                                             "everything_else": round(other_ms / n_instr, 4),
+                                             "bn_pool_passes": round(bn_ms / n_instr, 4),
+                                             "host_gap": round(max(0.0, 1e3 * elapsed / spec["steps"] - (conv_ms + other_ms) / n_instr), 4)},
+                "passes": passes,
+            })
+            if exch:
+                torch.cuda.synchronize()
+                res["exchange_exposed_ms_per_step"] = percentiles([a.elapsed_time(b) for a, b in exch])
+            if world > 1 and not stock:
+                # RCCL sanity on real gradients: exchange once by hand and compare checksums
+                opt.zero_grad()
+                with opt.no_sync():
+                    out = wrapped(*batch[:-1])
+                    hipF.backward_from_loss(hipF.binary_cross_entropy_with_logits(out, batch[-1]))
+                opt._gather(0, len(opt._params))
+                local_sum = opt.flat_grad.double().sum()
+                total = local_sum.clone()
+                dist.all_reduce(total)
+                flat, _scale = opt.reduce_gradients()
+                after = flat.double().sum().item()
+                opt.zero_grad()
+                extra = {"grad_checksum_sum_of_ranks": total.item(), "grad_checksum_after_allreduce": after,
+                         "rel_diff": abs(after - total.item()) / max(abs(total.item()), 1e-30),
+                         "flat_gradient_bytes": int(opt.flat_grad.numel() * 4)}
+        del model, opt, wrapped, batch
         torch.cuda.empty_cache()
         return res, extra
 
@@ -793,10 +848,10 @@ def main():
             "dtype": args.dtype, "optim": args.optim, "graph": args.graph,
             "steps": args.steps, "warmup": args.warmup, "priming": args.priming,
             "priming_seconds": args.priming_seconds}
-    primary, rccl_extra = run_leg(base)
+    primary, rccl_extra = run_leg(base, args.full, args.dump_outputs)
 
     also = []
-    if not args.no_also:
+    if args.full and not args.no_also:
         legs = []
         if args.model == "cnn":
             legs.append(dict(base, model="multimodal", graph=False))
@@ -810,7 +865,7 @@ def main():
             legs.append(dict(base, model="cnn", labels=1, length=5000, optim="flat", steps=k5, priming=10))
             legs.append(dict(base, model="cnn", labels=1, length=5000, optim="flat", dtype="bf16", steps=k5, priming=10))
         for spec in legs:
-            res, _ = run_leg(spec)
+            res, _ = run_leg(spec, True)
             also.append(res)
 
     # The reference's OWN batch sizes through the unchanged loop API (configs/ecg_baseline.yaml:12 batch 64,
@@ -818,41 +873,44 @@ def main():
     # eager step is bound by Python's enqueue time, and train_one_epoch replays a captured hipGraph instead
     # (ecg_hip.graph.LoopStepper).  Both forms are measured; detail file only, one summary row each in the line.
     small = []
-    if world == 1 and not args.no_also and not args.graph and args.dtype == "f32" and args.length == 1000 and args.optim == "flat":
+    if args.full and world == 1 and not args.no_also and not args.graph and args.dtype == "f32" and args.length == 1000 \
+            and args.optim == "flat":
         for B_, T_, labels_ in ((64, 5000, 5), (32, 5000, 1), (32, 1000, 5)):
             pair = {}
             for mode in ("1", "0"):
                 os.environ["ECG_HIP_LOOP_GRAPH"] = mode
                 res, _ = run_leg(dict(base, model="cnn", labels=labels_, length=T_, batch=B_, optim="flat", graph=False,
-                                      steps=max(20, args.steps), priming=10, priming_seconds=0.5))
+                                      steps=max(20, args.steps), priming=10, priming_seconds=0.5), True)
                 pair["graph" if mode == "1" else "eager"] = res
             os.environ.pop("ECG_HIP_LOOP_GRAPH", None)
             small.append(pair)
 
     ranks_seen = None
-    if world > 1:
+    if args.full and world > 1:
         ones = torch.ones(1, device=dev)
         dist.all_reduce(ones)
         ranks_seen = int(ones.item())
     if rank == 0:
         rccl = None
         if world > 1:
-            rccl = {"backend": backend + (" (one-GPU rehearsal: every rank on device 0)" if rehearsal else ""),
-                    "ranks_seen_by_allreduce": ranks_seen, **(rccl_extra or {})}
+            rccl = {"backend": backend + (" (one-GPU rehearsal: every rank on device 0)" if rehearsal else "")}
+            if args.full:
+                rccl.update(ranks_seen_by_allreduce=ranks_seen, **(rccl_extra or {}))
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(args.cpu_seconds)       # LAST: its thread pool must not disturb a GPU leg
-        detail_path = args.detail or os.path.join(ROOT, "gpurun_out", f"bench_detail_n{world}.json")
         line, detail = build_line(primary, also, cpu, rccl, n_gpus=world, steps=args.steps, warmup=args.warmup,
                                   batch=args.batch, length=args.length, priming=args.priming,
                                   priming_seconds=args.priming_seconds, n1_value=args.n1_value, small=small)
-        try:
-            os.makedirs(os.path.dirname(detail_path), exist_ok=True)
-            with open(detail_path, "w") as f:
-                json.dump(detail, f, indent=1)
-            line["detail"] = os.path.relpath(detail_path, ROOT)
-        except OSError as e:
-            line["detail"] = f"not written: {e.__class__.__name__}"
+        if args.full:
+            detail_path = args.detail or os.path.join(ROOT, "bench_out", f"bench_detail_n{world}.json")
+            try:
+                os.makedirs(os.path.dirname(detail_path), exist_ok=True)
+                with open(detail_path, "w") as f:
+                    json.dump(detail, f, indent=1)
+                line["detail"] = os.path.relpath(detail_path, ROOT)
+            except OSError as e:
+                line["detail"] = f"not written: {e.__class__.__name__}"
         print(json.dumps(line, separators=(",", ":")), flush=True)
     if world > 1:
         barrier()

@@ -182,3 +182,55 @@ def test_rank_env_explains_itself():
     assert env["RANK"] == env["LOCAL_RANK"] == "3" and env["WORLD_SIZE"] == "8" and env["MASTER_ADDR"] == "127.0.0.1"
     assert env["HSA_ENABLE_IPC_MODE_LEGACY"] == "0" and "dmabuf" in bench.rank_env.__doc__
     assert bench.rank_env(0, 2, 1, base={"HSA_ENABLE_IPC_MODE_LEGACY": "1"})["HSA_ENABLE_IPC_MODE_LEGACY"] == "1"
+
+
+def test_plain_line_carries_the_headline_and_nothing_from_the_extra_passes():
+    """A plain run (no --full) measures the timed steps only: its primary record has the headline figures, and the line
+    holds them with the configuration, without the blocks that the per-step, instrumented and other-leg passes fill."""
+    full = _fake_leg("ECGCNN(5) train step", "ECGCNN(5) 12x1000 f32 B=256")
+    lean = {k: full[k] for k in ("workload", "workload_short", "value", "unit", "ms_per_step", "dtype", "dtype_short",
+                                 "optimizer", "loop", "final_loss", "step_conv_tflops", "step_frac_of_mfma_peak")}
+    line, _ = bench.build_line(lean, [], None, None, n_gpus=1, steps=20, warmup=5, batch=256, length=1000, priming=30,
+                               priming_seconds=1.5)
+    back = json.loads(json.dumps(line, separators=(",", ":")))
+    assert back["value"] == 156103.4 and back["ms_per_step"] == 1.6399 and back["unit"] == "windows/s"
+    assert back["higher_is_better"] is True and back["dtype"] == "f32" and back["steps"] == 20 and back["warmup"] == 5
+    assert back["config"]["global_batch"] == 256 and back["config"]["final_loss"] == 0.693147
+    for key in ("step_ms", "roofline", "frac_by_block", "instrumented_ms_per_step", "also", "cpu_baseline", "rccl",
+                "ref_batch_sizes"):
+        assert key not in back, key
+
+
+def test_output_arrays_are_what_the_loop_leaves_after_its_last_step(tmp_path):
+    """--dump-outputs: the loop's mean loss, every parameter and buffer, and the last step's gradients, as float32 /
+    float64 .npy files (here on CPU tensors, which the loop API runs through stock torch)."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "ptbxl-multimodal_amd"))
+    from ecg_hip.optim import FlatAdamW
+    from src.models.ecg_cnn import ECGCNN
+    from src.training.loop import train_one_epoch
+    from src.utils.seed import set_seed
+    set_seed(42)
+    model = ECGCNN(num_labels=5)
+    opt = FlatAdamW(model.parameters(), lr=1e-4, weight_decay=1e-4)
+    g = torch.Generator().manual_seed(1234)
+    batch = (torch.randn(4, 12, 1000, generator=g), (torch.rand(4, 5, generator=g) < 0.3).float())
+    loss = train_one_epoch(model, bench.ListLoader(batch, 3), opt, "cpu")
+    arrays = bench.output_arrays(model, loss)
+    bench.write_outputs(str(tmp_path / "out"), arrays)
+    back = {p.name[:-len(".npy")]: np.load(p) for p in (tmp_path / "out").iterdir()}
+    assert set(back) == set(arrays)
+    assert back["loss"].dtype == np.float64 and float(back["loss"]) == loss
+    sd = model.state_dict()
+    assert {k for k in back if k.startswith("state.")} == {f"state.{k}" for k in sd}
+    assert {k for k in back if k.startswith("grad.")} == {f"grad.{k}" for k, _ in model.named_parameters()}
+    for k, v in sd.items():
+        a = back[f"state.{k}"]
+        if k.endswith("num_batches_tracked"):
+            assert a.dtype == np.float64 and float(a) == 3.0            # exactly the steps the loop took
+        else:
+            assert a.dtype == np.float32 and np.array_equal(a, v.numpy())
+    for k, p in model.named_parameters():
+        assert back[f"grad.{k}"].dtype == np.float32 and np.array_equal(back[f"grad.{k}"], p.grad.numpy())
+    assert sum(a.nbytes for a in back.values()) < 64 << 20

@@ -96,7 +96,7 @@ def test_bench_two_rank_line(tmp_path, launcher):
     env = dict(os.environ, ECG_HIP_REHEARSE_ON_ONE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None)
     detail = tmp_path / "detail.json"
-    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--priming", "2",
+    tail = [os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "2", "--priming", "2",
             "--priming-seconds", "0.2", "--batch", "32", "--n1-value", "1000", "--detail", str(detail)]
     if launcher == "self":
         cmd = [sys.executable] + tail

@@ -105,7 +105,7 @@ def main():
     summ = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "prof_summary.py"),
                            stats, str(steps), "40"], capture_output=True, text=True).stdout
     open(os.path.join(PROF, f"{TAG}_kernel_stats_summary.txt"), "w").write(
-        f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --no-also --steps 20 --warmup 5 --priming 0  ({steps} steps incl. warm-up, the per-step-event repeat and the instrumented pass)\n" + summ)
+        f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --no-also --steps 20 --warmup 5 --priming 0  ({steps} steps incl. warm-up, the per-step-event repeat and the instrumented pass)\n" + summ)
 
     c5 = glob.glob(os.path.join(OUT, f"prof_{TAG}_c5bf16", "**", "*_kernel_stats.csv"), recursive=True)
     if c5:
@@ -114,7 +114,7 @@ def main():
         summ5 = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "prof_summary.py"), c5s, str(steps), "40"],
                                capture_output=True, text=True).stdout
         open(os.path.join(PROF, f"{TAG}_kernel_stats_bf16_config5_summary.txt"), "w").write(
-            "# rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --no-also --priming-seconds 0 --dtype bf16 "
+            "# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --no-also --priming-seconds 0 --dtype bf16 "
             f"--length 5000 --labels 1 --steps 20 --warmup 5 --priming 0  ({steps} steps incl. warm-up, the per-step-event repeat "
             "and the instrumented pass)\n" + summ5)
     lines = traffic_tables()
