@@ -144,7 +144,8 @@ int ecg_conv1d_bwd_weight_bias(const float *dy, const float *x, float *dw, float
  *   dp  gradient of p      bf16 [N][C][ldp] (ecg_conv1d_bwd_data_bf16hh of the next block) — read by ecg_bn_relu_pool_bwd_h
  * Parameters, statistics, parameter gradients, the network input (fp32, read by block 0 and rounded while it is staged) and
  * the tail stay fp32.  Everything that does not fit (eval / frozen BatchNorm, other kernel sizes or channel counts, an fp32
- * input that needs an input gradient) runs the fp32 entry points above: there is no second bf16 form.  (Rounds 2-4 also
+ * input that needs an input gradient) runs the fp32 entry points above: there is no second bf16 TRAINING form (bf16
+ * inference has entry points of its own: ecg_conv1d_bn_relu_pool_eval_fwd_bf16 below).  (Rounds 2-4 also
  * shipped fp32-activation variants and a sample-on-K weight gradient with its "n16" operand copies; removed in round 5.)
  * Packed weights are bf16: wb_fwd [ceil(C_in/16)][K][C_out][16], wb_bwd [ceil(C_out/16)][K][C_in][16]
  * (tap-flipped), ecg_conv1d_bf16_packed_elems(C_reduce, C_result, K) 2-byte elements each.
@@ -309,6 +310,35 @@ int ecg_conv1d_bn_relu_pool_gap_eval_fwd(const float *x, const float *w_fwd, con
                                          const float *running_mean, const float *running_var,
                                          float eps, float *g, int N, int C_in, int C_out, int L,
                                          int K, int pad, ecg_stream_t stream);
+
+/* Inference in bf16 (opt-in, inference_precision("bf16") of the Python package): the same whole ConvBlock in ONE launch
+ * with bf16 operands on the matrix cores (v_mfma_f32_32x32x16_bf16, fp32 accumulate; csrc/conv1d_bf16_eval.hip, the ring
+ * kernel of csrc/conv1d_bf16_ring.hip with an eval epilogue).  Eval BatchNorm is folded with the bias inside the launch:
+ * scale = gamma * rsqrt(running_var + eps), shift = beta + (bias - running_mean) * scale; then ReLU and MaxPool1d(2) (an odd
+ * Lo drops its last position).  Weights are the bf16 packed wb_fwd (ecg_conv1d_bf16_packed_elems(C_in, C_out, K), 16-byte
+ * aligned).  bias may be null; gamma, beta and the running statistics may not.
+ *   x: x_bf16 == 0: fp32 [N][C_in][L] (ldx ignored; L even, 8-byte aligned base, C_in <= 16: the network input, rounded to
+ *      bf16 while it is staged); x_bf16 != 0: bf16 [N][C_in][ldx], ldx even and >= L, rows zero-filled from L to ldx, 4-byte
+ *      aligned base (what the previous eval block wrote with p_bf16 != 0).
+ *   p: p_bf16 != 0: bf16 [N][C_out][ldp], ldp % 8 == 0, ldp >= Lo/2, 16-byte aligned; rows are zero-filled from Lo/2 to ldp
+ *      (the row contract of ecg_bn_stats_relu_pool_fwd_h).  p_bf16 == 0: fp32 [N][C_out][Lo/2] (ldp ignored).
+ *   g: the _gap_ form writes only g [N][C_out] = mean_j max(0, max(z[2j], z[2j+1])) in fp32 over the unrounded z.
+ * ecg_conv1d_bn_relu_pool_eval_bf16_supported is a pure host-side query: bit 0 = covered for a bf16 x, bit 1 = covered for
+ * an fp32 x.  It needs K == 15, odd pad, C_in % 4 == 0, C_out % 32 == 0 and a chunk count (ceil(C_in / 16)) the kernel
+ * tiles, a pooled row of at least one position, and for the _gap_ form a conv row that fits one workgroup tile
+ * (the largest tile the channel counts allow: Lo <= 1280 for the model's last block — 12x1000 and 12x5000 end at 125 and
+ * 625 — and Lo <= 512 for an fp32 x).  The entry points refuse (ECG_EINVAL) what the query refuses and what breaks the contracts above.  Each
+ * output sums over (chunk, tap) in a fixed order and nothing reduces across samples or workgroups: a sample's result is
+ * bitwise independent of N and of its position in the batch.  Multiplies per output pair: those of the bf16 forward. */
+int ecg_conv1d_bn_relu_pool_eval_bf16_supported(int C_in, int C_out, int L, int K, int pad, int gap);
+int ecg_conv1d_bn_relu_pool_eval_fwd_bf16(const void *x, int x_bf16, int ldx, const void *wb_fwd, const float *bias,
+                                          const float *gamma, const float *beta, const float *running_mean,
+                                          const float *running_var, float eps, void *p, int p_bf16, int ldp, int N,
+                                          int C_in, int C_out, int L, int K, int pad, ecg_stream_t stream);
+int ecg_conv1d_bn_relu_pool_gap_eval_fwd_bf16(const void *x, int x_bf16, int ldx, const void *wb_fwd, const float *bias,
+                                              const float *gamma, const float *beta, const float *running_mean,
+                                              const float *running_var, float eps, float *g, int N, int C_in, int C_out,
+                                              int L, int K, int pad, ecg_stream_t stream);
 
 /* Last block of the backbone fused with AdaptiveAvgPool1d(1) (src/models/ecg_cnn.py:46,62):
  * g[n,c] = mean_j max(0, max(a[2j], a[2j+1])) — the pooled tensor is never materialised.

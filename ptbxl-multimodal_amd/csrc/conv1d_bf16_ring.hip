@@ -111,11 +111,20 @@ constexpr int commit_tap(int cb, int GT) {
 // tile is 75 MFMAs per wave against an epilogue of comparable length, and two independent workgroups fill each other's
 // epilogues (in-kernel stamps with one 1280-step workgroup per CU: taps 5.4 us, epilogue 2.9 us per tile, matrix pipe
 // idle in the latter).
-template <int CO_T, int WCO, int WT, int MT, bool STATS, int RES_CH, bool XF32 = false>
+// EPI: what the epilogue writes.  EPI_Y = the train-mode conv output y (bf16 [N][Cout][ldyo], + statistics with STATS);
+// the eval forms fold eval BatchNorm (scale / shift from the running statistics and the bias, computed in the prologue:
+// one lane = one channel), ReLU and MaxPool(2) into it — a pool pair is two neighbouring accumulator registers of a lane —
+// and write only the pooled row: EPI_PH bf16 [N][Cout][ldyo] zero-filled from Lo/2 to ldyo, EPI_PF fp32 [N][Cout][Lo/2]
+// (ev.out), EPI_GAP the global average of the pooled row, fp32 [N][Cout] (ev.out; a row is ONE tile: tiles_t == 1).
+enum { EPI_Y = 0, EPI_PH = 1, EPI_PF = 2, EPI_GAP = 3 };
+struct EvalArgs { const float *gamma, *beta, *mean, *var; float eps; float *out; };
+
+template <int CO_T, int WCO, int WT, int MT, bool STATS, int RES_CH, bool XF32 = false, int EPI = EPI_Y>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 4 : 2))) void conv1d_bf16_ring_kernel(
     const void *__restrict__ xv, const u16 *__restrict__ wb, const float *__restrict__ bias, u16 *__restrict__ y,
     float *__restrict__ partials, int Cin, int Cout, int L, int Lo, int pad, int tiles_t, int N, int G, int P_stride,
-    int ldx, int ldyo) {
+    int ldx, int ldyo, EvalArgs ev) {
+    static_assert(EPI == EPI_Y || !STATS, "the eval epilogues take no statistics");
     static_assert(WCO * WT == NW, "eight waves");
     constexpr int MC = CO_T / WCO / 32;
     static_assert(MC == 1 || MC == 2, "one or two 32-channel groups per wave");
@@ -172,11 +181,16 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 4 
     // (accumulators that START from the bias would save that add, but a register splat is not rematerialisable: hipcc
     // then keeps the re-initialised accumulators of the next tile in scratch across the epilogue — 46 dependent scratch
     // reloads per tile, 30-60 us; zeros are immediates)
-    float bia[MC], st_s[MC], st_q[MC];
+    float bia[MC], st_s[MC], st_q[MC], bsc[MC], bsh[MC];
 #pragma unroll
     for (int i = 0; i < MC; ++i) {
         bia[i] = bias ? bias[co0 + wco + 32 * i + l31] : 0.f;
         st_s[i] = 0.f; st_q[i] = 0.f;
+        if constexpr (EPI != EPI_Y) {                    // eval BatchNorm folded with the bias: z = acc * scale + shift
+            const int c = co0 + wco + 32 * i + l31;
+            bsc[i] = ev.gamma[c] * (1.0f / sqrtf(ev.var[c] + ev.eps));
+            bsh[i] = __fmaf_rn(bia[i] - ev.mean[c], bsc[i], ev.beta[c]);
+        }
     }
     f32x16 acc[MC][MT];
 #pragma unroll
@@ -306,7 +320,96 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 4 
     // wave-private 2.5 KB LDS patch ([32 channels][32 times] bf16, 80-byte rows) and leaves as two 16-byte-per-lane
     // stores: 16 rows x 64 contiguous bytes per instruction.  The patch lives in the x image of the tile's LAST chunk,
     // which nobody reads any more once the workgroup has passed the barrier in front of the epilogue.
+    // Eval forms: per accumulator (32 channels x 32 times) a lane holds 8 pooled values, positions 4 g4 + 2 half + {0, 1} of
+    // the accumulator's 16; pooled positions >= Lo/2 (the tile's tail, an odd Lo's last step) are 0.  EPI_PH / EPI_PF take
+    // the same trip through the wave's LDS patch as y does ([32 channels][16 pooled], 32 / 64 bytes a row) and leave as
+    // 16-byte stores (bf16) or bounds-checked 4-byte ones (fp32 rows of Lo/2, no alignment).  EPI_GAP sums the pooled
+    // values of a lane in a fixed order, adds the two halves of the wave, then the WT waves of a channel in wave order
+    // (LDS, inside the workgroup): the sum of an output never depends on the batch, on scheduling, or on atomics.
+    auto epilogue_eval = [&](int n, int tt, int img_off) __attribute__((always_inline)) {
+        const int pt0 = tt * T_T + wt, Lp = Lo >> 1;
+        const int patch0 = EPB ? WAREA + 2 * XB : img_off;
+        const int patch = patch0 + wave * (32 * EPROW);
+        float gs[MC];
+        __builtin_amdgcn_s_barrier();                    // every wave has issued (and received) its last reads of this image
+#pragma unroll
+        for (int i = 0; i < MC; ++i) {
+            const int ch = co0 + wco + 32 * i;
+            float gsum = 0.f;
+#pragma unroll
+            for (int j = 0; j < MT; ++j) {
+                float pv[8];
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    float v[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = __fmaf_rn(acc[i][j][4 * g4 + e], bsc[i], bsh[i]);
+                    const int pp = (pt0 + 32 * j + 8 * g4 + 4 * half) >> 1;
+                    const float a = fmaxf(fmaxf(v[0], v[1]), 0.f), b = fmaxf(fmaxf(v[2], v[3]), 0.f);
+                    pv[2 * g4] = pp < Lp ? a : 0.f;
+                    pv[2 * g4 + 1] = pp + 1 < Lp ? b : 0.f;
+                }
+                if constexpr (EPI == EPI_GAP) {
+                    gsum += ((pv[0] + pv[1]) + (pv[2] + pv[3])) + ((pv[4] + pv[5]) + (pv[6] + pv[7]));
+                } else if constexpr (EPI == EPI_PH) {
+#pragma unroll
+                    for (int g4 = 0; g4 < 4; ++g4)
+                        *reinterpret_cast<unsigned *>(&lds[patch + l31 * EPROW + 8 * g4 + 4 * half]) =
+                            (unsigned)__builtin_bit_cast(u16, (__bf16)pv[2 * g4]) |
+                            ((unsigned)__builtin_bit_cast(u16, (__bf16)pv[2 * g4 + 1]) << 16);
+                    const uint4 o = *reinterpret_cast<const uint4 *>(&lds[patch + (lane >> 1) * EPROW + 16 * (lane & 1)]);
+                    const int pos = (pt0 >> 1) + 16 * j + 8 * (lane & 1);     // ldyo % 8 == 0: 8 positions in or out
+                    if (pos < ldyo) *reinterpret_cast<uint4 *>(y + ((size_t)n * Cout + ch + (lane >> 1)) * ldyo + pos) = o;
+                } else {
+#pragma unroll
+                    for (int g4 = 0; g4 < 4; ++g4)
+                        *reinterpret_cast<float2 *>(&lds[patch + l31 * EPROW + 16 * g4 + 8 * half]) =
+                            make_float2(pv[2 * g4], pv[2 * g4 + 1]);
+                    const int rd = patch + (lane >> 1) * EPROW + 32 * (lane & 1);
+                    const float4 o0 = *reinterpret_cast<const float4 *>(&lds[rd]);
+                    const float4 o1 = *reinterpret_cast<const float4 *>(&lds[rd + 16]);
+                    const float o[8] = {o0.x, o0.y, o0.z, o0.w, o1.x, o1.y, o1.z, o1.w};
+                    const int pos = (pt0 >> 1) + 16 * j + 8 * (lane & 1);
+                    float *prow = ev.out + ((size_t)n * Cout + ch + (lane >> 1)) * Lp;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e)
+                        if (pos + e < Lp) prow[pos + e] = o[e];
+                }
+                __builtin_amdgcn_sched_barrier(0);       // one accumulator at a time
+            }
+            gs[i] = gsum;
+#pragma unroll
+            for (int j = 0; j < MT; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+        }
+        if constexpr (EPI == EPI_GAP) {
+            float *red = reinterpret_cast<float *>(&lds[patch0]);
+#pragma unroll
+            for (int i = 0; i < MC; ++i) {
+                const float s = gs[i] + __shfl_xor(gs[i], 32, 64);
+                if (half == 0) red[wave * (CO_T / WCO) + 32 * i + l31] = s;
+            }
+            __syncthreads();
+            // (the next writes of this area follow a barrier that every reader passes after using its values)
+            for (int c = tid; c < CO_T; c += NT) {
+                const int wrow = c / (CO_T / WCO), lc2 = c - wrow * (CO_T / WCO);
+                float s = 0.f;
+#pragma unroll
+                for (int j = 0; j < WT; ++j) s += red[(wrow * WT + j) * (CO_T / WCO) + lc2];
+                ev.out[(size_t)n * Cout + co0 + c] = s / (float)Lp;
+            }
+        }
+        if constexpr (EPI == EPI_PH) {                   // a row stride past the last tile (not what the library's callers
+            if (tt == tiles_t - 1) {                     // allocate): zero-fill it too
+                const int pc = tiles_t * (T_T / 2), w = ldyo - pc;
+                for (int e = tid; e < CO_T * w; e += NT)
+                    y[((size_t)n * Cout + co0 + e / w) * ldyo + pc + e % w] = 0;
+            }
+        }
+    };
     auto epilogue = [&](int n, int tt, int img_off) __attribute__((always_inline)) {
+        if constexpr (EPI != EPI_Y) { epilogue_eval(n, tt, img_off); return; }
         const int pt0 = tt * T_T + wt;
         const bool full = pt0 + MT * 32 <= Lo;           // wave-uniform: no masks, no store predicates
         const int patch = (EPB ? WAREA + 2 * XB : img_off) + wave * (32 * EPROW);
@@ -614,20 +717,54 @@ int bf16_ring_launch(const RingPlan &p, const void *x, int ldx, const void *wb, 
     u16 *yh = static_cast<u16 *>(y);
 #define ECG_RING(CO, WCO_, WT_, STATS_, RES_)                                                                        \
     hipLaunchKernelGGL((conv1d_bf16_ring_kernel<CO, WCO_, WT_, 5, STATS_, RES_>), grid, block, 0, st, xh, w, bias, yh, \
-                       partials, Cin, Cout, L, Lo, pad, tiles_t, N, p.G, P_stride, ldx, ldyo)
+                       partials, Cin, Cout, L, Lo, pad, tiles_t, N, p.G, P_stride, ldx, ldyo, EvalArgs{})
     if (p.xf32) {
         if (partials)
             hipLaunchKernelGGL((conv1d_bf16_ring_kernel<32, 1, 8, 2, true, 1, true>), grid, block, 0, st, xh, w, bias, yh,
-                               partials, Cin, Cout, L, Lo, pad, tiles_t, N, p.G, P_stride, ldx, ldyo);
+                               partials, Cin, Cout, L, Lo, pad, tiles_t, N, p.G, P_stride, ldx, ldyo, EvalArgs{});
         else
             hipLaunchKernelGGL((conv1d_bf16_ring_kernel<32, 1, 8, 2, false, 1, true>), grid, block, 0, st, xh, w, bias, yh,
-                               partials, Cin, Cout, L, Lo, pad, tiles_t, N, p.G, P_stride, ldx, ldyo);
+                               partials, Cin, Cout, L, Lo, pad, tiles_t, N, p.G, P_stride, ldx, ldyo, EvalArgs{});
     } else if (p.co_t == 128) { if (partials) ECG_RING(128, 2, 4, true, 0); else ECG_RING(128, 2, 4, false, 0); }
     else if (p.co_t == 64 && p.res_ch) { if (partials) ECG_RING(64, 1, 8, true, 2); else ECG_RING(64, 1, 8, false, 2); }
     else if (p.co_t == 64) { if (partials) ECG_RING(64, 1, 8, true, 0); else ECG_RING(64, 1, 8, false, 0); }
     else { if (partials) ECG_RING(32, 1, 8, true, 4); else ECG_RING(32, 1, 8, false, 4); }
 #undef ECG_RING
     return check_launch("conv1d_bf16_ring_kernel");
+}
+
+// ---- eval ConvBlock (conv1d_bf16_eval.hip: plan and entry points) ------------------------------------------------------
+// The same kernel with an eval epilogue.  Configurations (CO_T, WCO, WT, MT, RES_CH) by tile length T_T = WT * MT * 32; the
+// plan picks, among those the channel counts allow, the tile that pads the row least (12x1000 rows are 125-1000 long).
+int bf16_eval_launch(const RingPlan &p, int epi, const void *x, int ldx, const void *wb, const float *gamma,
+                     const float *beta, const float *mean, const float *var, float eps, const float *bias, void *p_bf16,
+                     int ldp, float *out, int N, int Cin, int Cout, int L, int Lo, int pad, hipStream_t st) {
+    using namespace ring;
+    const int tiles_t = cdiv(Lo, p.t_t);
+    dim3 grid((unsigned)((Cout / p.co_t) * p.G)), block(NT);
+    const EvalArgs ev{gamma, beta, mean, var, eps, out};
+    const u16 *w = static_cast<const u16 *>(wb);
+    u16 *yh = static_cast<u16 *>(p_bf16);
+#define ECG_EVAL1(CO, WCO_, WT_, MT_, RES_, XF_, E)                                                                    \
+    hipLaunchKernelGGL((conv1d_bf16_ring_kernel<CO, WCO_, WT_, MT_, false, RES_, XF_, E>), grid, block, 0, st, x, w, bias, \
+                       yh, nullptr, Cin, Cout, L, Lo, pad, tiles_t, N, p.G, 0, ldx, ldp, ev)
+#define ECG_EVAL(CO, WCO_, WT_, MT_, RES_, XF_)                                                                        \
+    do {                                                                                                             \
+        if (epi == EPI_PH) ECG_EVAL1(CO, WCO_, WT_, MT_, RES_, XF_, EPI_PH);                                         \
+        else if (epi == EPI_PF) ECG_EVAL1(CO, WCO_, WT_, MT_, RES_, XF_, EPI_PF);                                    \
+        else ECG_EVAL1(CO, WCO_, WT_, MT_, RES_, XF_, EPI_GAP);                                                      \
+    } while (0)
+    if (p.xf32) ECG_EVAL(32, 1, 8, 2, 1, true);
+    else if (p.co_t == 128 && p.t_t == 640) ECG_EVAL(128, 2, 4, 5, 0, false);
+    else if (p.co_t == 128 && p.t_t == 256) ECG_EVAL(128, 4, 2, 4, 0, false);
+    else if (p.co_t == 128) ECG_EVAL(128, 4, 2, 2, 0, false);
+    else if (p.co_t == 64 && p.res_ch && p.t_t == 1280) ECG_EVAL(64, 1, 8, 5, 2, false);
+    else if (p.co_t == 64 && p.res_ch) ECG_EVAL(64, 2, 4, 4, 2, false);
+    else if (p.co_t == 64) ECG_EVAL(64, 1, 8, 5, 0, false);
+    else ECG_EVAL(32, 1, 8, 5, 4, false);
+#undef ECG_EVAL
+#undef ECG_EVAL1
+    return check_launch("conv1d_bf16_ring_kernel (eval)");
 }
 
 }  // namespace ecg

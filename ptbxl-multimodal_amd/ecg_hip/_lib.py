@@ -65,6 +65,9 @@ SIGNATURES = {
     "ecg_conv1d_bn_relu_pool_eval_fwd": (_i, [_vp] * 7 + [_f, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "ecg_conv1d_bn_relu_pool_gap_eval_supported": (_i, [_i] * 5),
     "ecg_conv1d_bn_relu_pool_gap_eval_fwd": (_i, [_vp] * 7 + [_f, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "ecg_conv1d_bn_relu_pool_eval_bf16_supported": (_i, [_i] * 6),
+    "ecg_conv1d_bn_relu_pool_eval_fwd_bf16": (_i, [_vp, _i, _i] + [_vp] * 6 + [_f, _vp, _i, _i] + [_i] * 6 + [_vp]),
+    "ecg_conv1d_bn_relu_pool_gap_eval_fwd_bf16": (_i, [_vp, _i, _i] + [_vp] * 6 + [_f, _vp] + [_i] * 6 + [_vp]),
     "ecg_bn_relu_pool_gap_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "ecg_bn_relu_pool_gap_bwd": (_i, [_vp] * 10 + [_i, _i, _i, _i, _vp]),
     "ecg_bn_relu_pool_gap_bwd_ld": (_i, [_vp] * 7 + [_i] + [_vp] * 3 + [_i, _i, _i, _i, _vp]),

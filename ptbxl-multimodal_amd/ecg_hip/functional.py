@@ -7,6 +7,7 @@ the ones restated (and pinned against the reference) in oracle/ecg_oracle.c.
 import torch
 
 from . import _lib as L
+from . import eval_bf16 as _EB
 
 _call, _query, _f32, _st = L.call, L.query, L.f32, L.stream
 
@@ -199,7 +200,7 @@ def conv1d_pack(w, need_bwd=True):
 # block, dY and the input gradient handed back — while parameters, statistics, gradients of parameters, the network
 # input, the tail and the optimizer stay fp32.  A block that does not fit that form (frozen or eval-mode BatchNorm, no
 # gradient wanted, other kernel sizes or channel counts) runs the exact fp32 kernels instead, and tensors crossing between the
-# two forms are fp32: inference is always the fp32 one-launch path.
+# two forms are fp32.  Inference has its own knob, below.
 # ECG_HIP_CONV_PRECISION sets the process default.
 # --------------------------------------------------------------------------------------
 _conv_precision = _os.environ.get("ECG_HIP_CONV_PRECISION", "fp32")
@@ -228,6 +229,36 @@ class conv_precision:
 
     def __exit__(self, *exc):
         set_conv_precision(self.prev)
+        return False
+
+
+# Inference precision: "fp32" (default: the exact one-launch eval blocks) or "bf16" (opt-in): an eval ConvBlock (running
+# statistics, no gradient wanted) whose geometry the bf16 eval kernel covers runs as ONE launch on bf16 operands with the
+# BatchNorm fold, ReLU and pool in the epilogue (ecg_hip/eval_bf16.py), and hands bf16 rows to the next such block.
+# Independent of conv_precision.  ECG_HIP_INFERENCE_PRECISION sets the process default.
+_inference_precision = _os.environ.get("ECG_HIP_INFERENCE_PRECISION", "fp32")
+
+
+def set_inference_precision(mode):
+    global _inference_precision
+    if mode not in ("fp32", "bf16"):
+        raise ValueError("inference precision must be 'fp32' or 'bf16'")
+    _inference_precision = mode
+
+
+def get_inference_precision():
+    return _inference_precision
+
+
+class inference_precision(conv_precision):
+    """Context manager: `with inference_precision("bf16"): model.eval()(x)` under torch.no_grad()."""
+
+    def __enter__(self):
+        self.prev = get_inference_precision()
+        set_inference_precision(self.mode)
+
+    def __exit__(self, *exc):
+        set_inference_precision(self.prev)
         return False
 
 
@@ -266,7 +297,8 @@ class WeightPacker:
         same launch (one launch per step instead of one per layer plus the fp32 one)."""
         srcs = [c.weight for c in convs] + [l.weight for l in linears]
         mixed = _conv_precision == "bf16" and bool(need_bwd)       # (without gradients every block runs the fp32 kernels)
-        key = (need_bwd, mixed) + tuple((w.data_ptr(), tuple(w.shape)) for w in srcs)
+        infer = _inference_precision == "bf16" and not need_bwd     # bf16 eval blocks: wb_fwd only
+        key = (need_bwd, mixed, infer) + tuple((w.data_ptr(), tuple(w.shape)) for w in srcs)
         if key != self._key:
             self._key = key
             self.conv_packs, self.linear_T, fw, bw, hf, hb, co, ci, kk = [], [], [], [], [], [], [], [], []
@@ -276,7 +308,8 @@ class WeightPacker:
                 want_bwd = need_bwd and i > 0                # block 0 has no input-grad
                 # (bf16 operands for a conv whose geometry fits the mixed-precision form; whether the block really takes it
                 # is decided per call — a block that does not repacks its fp32 operands itself, ConvBlockFn._weights)
-                if mixed and _bf16_block_ok(Ci, Co, K, c.padding[0], 16, want_bwd):
+                if (mixed and _bf16_block_ok(Ci, Co, K, c.padding[0], 16, want_bwd)) or (infer and _EB.packable(Ci, Co, K,
+                                                                                                    c.padding[0])):
                     wf = wb = None
                     hwf = torch.empty(_query("ecg_conv1d_bf16_packed_elems", Ci, Co, K), dtype=torch.bfloat16, device=w.device)
                     hwb = (torch.empty(_query("ecg_conv1d_bf16_packed_elems", Co, Ci, K), dtype=torch.bfloat16,
@@ -379,7 +412,7 @@ def _bf16_block_ok(Ci, Co, K, pad, Lin, need_dx):
     return bool((sup & 1) and (sup & 4) and (not need_dx or (sup & 2)) and Lin + 2 * pad - K + 1 >= 2)
 
 
-_EVAL, _FP32, _BF16 = "eval", "fp32", "bf16"
+_EVAL, _FP32, _BF16, _EVAL_BF16 = "eval", "fp32", "bf16", "eval_bf16"
 
 
 class ConvBlockFn(torch.autograd.Function):
@@ -388,6 +421,7 @@ class ConvBlockFn(torch.autograd.Function):
     reused by backward:
       eval   inference (running statistics, no gradient wanted): conv + folded BN + ReLU + pool [+ GAP] in one launch
       bf16   the mixed-precision training form (set_conv_precision("bf16"), see _bf16_block_ok): bf16 rows between the kernels
+      eval_bf16  inference under set_inference_precision("bf16") where the bf16 eval kernel covers the block: one launch
       fp32   everything else — the parity path"""
 
     @staticmethod
@@ -413,13 +447,18 @@ class ConvBlockFn(torch.autograd.Function):
             mode = _BF16
         elif not use_batch and not need_grad:
             mode = _EVAL
-        if x_h and mode != _BF16:
+            if _inference_precision == "bf16" and _EB.takes(x, Ci, Co, K, pad, Lin, gap):
+                mode = _EVAL_BF16
+        if x_h and mode not in (_BF16, _EVAL_BF16):
             # the producer wrote p as bf16 because this block looked able to read it: the precision was switched, or a
             # BatchNorm frozen, between the two calls
             raise L.EcgHipError("ConvBlock: input arrived as a bf16 activation but this block does not take the mixed-"
                                 "precision form (conv precision / BatchNorm mode changed between blocks?)")
         ctx.mode, ctx.pad, ctx.gap, ctx.batch_stats, ctx.Lin, ctx.Lo = mode, pad, gap, use_batch, Lin, Lo
         ctx.sink_keys = (_key(w), _key(b), _key(gamma), _key(beta))
+        if mode == _EVAL_BF16:
+            wb, _ = ConvBlockFn._weights(w, packed, True, False)
+            return _EB.forward(x, wb, w.shape, b, gamma, beta, running_mean, running_var, eps, pad, gap, Lin, next_bf16)
         if mode == _EVAL:
             p = ConvBlockFn._fwd_eval(x, w, b, gamma, beta, running_mean, running_var, eps, pad, gap, packed)
             if p is not None:
@@ -669,18 +708,27 @@ def conv_block(x, conv, bn, gap=False, packed=None):
     return conv_block_chain(x, conv, bn, gap, packed)[0]
 
 
-def conv_block_chain(x, conv, bn, gap=False, packed=None, carry=None, next_conv=None, next_bn=None):
-    """conv_block for a chain of blocks: returns (p, carry).  In the mixed-precision form p is a bf16 activation
-    [N][C][ld] (rows zero-filled past the pooled length) when the NEXT block of the chain (next_conv / next_bn given) takes
-    that form too; the carry is then the true pooled length, to be handed to the next call — only the next block of the
-    chain may consume such a tensor."""
+def conv_block_chain(x, conv, bn, gap=False, packed=None, carry=None, next_conv=None, next_bn=None, next_gap=False):
+    """conv_block for a chain of blocks: returns (p, carry).  In the mixed-precision form and the bf16 inference form p is
+    a bf16 activation [N][C][ld] (rows zero-filled past the pooled length) when the NEXT block of the chain (next_conv /
+    next_bn given; next_gap: it is the last one, with the global average pool) takes that form too; the carry is then the
+    true pooled length, to be handed to the next call — only the next block of the chain may consume such a tensor."""
     nxt = False
-    if next_conv is not None and _conv_precision == "bf16" and not gap:
+    if next_conv is not None and not gap:
         x_len = carry if x.dtype == torch.bfloat16 else x.shape[2]
         Lo = x_len + 2 * conv.padding[0] - conv.kernel_size[0] + 1
-        nxt = bool(next_bn is not None and (next_bn.training or next_bn.running_mean is None) and torch.is_grad_enabled()
-                   and _bf16_block_ok(conv.out_channels, next_conv.out_channels, next_conv.kernel_size[0],
-                                      next_conv.padding[0], Lo // 2, True))
+        nK, npad = next_conv.kernel_size[0], next_conv.padding[0]
+        if _conv_precision == "bf16":
+            nxt = bool(next_bn is not None and (next_bn.training or next_bn.running_mean is None)
+                       and torch.is_grad_enabled()
+                       and _bf16_block_ok(conv.out_channels, next_conv.out_channels, nK, npad, Lo // 2, True))
+        if not nxt and _inference_precision == "bf16" and not torch.is_grad_enabled():
+            # this block and the next both take the bf16 eval form
+            nxt = bool(not (bn.training or bn.running_mean is None) and next_bn is not None
+                       and not (next_bn.training or next_bn.running_mean is None)
+                       and _EB.takes(x, conv.in_channels, conv.out_channels, conv.kernel_size[0], conv.padding[0], x_len,
+                                     False)
+                       and _EB.covered(conv.out_channels, next_conv.out_channels, nK, npad, Lo // 2, next_gap, True))
     p = ConvBlockFn.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
                           bn.num_batches_tracked, bn.training, bn.momentum, bn.eps, conv.padding[0], gap, packed,
                           torch.is_grad_enabled(), carry, nxt)

@@ -68,7 +68,7 @@ def fused_forward(packer, backbone, gap, x, x_demo, proj, head, mlp0=None, mlp2=
         last = i == len(blocks) - 1
         x, carry = hipF.conv_block_chain(x, blk.net[0], blk.net[1], gap=last, packed=packs[i], carry=carry,
                                       next_conv=None if last else blocks[i + 1].net[0],
-                                      next_bn=None if last else blocks[i + 1].net[1])
+                                      next_bn=None if last else blocks[i + 1].net[1], next_gap=i + 2 == len(blocks))
     return hipF.tail(x, x_demo, proj, head, mlp0, mlp2, film_gen, transposed=transposed)
 
 
@@ -78,6 +78,11 @@ def backbone_features(backbone: nn.Sequential, gap: nn.Module, x: torch.Tensor) 
     last pooled activation is never written to HBM."""
     blocks = list(backbone)
     last = blocks[-1]
+    with hipF.inference_precision("fp32"):   # the hook-compatible path keeps the fp32 blocks (Grad-CAM); bf16: fused_forward
+        return _backbone_features(blocks, last, backbone, gap, x)
+
+
+def _backbone_features(blocks, last, backbone, gap, x):
     if (x.is_cuda and isinstance(last, ConvBlock) and last._fusable and x.dim() == 3
             and not hipnn.has_hooks(backbone, gap, *blocks, last.net, *last.net)):
         for blk in blocks[:-1]:

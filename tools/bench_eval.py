@@ -1,10 +1,11 @@
 """Inference throughput of the path: eval-mode forward + sigmoid, one launch
 per ConvBlock (conv + running-stat BatchNorm + ReLU + MaxPool folded into the conv epilogue).
 
-    python tools/bench_eval.py [--batch 256] [--length 1000 5000] [--iters 50]
+    python tools/bench_eval.py [--batch 256] [--length 1000 5000] [--iters 50] [--precision fp32|bf16]
 
 One JSON line per (model, window length): windows/s with inputs resident in HBM, per-entry-point times
-from HIP events, and the conv forward's fraction of the fp32 MFMA peak.
+from HIP events, and the conv forward's fraction of the fp32 MFMA peak (--precision bf16: the opt-in bf16
+inference form, inference_precision("bf16"), and the fraction of the dense bf16 MFMA peak).
 """
 import argparse
 import json
@@ -17,6 +18,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "ptbxl-multimodal_amd")]
 PEAK_F32_TFLOPS = 157.3
+PEAK_BF16_TFLOPS = 2500.0
 
 
 def conv_fwd_flops(T):
@@ -32,6 +34,7 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--length", type=int, nargs="*", default=[1000, 5000])
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32")
     a = ap.parse_args()
     from ecg_hip import _lib
     from ecg_hip import functional as F
@@ -39,6 +42,8 @@ def main():
     from src.models.ecg_multimodal import ECGMultimodal
     from src.utils.seed import set_seed
     _lib.call("ecg_check_device")
+    F.set_inference_precision(a.precision)
+    bf16 = a.precision == "bf16"
     B = a.batch
     for T in a.length:
         for name in ("ECGCNN(5)", "ECGMultimodal"):
@@ -72,12 +77,16 @@ def main():
                     step()
             per = sorted(((f"{n}{list(s)}", float(np.mean(v))) for (n, s), v in kt.result.items()), key=lambda kv: -kv[1])
             val = B / (ms * 1e-3)
-            print(json.dumps({
+            line = {
                 "metric": "inference_windows_per_s", "value": round(val, 1), "unit": "windows/s", "ms_per_batch": round(ms, 4),
-                "dtype": "f32", "data": "synthetic",
-                "config": {"workload": f"{name} eval forward + sigmoid, 12x{T} fp32, batch {B}, fused conv+BN+ReLU+pool per block"},
-                "conv_frac_of_fp32_peak": round(val * conv_fwd_flops(T) / 1e12 / PEAK_F32_TFLOPS, 4),
-                "entry_point_ms": {k: round(v, 4) for k, v in per[:8]}}), flush=True)
+                "dtype": "bf16" if bf16 else "f32", "data": "synthetic",
+                "config": {"workload": f"{name} eval forward + sigmoid, 12x{T} {a.precision}, batch {B}, fused conv+BN+ReLU+pool per block"}}
+            if bf16:
+                line["conv_frac_of_bf16_peak"] = round(val * conv_fwd_flops(T) / 1e12 / PEAK_BF16_TFLOPS, 4)
+            else:
+                line["conv_frac_of_fp32_peak"] = round(val * conv_fwd_flops(T) / 1e12 / PEAK_F32_TFLOPS, 4)
+            line["entry_point_ms"] = {k: round(v, 4) for k, v in per[:8]}
+            print(json.dumps(line), flush=True)
 
 
 if __name__ == "__main__":
