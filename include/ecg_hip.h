@@ -355,6 +355,37 @@ int ecg_bn_relu_pool_gap_bwd_ld(const float *y, const float *dg, const float *ga
                                 float *dy, int ldy, float *dgamma, float *dbeta, float *ws,
                                 int N, int C, int L, int train, ecg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * Grad-CAM at the last Conv1d — replaces the hooked forward + full autograd backward of
+ * GradCAM1D.generate_cam (src/interpretability/grad_cam_1d.py:54-101) and of compute_gradcam in
+ * scripts/12_grad_cam_ecg_demo.py for a whole batch and K classes per sample in ONE launch, without
+ * a backward pass: behind that conv the model is eval BatchNorm -> ReLU -> MaxPool1d(2) -> mean ->
+ * linear map(s), so d logit_k / d A is u[k][c] * scale[c] / Lp on the arg-max of every pool pair whose
+ * maximum is positive and 0 elsewhere (csrc/gradcam.hip, DESIGN.md "Grad-CAM").
+ *   a      [N][C][lda], lda >= Lo: output of the target Conv1d, bias included
+ *   scale, shift [C]: the eval BatchNorm folded, z = a*scale + shift (scale may be negative)
+ *   u      d logit_k / d g.  u_stride_n == 0: [K][C] shared by all samples (ECGCNN); otherwise
+ *          [N][K][C] with that sample stride in floats (ECGMultimodal, or one class per sample)
+ *   S      output length: S == Lo copies; otherwise F.interpolate(mode="linear", align_corners=False)
+ *   norm   0: none (raw, after ReLU)
+ *          1: min-max BEFORE resampling, divided only if max > 0     (GradCAM1D._normalize_cam)
+ *          2: min-max AFTER resampling, divided by (max + 1e-8)      (scripts/12 compute_gradcam)
+ *   cam    [N][K][S]                 (required)
+ *   raw    [N][K][Lo]  nullable: relu(sum_c alpha*a) before normalisation
+ *   alpha  [N][K][C]   nullable: the channel weights (GradCAM1D's `weights`)
+ *   g      [N][C]      nullable: mean_j max(0, max(z[2j], z[2j+1])), the input of the tail, so that the
+ *                      logits of the same call need no second pass over the block
+ *   ws     ecg_gradcam_ws_floats(N, C, Lo, K, S) floats; may be NULL when raw is given
+ * Covered (ecg_gradcam_supported): C % 32 == 0, 32 <= C <= 256, 2 <= Lo <= 5792, 1 <= K <= 8,
+ * S >= 1; odd Lo drops its last position from the pool as MaxPool1d(2) does.  Fixed summation
+ * order, no atomics: the result of a sample does not depend on N, on its position in the batch or on K.
+ * ---------------------------------------------------------------------------------- */
+int ecg_gradcam_supported(int C, int Lo, int K, int S);
+size_t ecg_gradcam_ws_floats(int N, int C, int Lo, int K, int S);
+int ecg_gradcam_fwd(const float *a, int lda, const float *scale, const float *shift, const float *u,
+                    long long u_stride_n, float *cam, float *raw, float *alpha, float *g, float *ws,
+                    int N, int C, int Lo, int K, int S, int norm, ecg_stream_t stream);
+
 /* Unfused leaves (used when a caller hooks an inner module, e.g. Grad-CAM on net[0]:
  * scripts/00_demo_inference.py:36-37). */
 int ecg_bn_apply_fwd(const float *y, const float *gamma, const float *beta, const float *mean,

@@ -6,7 +6,15 @@ kernels of libecg_hip.so (include/ecg_hip.h) through `ecg_hip.functional`;
 one-collective-per-step data-parallel wrapper.  CUDA(HIP) tensors always take the HIP kernels
 (a missing shared library raises `EcgHipError`, never a silent fallback); CPU tensors take the
 stock torch layers the modules inherit from, as the reference does on a GPU-less box.
+`ecg_hip.grad_cam` is batched Grad-CAM at the last Conv1d: a closed form on the GPU, the hook algorithm elsewhere.
 """
 from ._lib import EcgHipError, LIB_PATH, load  # noqa: F401
 
-__all__ = ["EcgHipError", "LIB_PATH", "load"]
+
+def grad_cam(*args, **kwargs):
+    """ecg_hip.gradcam.grad_cam (imported on first use: the module needs the model classes, which import this package)."""
+    from .gradcam import grad_cam as _grad_cam
+    return _grad_cam(*args, **kwargs)
+
+
+__all__ = ["EcgHipError", "LIB_PATH", "load", "grad_cam"]

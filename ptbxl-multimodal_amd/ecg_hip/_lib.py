@@ -71,6 +71,9 @@ SIGNATURES = {
     "ecg_bn_relu_pool_gap_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "ecg_bn_relu_pool_gap_bwd": (_i, [_vp] * 10 + [_i, _i, _i, _i, _vp]),
     "ecg_bn_relu_pool_gap_bwd_ld": (_i, [_vp] * 7 + [_i] + [_vp] * 3 + [_i, _i, _i, _i, _vp]),
+    "ecg_gradcam_supported": (_i, [_i] * 4),
+    "ecg_gradcam_ws_floats": (_sz, [_i] * 5),
+    "ecg_gradcam_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _ll] + [_vp] * 5 + [_i] * 6 + [_vp]),
     "ecg_bn_apply_fwd": (_i, [_vp] * 6 + [_i, _i, _i, _vp]),
     "ecg_bn_bwd_ws_floats": (_sz, [_i, _i, _i]),
     "ecg_bn_bwd": (_i, [_vp] * 9 + [_i, _i, _i, _i, _vp]),

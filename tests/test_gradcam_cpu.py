@@ -1,0 +1,194 @@
+"""Grad-CAM without a GPU: the GradCAM1D drop-in and ecg_hip.grad_cam on CPU tensors (the hook algorithm) against the
+reference's own CAMs (tests/golden/g9_gradcam.npz), the float64 closed form of tests/gradcam_ref.py against the same
+fixture, and the host-side validation of the ecg_gradcam_* entry points."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import gradcam_ref as GR
+from util import golden, sd_from_npz
+
+MODELS = {"baseline": 5, "af": 1, "multimodal": 5}
+ZERO_CAMS = 3          # multimodal (window, class) pairs whose CAM is identically zero (class 2 of every window)
+
+
+def _model(name):
+    from src.models.ecg_cnn import ECGCNN
+    from src.models.ecg_multimodal import ECGMultimodal
+    m = ECGMultimodal() if name == "multimodal" else ECGCNN(num_labels=MODELS[name])
+    m.load_state_dict(sd_from_npz(golden("g3_ckpt_" + name)), strict=True)
+    return m.eval()
+
+
+def _last(m):
+    bb = m.ecg_backbone.backbone if hasattr(m, "ecg_backbone") else m.backbone
+    return bb, bb[-1].net[0], bb[-1].net[1]
+
+
+def _inputs(T):
+    ga = golden("g3_eval_known_answer")
+    return torch.from_numpy(ga["ecg"][:, :, :T].copy()), torch.from_numpy(ga["demo"])
+
+
+def test_drop_in_imports_from_this_package_and_reproduces_the_reference_cams():
+    """scripts/11_grad_cam_ecg_baseline.py:12,111-112 with this package alone on the path."""
+    import sys
+    from src.interpretability.grad_cam_1d import GradCAM1D
+    import src.interpretability.grad_cam_1d as mod
+    pkg = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "ptbxl-multimodal_amd")
+    assert os.path.abspath(mod.__file__).startswith(pkg + os.sep)
+    assert not any(os.path.exists(os.path.join(p, "src", "interpretability", "grad_cam_1d.py"))
+                   for p in sys.path if p and not os.path.abspath(p).startswith(os.path.dirname(pkg))), \
+        "another checkout that carries src/interpretability is on the path"
+    g9 = golden("g9_gradcam")
+    for name in ("baseline", "af"):
+        model = _model(name)
+        model.train()                                   # the constructor puts it in eval mode, as the reference's does
+        target_layer = model.backbone[-1].net[0]
+        grad_cam = GradCAM1D(model, target_layer)
+        assert not model.training and grad_cam.model is model and grad_cam.target_layer is target_layer
+        assert grad_cam.activations is None and grad_cam.gradients is None
+        for T in (5000, 1000):
+            x, _ = _inputs(T)
+            for n in range(3):
+                for k in range(MODELS[name]):
+                    cam = grad_cam.generate_cam(x[n:n + 1], k)
+                    up = grad_cam.generate_cam(x[n:n + 1], k, signal_length=T)
+                    assert cam.shape == (T // 8,) and up.shape == (T,)
+                    assert grad_cam.activations.shape == grad_cam.gradients.shape == (1, 256, T // 8)
+                    np.testing.assert_allclose(cam.numpy(), g9[f"{name}_T{T}_cam"][n, k], atol=2e-6)
+                    np.testing.assert_allclose(up.numpy(), g9[f"{name}_T{T}_cam_up"][n, k], atol=2e-6)
+        assert not target_layer._forward_hooks and not target_layer._backward_hooks     # nothing left behind
+
+
+@pytest.mark.parametrize("name", list(MODELS))
+def test_float64_closed_form_matches_every_fixture_entry(name):
+    """No backward pass: stock-torch activations of the last Conv1d + the closed form give the reference's CAMs within 2e-5
+    (5x the worst float32-vs-float64 difference of the reference itself, 3.7e-6); CAMs that are all zero stay exactly zero."""
+    g9 = golden("g9_gradcam")
+    model = _model(name)
+    bb, conv, bn = _last(model)
+    scale, shift = GR.fold_bn(bn)
+    zeros = 0
+    for T in (5000, 1000):
+        x, demo = _inputs(T)
+        with torch.no_grad():
+            A = conv(bb[:-1](x)).numpy()
+        U = GR.tail_U(model, demo if name == "multimodal" else None)
+        cf = GR.closed_form(A, scale, shift, U)
+        p = f"{name}_T{T}_"
+        np.testing.assert_allclose(cf["margin"], g9[p + "margin"].min(), atol=2e-6)      # (z in fp32 there)
+        np.testing.assert_allclose(cf["pre"].max(-1), g9[p + "premax"], atol=2e-6)
+        np.testing.assert_allclose(cf["raw"], g9[p + "raw"], atol=2e-6)
+        dead = g9[p + "premax"] <= 0
+        assert np.all(cf["raw"][dead] == 0)
+        if name == "multimodal":                     # scripts/12: resample, then min-max with +1e-8
+            up = GR.finish(cf["raw"], T, 2)
+            assert np.all(up[dead] == 0) and np.all(g9[p + "cam_up"][dead] == 0)
+            zeros += int(dead.sum())
+        else:                                        # GradCAM1D: min-max, then resample
+            np.testing.assert_allclose(GR.finish(cf["raw"], T // 8, 1), g9[p + "cam"], atol=2e-5)
+            up = GR.finish(cf["raw"], T, 1)
+            assert not dead.any()
+        np.testing.assert_allclose(up, g9[p + "cam_up"], atol=2e-5)
+    if name == "multimodal":
+        assert zeros == 2 * ZERO_CAMS                # the same three (window, class) pairs at both lengths
+
+
+def test_resampling_rule_is_torchs():
+    rng = np.random.default_rng(3)
+    for Lo, S in [(2, 5), (63, 777), (125, 1000), (625, 5000), (1250, 1000), (7, 7)]:
+        v = rng.standard_normal((2, Lo)).astype(np.float32)
+        want = torch.nn.functional.interpolate(torch.from_numpy(v)[:, None].double(), size=S, mode="linear",
+                                               align_corners=False)[:, 0].numpy()
+        np.testing.assert_allclose(GR.resample(v, S), want, atol=2e-5)    # (indices in fp32 here, in float64 there)
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as g
+    from ecg_hip import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        g.build()
+    return _lib.load()
+
+
+def test_gradcam_entry_points_validate_on_the_host(lib):
+    assert lib.ecg_gradcam_supported(256, 125, 5, 1000) == 1 and lib.ecg_gradcam_supported(256, 625, 8, 5000) == 1
+    assert lib.ecg_gradcam_supported(32, 2, 1, 1) == 1 and lib.ecg_gradcam_supported(64, 2500, 8, 5000) == 1
+    assert lib.ecg_gradcam_supported(48, 125, 1, 125) == 0        # C % 32
+    assert lib.ecg_gradcam_supported(256, 1, 1, 1) == 0           # no pool pair
+    assert lib.ecg_gradcam_supported(256, 125, 0, 125) == 0 and lib.ecg_gradcam_supported(256, 125, 9, 125) == 0
+    assert lib.ecg_gradcam_supported(256, 125, 1, 0) == 0
+    assert lib.ecg_gradcam_ws_floats(256, 256, 125, 5, 1000) == lib.ecg_gradcam_ws_floats(256, 256, 125, 5, 1000) \
+        >= 256 * 5 * 125
+    assert lib.ecg_gradcam_ws_floats(1, 48, 125, 1, 125) == 0
+    one = 16          # a non-null address that is never dereferenced: validation fails first, nothing is launched
+
+    def fwd(a=one, lda=125, scale=one, shift=one, u=one, us=0, cam=one, raw=None, alpha=None, g=None, ws=one, N=2, C=256,
+            Lo=125, K=5, S=1000, norm=1):
+        return lib.ecg_gradcam_fwd(a, lda, scale, shift, u, us, cam, raw, alpha, g, ws, N, C, Lo, K, S, norm, None)
+    for kw, text in [(dict(a=None), b"null"), (dict(scale=None), b"null"), (dict(shift=None), b"null"),
+                     (dict(u=None), b"null"), (dict(cam=None), b"null"), (dict(ws=None), b"null"),
+                     (dict(lda=124), b"lda"), (dict(K=0), b"K=0"), (dict(S=0), b"S=0"), (dict(norm=3), b"norm"),
+                     (dict(norm=-1), b"norm"), (dict(N=0), b"N=0"), (dict(C=48), b"not covered"),
+                     (dict(us=100), b"u_stride_n")]:
+        assert fwd(**kw) == 1, kw                       # ECG_EINVAL
+        assert text in lib.ecg_last_error(), (kw, lib.ecg_last_error())
+    assert lib.ecg_version() == 100
+
+
+def _hooks(model):
+    return sum(len(m._forward_hooks) + len(m._backward_hooks) + len(m._forward_pre_hooks) for m in model.modules())
+
+
+@pytest.mark.parametrize("name", ["baseline", "multimodal"])
+def test_grad_cam_on_cpu_tensors_is_the_hook_algorithm_and_leaves_no_hooks(name):
+    import ecg_hip
+    from ecg_hip.gradcam import grad_cam
+    from src.interpretability.grad_cam_1d import GradCAM1D
+    assert ecg_hip.grad_cam.__doc__
+    g9 = golden("g9_gradcam")
+    T = 1000
+    model = _model(name)
+    x, demo = _inputs(T)
+    xd = demo if name == "multimodal" else None
+    gc = GradCAM1D(model, _last(model)[1])
+    ks = list(range(MODELS[name]))
+    cams, logits, raw = grad_cam(model, x, xd, class_idx=ks, signal_length=T, normalize="after" if xd is not None else
+                                 "before", return_logits=True, return_raw=True)
+    assert cams.shape == (3, len(ks), T) and raw.shape == (3, len(ks), T // 8) and _hooks(model) == 0
+    with torch.no_grad():
+        want = model(x, xd) if xd is not None else model(x)
+    np.testing.assert_allclose(logits.numpy(), want.numpy(), atol=1e-6)
+    np.testing.assert_allclose(cams.numpy(), g9[f"{name}_T{T}_cam_up"], atol=2e-5)
+    np.testing.assert_allclose(raw.numpy(), g9[f"{name}_T{T}_raw"], atol=2e-6)
+    batched = gc.generate_cams(x, ks, signal_length=T, x_demo=xd, normalize="after" if xd is not None else "before")
+    assert torch.equal(batched, cams) and _hooks(model) == 0
+    if xd is None:
+        for n in range(3):
+            for k in ks:
+                one = gc.generate_cam(x[n:n + 1], k, signal_length=T)
+                np.testing.assert_allclose(one.numpy(), cams[n, k].numpy(), atol=1e-6)    # B = 1 vs batched convolutions
+    # the four forms of class_idx
+    pred = logits.argmax(1)
+    by_int = grad_cam(model, x, xd, class_idx=ks[-1], signal_length=T)
+    by_vec = grad_cam(model, x, xd, class_idx=pred, signal_length=T)
+    by_pred = grad_cam(model, x, xd, class_idx="pred", signal_length=T)
+    all_b = grad_cam(model, x, xd, class_idx=ks, signal_length=T)
+    assert by_int.shape == by_vec.shape == by_pred.shape == (3, T)
+    assert torch.equal(by_vec, by_pred)
+    for n in range(3):
+        np.testing.assert_allclose(by_vec[n].numpy(), all_b[n, pred[n]].numpy(), atol=1e-6)
+    np.testing.assert_allclose(by_int.numpy(), all_b[:, -1].numpy(), atol=1e-6)
+    assert grad_cam(model, x, xd, class_idx=0).shape == (3, T // 8)
+    assert grad_cam(model, x, xd, class_idx=0, normalize=None, signal_length=T).min() >= 0
+    with pytest.raises(ValueError):
+        grad_cam(model.train(), x, xd)
+    model.eval()
+    from ecg_hip import EcgHipError
+    with pytest.raises(EcgHipError, match="CUDA"):
+        grad_cam(model, x, xd, fused=True)
+    assert _hooks(model) == 0
