@@ -25,27 +25,17 @@
 // Parity: tests/test_gpu_ops.py::test_bf16_ring_* (exact on bf16-rounded operands vs the oracle; statistics; ragged
 // rows; both weight modes), test_bf16_conv_full_size_config5_*.
 // Replaces the ATen work behind ConvBlock.net[0] (reference src/models/ecg_cnn.py:13) and its input gradient.
-#include "common.h"
+#include "mfma_util.h"
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
 
 namespace ecg {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-
-// in-kernel stamps of the diagnostic build (make STAMP=1; tools/stamp_ring.py): s_memtime at start / prologue done / first
-// tile's taps done / first tile's epilogue done / end of the workgroup
+// in-kernel stamps of the diagnostic build (make STAMP=1; tools/stamp_ring.py; ECG_STAMP_AT(g_stamps_r, slot), mfma_util.h):
+// s_memtime at start / prologue done / first tile's taps done / first tile's epilogue done / end of the workgroup
 #ifdef ECG_STAMP
 __device__ unsigned long long *g_stamps_r = nullptr;
-#define ECG_STAMPR_AT(slot) do { if (g_stamps_r && threadIdx.x == 0) { \
-    g_stamps_r[(size_t)blockIdx.x * 8 + (slot)] = __builtin_amdgcn_s_memtime(); \
-    if ((slot) == 0) g_stamps_r[(size_t)blockIdx.x * 8 + 7] = __builtin_amdgcn_s_memrealtime(); \
-    if ((slot) == 4) g_stamps_r[(size_t)blockIdx.x * 8 + 6] = __builtin_amdgcn_s_memrealtime(); } } while (0)
-#else
-#define ECG_STAMPR_AT(slot) do { } while (0)
 #endif
 
 namespace ring {
@@ -156,16 +146,12 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 4 
     __shared__ __attribute__((aligned(1024))) unsigned char lds[WAREA + 2 * XB + EPB];
     unsigned char *const xlds = lds + WAREA;
 
-    ECG_STAMPR_AT(0);
+    ECG_STAMP_AT(g_stamps_r, 0);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5, l31 = lane & 31;
-    int wg;
-    {   // XCD-aware order: the C_out tiles of one tile range sit on one XCD and read the same x panels from its L2
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    // XCD-aware order: the C_out tiles of one tile range sit on one XCD and read the same x panels from its L2
+    const int wg = xcd_chunked(blockIdx.x, gridDim.x);
     const int CT = Cout / CO_T;
     const int tile_co = wg % CT, g = wg / CT;
     const int ntiles = N * tiles_t;
@@ -204,24 +190,15 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 4 
     // global slice of tap f (flat inside the tile's reduction): wb + f * Cout * 32 bytes, rows co0 .. co0 + CO_T
     // LDS row r of a slice holds global half h at half position h ^ bit3(r)  (swizzle on the SOURCE address)
     const size_t tap_bytes = (size_t)Cout * 32;
-    // The LDS-DMA is issued from INLINE ASM: hipcc models __builtin_amdgcn_global_load_lds like a FLAT access, and then waits
-    // vmcnt(0) / lgkmcnt(0) for every load and LDS read that was pending when one issued (39 + 4 full drains per 30 taps in
-    // this loop).  An asm statement with no register result is invisible to that bookkeeping and safe (nothing to
-    // protect but LDS, which the counted vmcnt + barrier at the group starts orders).  M0 is saved and restored inside
-    // the statement (the compiler owns it).
+    // The LDS-DMA pieces go through glds16 (inline asm, mfma_util.h): the counted vmcnt + barrier at the group starts
+    // orders them against the LDS reads.
     const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)lds;
     // source = wave-uniform 64-bit base (SGPR pair: tap slice + row block) + this lane's 32-bit byte offset inside the piece
     const unsigned wlane = (unsigned)((lane >> 1) * 32 + (((lane & 1) ^ ((lane >> 4) & 1)) << 4));
     const unsigned char *const wtile = reinterpret_cast<const unsigned char *>(wb) + (size_t)co0 * 32;
     auto dma_piece = [&](int f, int rb, unsigned dst_off) __attribute__((always_inline)) {   // rows rb*32 .. +31 of tap f -> 1 KB at lds + dst_off
-        const unsigned long long s0 = (unsigned long long)(wtile + (size_t)f * tap_bytes + rb * 1024);   // uniform; made provably so
-        const unsigned char *src = reinterpret_cast<const unsigned char *>(
-            ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(s0 >> 32)) << 32) |
-            (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)s0));
-        const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_base + dst_off));
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(wlane), "s"(src), "s"(dst) : "memory");
+        glds16(wtile + (size_t)f * tap_bytes + rb * 1024, wlane,      // (the source is wave-uniform)
+               (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_base + dst_off)));
     };
     int wtap = 0;                                        // ring: first tap (mod KT) of the NEXT group to issue
     auto dma_group = [&](int slot) __attribute__((always_inline)) {
@@ -477,7 +454,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 4 
     ld_advance();
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // (the asm DMA pieces are not in hipcc's books)
     __syncthreads();                                     // slots 0..3 / resident slice and x image 0 are complete
-    ECG_STAMPR_AT(1);
+    ECG_STAMP_AT(g_stamps_r, 1);
 
     // ---- fragment addressing: ONE base register per operand and tap, everything else an instruction offset ----
     // (left to itself hipcc precomputes a separate address register for every (tap, sub-tile) read of the unrolled body
@@ -612,9 +589,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 4 
         // when the workgroup's tile count is odd — nothing is live across an epilogue but zeroed accumulators
         for (int tile = q0; tile < q1; tile += 2) {
             run_chunk(std::integral_constant<int, 0>{}, 0);
-            if (tile == q0) ECG_STAMPR_AT(2);
+            if (tile == q0) ECG_STAMP_AT(g_stamps_r, 2);
             epilogue(cn, ctt, WAREA);
-            if (tile == q0) ECG_STAMPR_AT(3);
+            if (tile == q0) ECG_STAMP_AT(g_stamps_r, 3);
             if (++ctt == tiles_t) { ctt = 0; ++cn; }
             if (tile + 1 < q1) {
                 run_chunk(std::integral_constant<int, 1>{}, 0);
@@ -626,9 +603,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 4 
         for (int tile = q0; tile < q1; ++tile) {
             for (int body = 0; body < nbodies; ++body)
                 static_for<BODY_CH>([&](auto CB_) __attribute__((always_inline)) { run_chunk(CB_, body); });
-            if (tile == q0) ECG_STAMPR_AT(2);
+            if (tile == q0) ECG_STAMP_AT(g_stamps_r, 2);
             epilogue(cn, ctt, WAREA + ((BODY_CH - 1) & 1) * XB);
-            if (tile == q0) ECG_STAMPR_AT(3);
+            if (tile == q0) ECG_STAMP_AT(g_stamps_r, 3);
             if (++ctt == tiles_t) { ctt = 0; ++cn; }
         }
     }
@@ -637,7 +614,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 4 
     if (g_stamps_r && threadIdx.x == 0) g_stamps_r[(size_t)blockIdx.x * 8 + 5] = (unsigned long long)(q1 - q0);
 #endif
 
-    if (!STATS) ECG_STAMPR_AT(4);
+    if (!STATS) ECG_STAMP_AT(g_stamps_r, 4);
     if (STATS) {
         float *red = reinterpret_cast<float *>(xlds);
         __syncthreads();
@@ -659,7 +636,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 4 
             for (int j = 0; j < WT; ++j) s += red[((wrow * WT + j) * (CO_T / WCO) + lc2) * 2 + w];
             partials[((size_t)(co0 + col) * P_stride + g) * 2 + w] = s;
         }
-        ECG_STAMPR_AT(4);
+        ECG_STAMP_AT(g_stamps_r, 4);
     }
 }
 
@@ -670,17 +647,12 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 4 
 // ---------------------------------------------------------------------------------------------------------
 struct RingPlan { bool ok; int co_t, t_t, res_ch, G; bool xf32; };
 
-#ifndef ECG_BF16_RING
-#define ECG_BF16_RING 1      // compile-time A/B knob (make VARIANT=noring EXTRA="-DECG_BF16_RING=0"): no environment is read
-#endif
-static constexpr int ring_enabled() { return ECG_BF16_RING; }
-
 // Which shapes the ring kernel takes: bf16 in and out (x_bf16 / y_bf16 of the callers), K = 15, odd pad, even ldx,
 // ldy % 4 == 0, and rows long enough that 640-step tiles waste no more than the 256-step tiles of the old kernel.
 // xf32: the input is the fp32 network input (one 16-channel chunk: C_in <= 16), rounded to bf16 while it is staged.
 RingPlan bf16_ring_plan(int N, int Cin, int Cout, int Lo, int K, int pad, int ldx, int ldyo, bool xf32) {
     RingPlan p{false, 0, 0, 0, 0, xf32};
-    if (!ring_enabled() || K != 15 || (pad & 1) == 0 || Cin % 4 || Cout % 32 || ldx % 2 || ldyo % 8) return p;
+    if (K != 15 || (pad & 1) == 0 || Cin % 4 || Cout % 32 || ldx % 2 || ldyo % 8) return p;
     const int nch = (Cin + 15) / 16;
     if (xf32) {
         if (nch != 1) return p;
@@ -692,10 +664,9 @@ RingPlan bf16_ring_plan(int N, int Cin, int Cout, int Lo, int K, int pad, int ld
     // a tile is a whole number of unrolled loop bodies: 2 chunks (resident weights, 128-channel ring) or 4 (64-channel ring)
     const int body_ch = (p.res_ch == 0 && p.co_t == 64) ? 4 : 2;
     if (!xf32 && nch % body_ch) return p;
-    if (ring_enabled() != 2) {          // 2 = force (tests of short rows); 1 = only where the tiles fit the row
-        const long long new_pad = (long long)cdiv(Lo, p.t_t) * p.t_t, old_pad = (long long)cdiv(Lo, 256) * 256;
-        if (new_pad > old_pad + old_pad / 50) return p;
-    }
+    // only where the tiles fit the row
+    const long long new_pad = (long long)cdiv(Lo, p.t_t) * p.t_t, old_pad = (long long)cdiv(Lo, 256) * 256;
+    if (new_pad > old_pad + old_pad / 50) return p;
     const int CT = Cout / p.co_t;
     const long long ntiles = (long long)N * cdiv(Lo, p.t_t);
     long long G = (xf32 ? 512 : 256) / CT;                // (the fp32-input variant runs two workgroups per CU)

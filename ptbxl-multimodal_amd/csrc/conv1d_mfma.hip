@@ -18,27 +18,17 @@
 //
 // Replaces the ATen work behind ConvBlock.net[0] (reference src/models/ecg_cnn.py:13) and its
 // backward (src/training/loop.py:33).
-#include "common.h"
+#include "mfma_util.h"
 #include <cstdlib>
 #include <type_traits>
 
 namespace ecg {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));   // native vector: stays in VGPRs (HIP's float4 struct did not)
-
 constexpr int kKM = 15;   // largest kernel size the MFMA path stages (the reference uses 15)
 
-// In-kernel stamps (diagnostic build only: make STAMP=1 -> tools/_build/libecg_hip_stamp.so; the product library has none).
-// Wave 0 of every workgroup writes s_memtime at a few points into a buffer no other code reads.
+// in-kernel stamps of the diagnostic build (make STAMP=1; tools/stamp_fwd.py): ECG_STAMP_AT(g_stamps, slot), mfma_util.h
 #ifdef ECG_STAMP
 __device__ unsigned long long *g_stamps = nullptr;
-#define ECG_STAMP_AT(slot) do { if (g_stamps && threadIdx.x == 0) { \
-    g_stamps[(size_t)blockIdx.x * 8 + (slot)] = __builtin_amdgcn_s_memtime(); \
-    if ((slot) == 0) g_stamps[(size_t)blockIdx.x * 8 + 7] = __builtin_amdgcn_s_memrealtime(); \
-    if ((slot) == 4) g_stamps[(size_t)blockIdx.x * 8 + 6] = __builtin_amdgcn_s_memrealtime(); } } while (0)
-#else
-#define ECG_STAMP_AT(slot) do { } while (0)
 #endif
 
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
@@ -50,24 +40,6 @@ __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
 // reads just issued for the NEXT step in front of MFMAs that only need the previous ones; an explicit counted wait
 // placed before the MFMAs tells its scoreboard the operands are complete (a count larger than the reads really in
 // flight is harmless: the compiler still adds whatever wait correctness needs).
-// One LDS-DMA piece (1 KB per wave) from INLINE ASM: wave-uniform 64-bit base in SGPRs + this lane's 32-bit byte offset ->
-// LDS byte address `dst` (wave-uniform, + 16 * lane implied).  hipcc books __builtin_amdgcn_global_load_lds like a FLAT
-// access: every LDS read that is pending when one issues is later waited for with lgkmcnt(0), together with the fragments
-// read since (22 of the 30 steps of a forward chunk).  The asm statement has no register result, so there is nothing for
-// the compiler to protect; M0 is saved and restored inside it; completion is waited for explicitly (vmcnt) before the
-// barrier that publishes the image.
-__device__ __forceinline__ void glds16(const void *base_in, unsigned voff, unsigned dst) {
-    // (uniform by construction; readfirstlane makes it PROVABLY so for the "s" operand — the diagnostic STAMP build could
-    // not prove it on its own)
-    const unsigned long long b = (unsigned long long)base_in;
-    const unsigned blo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b);
-    const unsigned bhi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32));
-    const void *base = (const void *)(((unsigned long long)bhi << 32) | blo);
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
-}
-
 __device__ __forceinline__ void wait_lgkm_f(int n) {
     switch (n) {
         case 1: __builtin_amdgcn_s_waitcnt(0xC17F); break;
@@ -78,361 +50,76 @@ __device__ __forceinline__ void wait_lgkm_f(int n) {
     }
 }
 
-// row of element r of a 32x32 accumulator held by this lane: (r&3) + 8*(r>>2) + 4*(lane>>5)
-__device__ __forceinline__ int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
 // =======================================================================================
 // forward (and input-grad with flipped/transposed packed weights)
 // =======================================================================================
-// grid = (ceil(Lo/T_T), Cout/CO_T, N), 256 threads = 4 waves laid out WCO x WT over the tile.
-//
-// Pipeline (per chunk of CI_C = 4 input channels = 30 reduction steps = 120 MFMAs per wave):
-//   LDS holds TWO chunk images {weights [K][4][CO_T] | x tile [4][T_T+16]}.  While the MFMAs of
-//   chunk c run out of image c&1,
-//     * the weight slice of chunk c+1 streams global -> LDS directly (global_load_lds_dwordx4:
-//       no VGPRs, no ds_write; one 1 KB wave-instruction every few steps),
-//     * the x tile of chunk c+1 (3 floats per thread, loaded one chunk earlier) is written with
-//       its zero padding applied by an AND mask, and the x tile of chunk c+2 is loaded,
-//   and ONE barrier (with the vmcnt(0) the compiler attaches to it) closes the chunk.
-//   Every global offset is loop-invariant per thread and precomputed; a chunk only advances a
-//   uniform base pointer.
-// Loads are UNCONDITIONAL (clamped addresses, zeroing by mask): a load that is only used under
-// a condition gets sunk into a branch by hipcc and followed by s_waitcnt vmcnt(0).
 // Epilogue modes: EPI_PLAIN stores y; EPI_STATS also emits the train-mode BN (sum, sum^2)
 // partials; EPI_EVAL folds the eval-mode BatchNorm affine, ReLU and MaxPool1d(2) into the store —
 // the inference path writes only the pooled activation (one launch per ConvBlock); EPI_EVAL_GAP also folds
 // the global average pool behind it (last block, whole row inside one t tile): only g [N][C_out] is written.
 enum { EPI_PLAIN = 0, EPI_STATS = 1, EPI_EVAL = 2, EPI_EVAL_GAP = 3 };
-#ifndef ECG_FWD_FL
-#define ECG_FWD_FL 1         // two-level accumulation (below); tools build -DECG_FWD_FL=0 to A/B its cost and effect
-#endif
-
-// XCD-aware block order.  Workgroups are dealt round-robin over the 8 XCDs (b and b+8 share an L2),
-// so neighbouring block ids — which here would be the tiles that read the SAME input panel — land on
-// eight different L2s and each fetches the panel again.  This bijective remap gives every XCD a
-// contiguous chunk of the logical tile order instead (cdna_hip_programming.md T1, any grid size):
-// tiles that share a panel sit next to each other in the chunk, are dispatched back to back and hit
-// in their XCD's L2.  Placement is a speed matter only; nothing depends on it for correctness.
-__device__ __forceinline__ int xcd_chunked(int bid, int nwg) {
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-}
 struct EvalEpi { const float *gamma, *beta, *mean, *var; float eps; int gap; };
 
-template <int CO_T, int T_T, int WCO, int WT, int EPI>
-__global__ __launch_bounds__(256, 2) void conv1d_mfma_fwd_kernel(
-    const float *__restrict__ x, const float *__restrict__ wp, const float *__restrict__ bias,
-    float *__restrict__ y, float *__restrict__ partials, int Cin, int Cout, int L, int ldx, int Lo,
-    int pad, int P, int tiles_t, EvalEpi ev) {
-    constexpr bool STATS = (EPI == EPI_STATS), GAP = (EPI == EPI_EVAL_GAP);
-    static_assert(WCO * WT == 4, "4 waves per workgroup");
-    constexpr int KK = kKM, CI_C = 4, NST = KK * CI_C / 2;
-    constexpr int MC = CO_T / WCO / 32, MT = T_T / WT / 32;
-    static_assert(MC >= 1 && MT >= 1, "wave tile must hold at least one 32x32 accumulator");
-    constexpr int XS = T_T + 16;                 // x-tile row stride (span T_T + 14)
-    constexpr int WSZ = KK * CI_C * CO_T;        // floats of one weight chunk [K][CI_C][CO_T]
-    constexpr int NDMA = (WSZ + 255) / 256;      // 1 KB wave-instructions per chunk
-    constexpr int WPAD = NDMA * 256;             // weight region padded to whole DMA pieces
-    constexpr int DPW = (NDMA + 3) / 4;          // DMA instructions per wave per chunk
-    constexpr int XEL = CI_C * XS;
-    constexpr int XLOADS = (XEL + 255) / 256;
-    constexpr int IMG = WPAD + XEL;
-    constexpr int REDF = (STATS || GAP) ? 4 * (CO_T / WCO) * 2 : 0;
-    static_assert(REDF <= IMG, "stat scratch aliases image 0");
-    static_assert(NST >= 2 + DPW + XLOADS, "not enough steps to spread the staging over");
-
-    // ONE shared array: a second __shared__ object beside an LDS-DMA target makes hipcc wait
-    // vmcnt(0) in front of every LDS read.
-    __shared__ __attribute__((aligned(1024))) float lds[2 * IMG];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int half = lane >> 5, l31 = lane & 31;
-    ECG_STAMP_AT(0);
-    // logical tile order: the C_out tiles of one (n, t tile) are adjacent — they read the same x panel
-    const int CT = Cout / CO_T;
-    const int tile = xcd_chunked(blockIdx.x, gridDim.x);
-    const int tile_co = tile % CT, tile_nt = tile / CT;
-    const int tile_t = tile_nt % tiles_t, n = tile_nt / tiles_t;
-    const int t0 = tile_t * T_T, co0 = tile_co * CO_T;
-    const int wco = (wave / WT) * (CO_T / WCO), wt = (wave % WT) * (T_T / WT);
-    const float *xn = x + (size_t)n * Cin * ldx;     // ldx >= L: row stride of the input tensor
-
-    // TWO-LEVEL ACCUMULATION (ECG_FWD_FL): v_mfma_f32_32x32x2_f32 is one k-ordered fp32 fma chain, C_in * 15 terms long
-    // (up to 3 840 in the block-3 input gradient): its rounding error grew with the square root of that — 2.8x (forward)
-    // and 3.9x (input gradient) what oneDNN's blocked sums leave on the block-3 shapes (tools/wgrad_error.py), and with
-    // it the number of ReLU / pooling decisions that differ from an exact forward pass.  The first MFMA of every chunk
-    // therefore starts from the inline constant 0 and the chunk's 60-term sum joins a second register set at the end of
-    // the chunk: chains of 60 + C_in / 4 terms, same fixed order for every launch.
-    constexpr bool FL = (ECG_FWD_FL != 0);
-    f32x16 acc[MC][MT], acc2[MC][MT];
-    f32x16 zero16;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
-#pragma unroll
-    for (int a = 0; a < MC; ++a)
-#pragma unroll
-        for (int b = 0; b < MT; ++b) { acc[a][b] = zero16; acc2[a][b] = zero16; }
-
-    // ---- per-channel epilogue parameters, lane-indexed: lane (r + 32*half), r < 16, holds those of accumulator
-    // row (r, half) of each 32-channel group.  They are loaded HERE, before the main loop: vmcnt is in-order, so
-    // a global load issued between the epilogue's stores has to wait for the round trip of every store before it
-    // (16 rows x ~1 us per workgroup when the bias was fetched row by row).
-    constexpr bool EVALM = (EPI == EPI_EVAL || EPI == EPI_EVAL_GAP);
-    float p_b[MC], p_mu[MC], p_sc[MC], p_be[MC];
-#pragma unroll
-    for (int i = 0; i < MC; ++i) {
-        const int ch = co0 + wco + 32 * i + acc_row(l31 & 15, half);
-        p_b[i] = bias ? bias[ch] : 0.f;
-        p_mu[i] = p_sc[i] = p_be[i] = 0.f;
-        if (EVALM) {
-            const float is = (float)(1.0 / sqrt((double)ev.var[ch] + (double)ev.eps));
-            p_sc[i] = is * ev.gamma[ch]; p_mu[i] = ev.mean[ch]; p_be[i] = ev.beta[ch];
-        }
-    }
-
-    // ---- loop-invariant per-thread staging offsets -------------------------------------------
-    int woff[DPW];          // weight piece j of this wave: element offset inside wp (chunk 0)
-#pragma unroll
-    for (int j = 0; j < DPW; ++j) {
-        const int e = min(((j * 4 + wave) * 64 + lane) * 4, WSZ - 4);   // float index in the image
-        const int row = e / CO_T, col = e - row * CO_T;                  // row = k*CI_C + ci
-        const int k = row / CI_C, ci = row - k * CI_C;
-        woff[j] = (k * Cin + ci) * Cout + col;
-    }
-    int xoff[XLOADS];
-    unsigned xmask = 0;
-#pragma unroll
-    for (int j = 0; j < XLOADS; ++j) {
-        const int e = min(tid + 256 * j, XEL - 1);
-        const int ci = e / XS, pos = e - ci * XS;
-        const int s = t0 - pad + pos;
-        xoff[j] = ci * ldx + min(max(s, 0), L - 1);
-        xmask |= ((s >= 0) && (s < L)) ? (1u << j) : 0u;
-    }
-    float xreg[XLOADS];
-
-    const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) float *)lds;
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    auto dma_w = [&](int j, int ci0, float *img) {       // one 1 KB piece of the weight slice
-        if ((j * 4 + wave_u) < NDMA)
-            glds16(wp + (size_t)ci0 * Cout + co0, (unsigned)woff[j] * 4u,
-                   (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_base + (unsigned)((img - lds) + (j * 4 + wave_u) * 256) * 4u)));
-    };
-    auto load_x = [&](int j, int ci0) { xreg[j] = xn[(size_t)ci0 * ldx + xoff[j]]; };
-    auto commit_x = [&](int j, float *img) {
-        const int e = tid + 256 * j;
-        const unsigned keep = 0u - ((xmask >> j) & 1u);
-        if (256 * (j + 1) <= XEL || e < XEL)
-            img[WPAD + e] = __uint_as_float(__float_as_uint(xreg[j]) & keep);
-    };
-
-    const int nchunks = Cin / CI_C;
-    // prologue: chunk 0 -> image 0; x tile of chunk 1 -> registers
-#pragma unroll
-    for (int j = 0; j < DPW; ++j) dma_w(j, 0, lds);
-#pragma unroll
-    for (int j = 0; j < XLOADS; ++j) load_x(j, 0);
-#pragma unroll
-    for (int j = 0; j < XLOADS; ++j) commit_x(j, lds);
-    if (nchunks > 1) {
-#pragma unroll
-        for (int j = 0; j < XLOADS; ++j) load_x(j, CI_C);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (the asm DMA pieces are not in hipcc's books)
-    __syncthreads();
-    ECG_STAMP_AT(1);
-
-    for (int c = 0; c < nchunks; ++c) {
-        const float *ws = lds + (c & 1) * IMG, *xs = ws + WPAD;
-        float *nxt = lds + ((c + 1) & 1) * IMG;
-        const bool do_next = c + 1 < nchunks, do_next2 = c + 2 < nchunks;
-        const int ci_next = (c + 1) * CI_C, ci_next2 = (c + 2) * CI_C;
-
-        // One reduction step = one (tap, ci-pair): MC + MT LDS reads feed MC*MT MFMAs; the
-        // fragments of step s+1 are read BEFORE the MFMAs of step s are issued.
-        auto ld = [&](int st, float *a, float *b) {
-            const int k = st / (CI_C / 2), cp = st % (CI_C / 2);
-            const float *wrow = ws + ((k * CI_C + 2 * cp + half) * CO_T + wco + l31);
-            const float *xrow = xs + (2 * cp + half) * XS + wt + l31 + k;
-#pragma unroll
-            for (int i = 0; i < MC; ++i) a[i] = wrow[32 * i];
-#pragma unroll
-            for (int i = 0; i < MT; ++i) b[i] = xrow[32 * i];
-        };
-        float a_c[MC], b_c[MT], a_n[MC], b_n[MT];
-        ld(0, a_c, b_c);
-#pragma unroll
-        for (int st = 0; st < NST; ++st) {
-            ld(st + 1 < NST ? st + 1 : 0, a_n, b_n);
-            wait_lgkm_f((MC + 1) / 2 + (MT + 1) / 2);      // the reads just issued (pairs merge into ds_read2_b32) may fly
-            // staging, one operation per step: x commits, then weight DMA pieces, then x loads
-            if (st < XLOADS) {
-                if (do_next) commit_x(st, nxt);
-            } else if (st < XLOADS + DPW) {
-                if (do_next) dma_w(st - XLOADS, ci_next, nxt);
-            } else if (st < 2 * XLOADS + DPW) {
-                if (do_next2) load_x(st - XLOADS - DPW, ci_next2);
-            }
-            __builtin_amdgcn_sched_barrier(0);     // keep reads + staging ABOVE this step's MFMAs
-#pragma unroll
-            for (int i = 0; i < MC; ++i)
-#pragma unroll
-                for (int j = 0; j < MT; ++j)
-                    acc[i][j] = mfma32(a_c[i], b_c[j], (FL && st == 0) ? zero16 : acc[i][j]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < MC; ++i) a_c[i] = a_n[i];
-#pragma unroll
-            for (int i = 0; i < MT; ++i) b_c[i] = b_n[i];
-        }
-        if (FL) {
-#pragma unroll
-            for (int i = 0; i < MC; ++i)
-#pragma unroll
-                for (int j = 0; j < MT; ++j) acc2[i][j] += acc[i][j];
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();      // image c&1 free again; image (c+1)&1 complete (vmcnt(0) + barrier)
-        if (c == 0) ECG_STAMP_AT(2);
-    }
-    if (FL) {
-#pragma unroll
-        for (int i = 0; i < MC; ++i)
-#pragma unroll
-            for (int j = 0; j < MT; ++j) acc[i][j] = acc2[i][j];
-    }
-    ECG_STAMP_AT(3);
-    float *red = lds;         // all images are dead: reuse image 0 for the statistics scratch
-
-    // ---- epilogue: bias, store, per-channel (sum, sum^2) partials --------------------------
-    // Nothing is in flight here (the last chunk's barrier drained vmcnt), but the compiler cannot prove it for the
-    // staging registers of a loop it thinks may run zero times: without this explicit (free) wait it protects their
-    // reuse below with `s_waitcnt vmcnt(2..0)` in the MIDDLE of the stores, i.e. a wait for the stores themselves.
-    __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0), expcnt/lgkmcnt untouched
-    // No global load and no LDS-crossbar permute between the stores.  Row r of the two halves: parameters come out
-    // of the lane-indexed registers by v_readlane; per-row sums are reduced over each 16-lane DPP row only and
-    // accumulated in lanes r / r+16 of ONE register per 32 channels, the two 16-lane sums meet once at the end.
-    auto pick = [&](float v, int r) {
-        const int vi = __float_as_int(v);
-        const float lo = __int_as_float(__builtin_amdgcn_readlane(vi, r));
-        const float hi = __int_as_float(__builtin_amdgcn_readlane(vi, r + 32));
-        return half ? hi : lo;
-    };
-    float st_s[MC], st_q[MC];
-#pragma unroll
-    for (int i = 0; i < MC; ++i) { st_s[i] = 0.f; st_q[i] = 0.f; }
-    const int Lp = Lo >> 1;
-    // element offset of (row 0 of this lane's half, first column of this lane) inside the output of sample n
-    float *yw = EVALM ? y + ((size_t)n * Cout + co0 + wco + 4 * half) * Lp + ((t0 + wt + l31) >> 1)
-                      : y + ((size_t)n * Cout + co0 + wco + 4 * half) * Lo + t0 + wt + l31;
-#pragma unroll
-    for (int i = 0; i < MC; ++i) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int rowk = 32 * i + (r & 3) + 8 * (r >> 2);          // channel row inside the wave tile, minus 4*half
-            const float bv = pick(p_b[i], r);
-            float s = 0.f, q = 0.f;
-            if (EVALM) {
-                // p[j] = max(0, max(a[2j], a[2j+1])), a = (v - mean) * (invstd * gamma) + beta.  The two
-                // samples of a pooling pair sit on adjacent lanes: one DPP quad_perm fetches the partner.
-                const float mu = pick(p_mu[i], r), sc = pick(p_sc[i], r), be = pick(p_be[i], r);
-#pragma unroll
-                for (int j = 0; j < MT; ++j) {
-                    const int t = t0 + wt + 32 * j + l31;
-                    const float a = bn_apply1(acc[i][j][r] + bv, mu, sc, be);
-                    const float o = dpp_move<0xB1>(a);                 // lane ^ 1
-                    const float m = fmaxf(fmaxf(a, o), 0.f);
-                    const bool owner = !(l31 & 1) && (t >> 1) < Lp;
-                    if (GAP) s += owner ? m : 0.f;
-                    else if (owner) yw[rowk * Lp + 16 * j] = m;
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < MT; ++j) {
-                    const float v = acc[i][j][r] + bv;
-                    if (t0 + wt + 32 * j + l31 < Lo) {
-                        yw[rowk * Lo + 32 * j] = v;
-                        if (STATS) { s += v; q = __fmaf_rn(v, v, q); }
-                    }
-                }
-            }
-            if (STATS || GAP) {
-                const bool mine = (l31 & 15) == r;       // lanes r and r+16 of each half keep row (r, half)
-                s = row16_sum(s);                        // 4 DPP adds: every lane holds the sum of its 16-lane row
-                st_s[i] += mine ? s : 0.f;
-                if (STATS) { q = row16_sum(q); st_q[i] += mine ? q : 0.f; }
-            }
-        }
-    }
-    if (STATS || GAP) {
-#pragma unroll
-        for (int i = 0; i < MC; ++i) {
-            const float s = st_s[i] + __shfl_xor(st_s[i], 16, 64);
-            const float q = st_q[i] + __shfl_xor(st_q[i], 16, 64);
-            if (l31 < 16) {
-                const int lc = 32 * i + acc_row(l31, half);   // channel inside the wave tile
-                red[(wave * (CO_T / WCO) + lc) * 2] = s;
-                red[(wave * (CO_T / WCO) + lc) * 2 + 1] = q;
-            }
-        }
-    }
-    if (GAP) {
-        __syncthreads();
-        // global average pool: combine the WT waves of each channel row, divide by the pooled length
-        for (int col = tid; col < CO_T; col += 256) {
-            const int wrow = col / (CO_T / WCO), lc = col - wrow * (CO_T / WCO);
-            float g = 0.f;
-#pragma unroll
-            for (int j = 0; j < WT; ++j) g += red[((wrow * WT + j) * (CO_T / WCO) + lc) * 2];
-            y[(size_t)n * Cout + co0 + col] = g / (float)(Lo >> 1);
-        }
-    }
-    if (STATS) {
-        __syncthreads();
-        // combine the WT waves that share each channel row; one (sum, sum^2) pair per channel
-        for (int e = tid; e < CO_T * 2; e += 256) {
-            const int col = e >> 1, w = e & 1;
-            const int wrow = col / (CO_T / WCO), lc = col - wrow * (CO_T / WCO);
-            float s = 0.f;
-#pragma unroll
-            for (int j = 0; j < WT; ++j) s += red[((wrow * WT + j) * (CO_T / WCO) + lc) * 2 + w];
-            const int pidx = n * tiles_t + tile_t;
-            partials[((size_t)(co0 + col) * P + pidx) * 2 + w] = s;
-        }
-    }
-#ifdef ECG_STAMP
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the stores of the epilogue have left the wave
-#endif
-    ECG_STAMP_AT(4);
-}
-
-// ---------------------------------------------------------------------------------------
-// Forward / input gradient by a two-phase fast-FIR split (all four epilogues of the kernel above).
-// The kernels above are bound by the fp32 matrix pipe (0.76-0.84 of its nominal peak at the clocks the chip holds), so the
-// only way down is fewer MFMAs.  With xt[p] = x[t0 - pad + p] and output column m of the tile <-> outputs t0 + 2m, t0 + 2m + 1:
+// Forward / input gradient by a two-phase fast-FIR split, all four epilogues.
+// grid = ceil(Lo/TS) * Cout/CO_T * N workgroups (xcd_chunked order: the C_out tiles of one (n, t tile) are adjacent — they
+// read the same x panel), 256 threads = 4 waves laid out WCO x WT over the tile.
+//
+// A kernel that spends one MFMA per (tap, channel pair) is bound by the fp32 matrix pipe (the direct form this kernel replaced
+// ran at 0.76-0.84 of its nominal peak at the clocks the chip holds), so the only way down is fewer MFMAs.  With
+// xt[p] = x[t0 - pad + p] and output column m of the tile <-> outputs t0 + 2m, t0 + 2m + 1:
 //     A[m] = sum_{j=0..7} w[2j]             * xt[2m + 2j]
 //     B[m] = sum_{j=0..6} w[2j+1]           * xt[2m + 2j + 1]
 //     D[m] = sum_{j=0..7} (w[2j] - w[2j-1]) * (xt[2m + 2j] - xt[2m + 2j + 1])          (w[-1] = 0)
 //     y[t0 + 2m] = A[m] + B[m],     y[t0 + 2m + 1] = A[m] + B[m + 1] - D[m]
 // i.e. 23 multiplies per output pair instead of 30: three 32 x 32 accumulators (A, B, D) over M_T = T/2 columns take 46 MFMAs
-// per chunk of four input channels where the direct form takes 60.  The third product on DIFFERENCES, not on the textbook's sums
-// ((w[2j] + w[2j-1]) (x.. + x..), y_odd = C - A - B'; ECG_FFA_MINUS = 0 builds it for A/B): neighbouring samples of like sign and
-// magnitude — pooled ReLU outputs — subtract exactly and D is small, where C is twice the size of A and every odd output a
-// difference of large sums (trajectory drift against float64 1.62x the CPU fp32 path's with C, 0.41x with D: EXPERIMENTS I5).
-// Nothing is pre-processed: the LDS images are the ones of
-// the kernel above ({weights [K][4][CO_T] | x tile [4][2 M_T + 16]}); one ds_read_b64 per lane yields (xt[2m+2j], xt[2m+2j+1])
-// for the A, B and D step of tap pair j (conflict-free: 32 lanes x 8 bytes), the two differences are one VALU operation each.
+// per chunk of four input channels where the direct form takes 60.  The third product is on DIFFERENCES, not on the textbook's
+// sums ((w[2j] + w[2j-1]) (x.. + x..), y_odd = C - A - B'): neighbouring samples of like sign and magnitude — pooled ReLU
+// outputs — subtract exactly and D is small, where C is twice the size of A and every odd output a difference of large sums
+// (trajectory drift against float64 1.62x the CPU fp32 path's with C — it fails the trajectory bars — 0.41x with D:
+// EXPERIMENTS I5).
+// Nothing is pre-processed: one ds_read_b64 per lane yields (xt[2m+2j], xt[2m+2j+1]) for the A, B and D step of tap pair j
+// (conflict-free: 32 lanes x 8 bytes), the two differences are one VALU operation each.
 // B[m + 1] of the tile's last column belongs to the next tile, so a tile of M_T columns yields 2 M_T - 2 outputs: tiles are
 // TS = 2 M_T - 2 apart (column M_T - 1 only supplies B); for the model's row lengths that is the same number of tiles as
 // 2 M_T-wide ones.  In the epilogue B goes through LDS once (the images are dead) to come back shifted by a column.
 // Rounding: the two extra subtractions per product and the final combination are fp32; the result differs from the direct form
-// by a few ulp of the accumulated magnitude (tests state the bounds: test_conv_fast_fir_error_by_signal_class).  Inference epilogues: the pooling pair (2m, 2m + 1) sits in ONE
-// lane, so BatchNorm + ReLU + MaxPool(2) is three VALU operations per pair and the pooled row leaves as contiguous dwords.
+// by a few ulp of the accumulated magnitude (tests state the bounds: test_conv_fast_fir_error_by_signal_class).
+//
+// Pipeline (per chunk of CI_C = 4 input channels = 16 reduction steps = 46 MFMAs per wave):
+//   LDS holds TWO chunk images {weights [K][4][CO_T] | x tile [4][2 M_T + 16]}.  While the MFMAs of
+//   chunk c run out of image c&1,
+//     * the weight slice of chunk c+1 streams global -> LDS directly (glds16:
+//       no VGPRs, no ds_write; one 1 KB wave-instruction every few steps),
+//     * the x tile of chunk c+1 (loaded one chunk earlier) is written with
+//       its zero padding applied by an AND mask, and the x tile of chunk c+2 is loaded,
+//   and ONE barrier behind an explicit vmcnt(0) (the asm DMA pieces are not in hipcc's books) closes the chunk.
+//   Every global offset is loop-invariant per thread and precomputed; a chunk only advances a
+//   uniform base pointer.  The fragments of step s+1 are read BEFORE the MFMAs of step s are issued.
+// Loads are UNCONDITIONAL (clamped addresses, zeroing by mask): a load that is only used under
+// a condition gets sunk into a branch by hipcc and followed by s_waitcnt vmcnt(0).
+// ONE shared array: a second __shared__ object beside an LDS-DMA target makes hipcc wait vmcnt(0) in front of every LDS read.
+//
+// TWO-LEVEL ACCUMULATION: v_mfma_f32_32x32x2_f32 is one k-ordered fp32 fma chain, C_in * 15 terms long in a single
+// accumulator (up to 3 840 in the block-3 input gradient): its rounding error grew with the square root of that — 2.8x (forward)
+// and 3.9x (input gradient) what oneDNN's blocked sums leave on the block-3 shapes (tools/wgrad_error.py), and with
+// it the number of ReLU / pooling decisions that differ from an exact forward pass (single-level sums fail
+// test_conv_rounding_error_vs_float64 and the trajectory bars).  The first MFMA of every chunk (FLP = 2: of every second
+// chunk) therefore starts from the inline constant 0 and the chunk's sum joins a second register set at the end of the
+// chunk: short chains + C_in / 4 terms, same fixed order for every launch.
+//
+// Epilogue.  The per-channel parameters are lane-indexed: lane (r + 32*half), r < 16, holds those of accumulator
+// row (r, half) of the wave's 32-channel group.  They are loaded before the main loop: vmcnt is in-order, so
+// a global load issued between the epilogue's stores has to wait for the round trip of every store before it
+// (16 rows x ~1 us per workgroup when the bias was fetched row by row); in the epilogue they come out of the registers by
+// v_readlane — no global load and no LDS-crossbar permute between the stores.  Per-row sums are reduced over each 16-lane DPP
+// row only and accumulated in lanes r / r+16 of ONE register, the two 16-lane sums meet once at the end.
+// Nothing is in flight when the epilogue starts (the last chunk's barrier drained vmcnt), but the compiler cannot prove it
+// for the staging registers of a loop it thinks may run zero times: without the explicit (free) vmcnt(0) there it protects
+// their reuse with `s_waitcnt vmcnt(2..0)` in the MIDDLE of the stores, i.e. a wait for the stores themselves.
+// Inference epilogues: the pooling pair (2m, 2m + 1) sits in ONE lane, so BatchNorm + ReLU + MaxPool(2) is three VALU
+// operations per pair and the pooled row leaves as contiguous dwords.
 #ifndef ECG_FFA_MINB
 #define ECG_FFA_MINB 2       // workgroups per CU the register allocation aims at (4: 128 registers, spills; measured slower)
-#endif
-#ifndef ECG_FFA_MINUS
-#define ECG_FFA_MINUS 1      // third product on differences (0: the textbook sum form, A/B only — fails the trajectory bars)
 #endif
 #ifndef ECG_FFA_FLP2
 #define ECG_FFA_FLP2 64      // one second-level add per TWO chunks where C_in % 8 == 0 and C_in >= this (0: per chunk everywhere)
@@ -466,7 +153,7 @@ __global__ __launch_bounds__(256, ECG_FFA_MINB) void conv1d_mfma_ffa_kernel(
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, l31 = lane & 31;
-    ECG_STAMP_AT(0);
+    ECG_STAMP_AT(g_stamps, 0);
     const int CT = Cout / CO_T;
     const int tile = xcd_chunked(blockIdx.x, gridDim.x);
     const int tile_co = tile % CT, tile_nt = tile / CT;
@@ -475,7 +162,6 @@ __global__ __launch_bounds__(256, ECG_FFA_MINB) void conv1d_mfma_ffa_kernel(
     const int wco = (wave / WT) * 32, wm = (wave % WT) * 32;
     const float *xn = x + (size_t)n * Cin * ldx;
 
-    constexpr bool FL = (ECG_FWD_FL != 0);
     f32x16 acc[3], acc2[3];
     f32x16 zero16;
 #pragma unroll
@@ -483,7 +169,7 @@ __global__ __launch_bounds__(256, ECG_FFA_MINB) void conv1d_mfma_ffa_kernel(
 #pragma unroll
     for (int a = 0; a < 3; ++a) { acc[a] = zero16; acc2[a] = zero16; }
 
-    const int pch = co0 + wco + acc_row(l31 & 15, half);      // lane-indexed epilogue parameters (see the kernel above)
+    const int pch = co0 + wco + acc_row(l31 & 15, half);      // lane-indexed epilogue parameters
     const float p_b = bias ? bias[pch] : 0.f;
     float p_mu = 0.f, p_sc = 0.f, p_be = 0.f;
     if (EVALM) {
@@ -539,7 +225,7 @@ __global__ __launch_bounds__(256, ECG_FFA_MINB) void conv1d_mfma_ffa_kernel(
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    ECG_STAMP_AT(1);
+    ECG_STAMP_AT(g_stamps, 1);
 
     typedef float f32x2t __attribute__((ext_vector_type(2)));
     // FLP = 2: a first-level sum runs over TWO chunks (OPEN starts it from zero, CLOSE adds it to the second level)
@@ -551,7 +237,7 @@ __global__ __launch_bounds__(256, ECG_FFA_MINB) void conv1d_mfma_ffa_kernel(
         const int ci_next = (c + 1) * CI_C, ci_next2 = (c + 2) * CI_C;
 
         // one step = tap pair j of channel pair cp: w[2j], w[2j+1] (one dword each) and (xt[2m+2j], xt[2m+2j+1]) (one b64)
-        // feed the A, B and C MFMAs; the reads of step s + 1 are issued before the MFMAs of step s
+        // feed the A, B and D MFMAs; the reads of step s + 1 are issued before the MFMAs of step s
         auto ld = [&](int st, float &wa, float &wb, f32x2t &xq) {
             const int j = st / (CI_C / 2), cp = st % (CI_C / 2);
             const float *wrow = ws + ((2 * j * CI_C + 2 * cp + half) * CO_T + wco + l31);
@@ -576,23 +262,23 @@ __global__ __launch_bounds__(256, ECG_FFA_MINB) void conv1d_mfma_ffa_kernel(
             } else if (st < 2 * XLOADS + DPW) {
                 if (do_next2) load_x(st - XLOADS - DPW, ci_next2);
             }
-            const float wc = ECG_FFA_MINUS ? wa_c - wprev[cp] : wa_c + wprev[cp];
-            const float xc = ECG_FFA_MINUS ? xq_c[0] - xq_c[1] : xq_c[0] + xq_c[1];
+            const float wc = wa_c - wprev[cp];
+            const float xc = xq_c[0] - xq_c[1];
             __builtin_amdgcn_sched_barrier(0);
-            acc[0] = mfma32(wa_c, xq_c[0], (FL && OPEN && j == 0 && cp == 0) ? zero16 : acc[0]);
-            if (2 * j + 1 < KK) acc[1] = mfma32(wb_c, xq_c[1], (FL && OPEN && j == 0 && cp == 0) ? zero16 : acc[1]);
-            acc[2] = mfma32(wc, xc, (FL && OPEN && j == 0 && cp == 0) ? zero16 : acc[2]);
+            acc[0] = mfma32(wa_c, xq_c[0], (OPEN && j == 0 && cp == 0) ? zero16 : acc[0]);
+            if (2 * j + 1 < KK) acc[1] = mfma32(wb_c, xq_c[1], (OPEN && j == 0 && cp == 0) ? zero16 : acc[1]);
+            acc[2] = mfma32(wc, xc, (OPEN && j == 0 && cp == 0) ? zero16 : acc[2]);
             __builtin_amdgcn_sched_barrier(0);
             wprev[cp] = wb_c;
             wa_c = wa_n; wb_c = wb_n; xq_c = xq_n;
         }
-        if (FL && CLOSE) {
+        if (CLOSE) {
 #pragma unroll
             for (int a = 0; a < 3; ++a) acc2[a] += acc[a];
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (c == 0) ECG_STAMP_AT(2);
+        if (c == 0) ECG_STAMP_AT(g_stamps, 2);
     };
     {
         const std::true_type yes{};
@@ -603,14 +289,12 @@ __global__ __launch_bounds__(256, ECG_FFA_MINB) void conv1d_mfma_ffa_kernel(
         }
         for (; c < nchunks; ++c) chunk(c, yes, yes);
     }
-    if (FL) {
 #pragma unroll
-        for (int a = 0; a < 3; ++a) acc[a] = acc2[a];
-    }
-    ECG_STAMP_AT(3);
+    for (int a = 0; a < 3; ++a) acc[a] = acc2[a];
+    ECG_STAMP_AT(g_stamps, 3);
 
     // ---- epilogue -------------------------------------------------------------------------------------
-    __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0) (see the kernel above)
+    __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0): free, see the header
     // B one column to the left: through LDS (the last column of a wave's block comes from the wave beside it)
     float *bx = lds, *red = lds + CO_T * BXS;
 #pragma unroll
@@ -637,7 +321,7 @@ __global__ __launch_bounds__(256, ECG_FFA_MINB) void conv1d_mfma_ffa_kernel(
         const int rowk = (r & 3) + 8 * (r >> 2);
         const float bv = pick(p_b, r);
         const float v0 = (acc[0][r] + acc[1][r]) + bv;
-        const float v1 = (ECG_FFA_MINUS ? (acc[0][r] + bn[r]) - acc[2][r] : (acc[2][r] - acc[0][r]) - bn[r]) + bv;
+        const float v1 = ((acc[0][r] + bn[r]) - acc[2][r]) + bv;
         float s = 0.f, q = 0.f;
         if (EVALM) {
             const float mu = pick(p_mu, r), sc = pick(p_sc, r), be = pick(p_be, r);
@@ -697,22 +381,17 @@ __global__ __launch_bounds__(256, ECG_FFA_MINB) void conv1d_mfma_ffa_kernel(
 #ifdef ECG_STAMP
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the stores of the epilogue have left the wave
 #endif
-    ECG_STAMP_AT(4);
+    ECG_STAMP_AT(g_stamps, 4);
 }
 
-struct FwdCfg { int co_t, t_t, stride; };     // stride: distance of the t tiles (fast-FIR kernel: t_t - 2)
-#ifndef ECG_FWD_FFA
-#define ECG_FWD_FFA 7       // bit 0: forward (statistics epilogue), bit 1: plain epilogue (input gradient, unfused forward),
-#endif                      // bit 2: the inference epilogues
+struct FwdCfg { int co_t, t_t, stride; };     // stride: distance of the t tiles, t_t - 2 (column M_T - 1 only supplies B)
 
-// Tile choice of the one-tile-per-workgroup kernel (inference epilogues).  Measured on MI355X (B=256): 64x128
+// Tile choice.  Measured on MI355X (B=256): 64x128
 // tiles at 4 resident workgroups per CU beat 128x128 at 2 per CU by 6-8 % (more independent waves per SIMD to
 // cover each other's prologue, epilogue and staging waits), so the 64-channel tile is used whenever C_out allows it.
-static FwdCfg fwd_cfg(int N, int Cout, int Lo, bool train) {
-    (void)N; (void)Lo;
-    const bool ffa = train ? (ECG_FWD_FFA & 1) != 0 : (ECG_FWD_FFA & 4) != 0;   // (callers: statistics partials | one-tile GAP)
-    if (Cout % 64 == 0) return {64, 128, ffa ? 126 : 128};
-    return {32, 256, ffa ? 254 : 256};
+static FwdCfg fwd_cfg(int Cout) {
+    if (Cout % 64 == 0) return {64, 128, 126};
+    return {32, 256, 254};
 }
 
 bool mfma_fwd_supported(int Cin, int Cout, int K, int pad) {
@@ -722,63 +401,47 @@ bool mfma_fwd_supported(int Cin, int Cout, int K, int pad) {
 
 int mfma_fwd_stat_partials(int N, int Cin, int Cout, int Lo) {
     (void)Cin;
-    return N * cdiv(Lo, fwd_cfg(N, Cout, Lo, true).stride);
+    return N * cdiv(Lo, fwd_cfg(Cout).stride);
 }
 
 template <int CO_T, int T_T, int WCO, int WT>
 static void launch_fwd(const float *x, const float *wp, const float *bias, float *y,
                        float *partials, const EvalEpi *ev, int N, int Cin, int Cout, int L, int ldx,
                        int Lo, int pad, hipStream_t st) {
-    if (ev ? (ECG_FWD_FFA & 4) != 0 : (((ECG_FWD_FFA & 1) && partials) || ((ECG_FWD_FFA & 2) && !partials))) {
-        const int tiles_t = cdiv(Lo, T_T - 2);
-        dim3 grid((unsigned)((size_t)tiles_t * (Cout / CO_T) * N)), block(256);
-        const int P = N * tiles_t;
-        const EvalEpi none{nullptr, nullptr, nullptr, nullptr, 0.f, 0};
-        // One second-level add per TWO four-channel chunks where the reduction is long (C_in % 8 == 0, C_in >= 64): first-level chains
-        // of 64 instead of 32 terms, half as many second-level adds — the add (three accumulator sets behind the last MFMAs of a
-        // chunk) is what a chunk boundary costs, not its barrier.  Same box, forward + input gradient of the four blocks against
-        // eight-channel chunks with one add each (70 KB of LDS: two workgroups per CU; this form keeps three): 845.6 -> 832.8 us at
-        // 12x1000, 3 737.6 -> 3 643.3 at 12x5000.  NOT on the 32-channel reduction of block 1's forward (another -9 / -31 us): its y
-        // error against float64 goes 0.56 -> 0.69 of the CPU fp32 path's and the trajectory test fails its bars (drift 1.28x /
-        // 2.76x the CPU's at B = 32 / 256; with the threshold at 64: 0.41x / 0.39x) — EXPERIMENTS I5.
-#define ECG_FFA(MODE, EV) do { \
-        if (ECG_FFA_FLP2 && Cin % 8 == 0 && Cin >= ECG_FFA_FLP2) \
-            hipLaunchKernelGGL((conv1d_mfma_ffa_kernel<CO_T, T_T / 2, WCO, WT, MODE, 4, 2>), grid, block, 0, st, x, wp, \
-                               bias, y, partials, Cin, Cout, L, ldx, Lo, pad, P, tiles_t, EV); \
-        else \
-            hipLaunchKernelGGL((conv1d_mfma_ffa_kernel<CO_T, T_T / 2, WCO, WT, MODE>), grid, block, 0, st, x, wp, bias, y, \
-                               partials, Cin, Cout, L, ldx, Lo, pad, P, tiles_t, EV); } while (0)
-        if (ev && ev->gap) ECG_FFA(EPI_EVAL_GAP, *ev);
-        else if (ev) ECG_FFA(EPI_EVAL, *ev);
-        else if (partials) ECG_FFA(EPI_STATS, none);
-        else ECG_FFA(EPI_PLAIN, none);
-#undef ECG_FFA
-        return;
-    }
-    const int tiles_t = cdiv(Lo, T_T);
+    const int tiles_t = cdiv(Lo, T_T - 2);
     dim3 grid((unsigned)((size_t)tiles_t * (Cout / CO_T) * N)), block(256);
     const int P = N * tiles_t;
     const EvalEpi none{nullptr, nullptr, nullptr, nullptr, 0.f, 0};
-#define ECG_FWD(MODE, EV) \
-    hipLaunchKernelGGL((conv1d_mfma_fwd_kernel<CO_T, T_T, WCO, WT, MODE>), grid, block, 0, st, x, wp, \
-                       bias, y, partials, Cin, Cout, L, ldx, Lo, pad, P, tiles_t, EV)
-    if (ev && ev->gap) ECG_FWD(EPI_EVAL_GAP, *ev);
-    else if (ev) ECG_FWD(EPI_EVAL, *ev);
-    else if (partials) ECG_FWD(EPI_STATS, none);
-    else ECG_FWD(EPI_PLAIN, none);
-#undef ECG_FWD
+    // One second-level add per TWO four-channel chunks where the reduction is long (C_in % 8 == 0, C_in >= 64): first-level chains
+    // of 64 instead of 32 terms, half as many second-level adds — the add (three accumulator sets behind the last MFMAs of a
+    // chunk) is what a chunk boundary costs, not its barrier.  Same box, forward + input gradient of the four blocks against
+    // eight-channel chunks with one add each (70 KB of LDS: two workgroups per CU; this form keeps three): 845.6 -> 832.8 us at
+    // 12x1000, 3 737.6 -> 3 643.3 at 12x5000.  NOT on the 32-channel reduction of block 1's forward (another -9 / -31 us): its y
+    // error against float64 goes 0.56 -> 0.69 of the CPU fp32 path's and the trajectory test fails its bars (drift 1.28x /
+    // 2.76x the CPU's at B = 32 / 256; with the threshold at 64: 0.41x / 0.39x) — EXPERIMENTS I5.
+#define ECG_FFA(MODE, EV) do { \
+    if (ECG_FFA_FLP2 && Cin % 8 == 0 && Cin >= ECG_FFA_FLP2) \
+        hipLaunchKernelGGL((conv1d_mfma_ffa_kernel<CO_T, T_T / 2, WCO, WT, MODE, 4, 2>), grid, block, 0, st, x, wp, \
+                           bias, y, partials, Cin, Cout, L, ldx, Lo, pad, P, tiles_t, EV); \
+    else \
+        hipLaunchKernelGGL((conv1d_mfma_ffa_kernel<CO_T, T_T / 2, WCO, WT, MODE>), grid, block, 0, st, x, wp, bias, y, \
+                           partials, Cin, Cout, L, ldx, Lo, pad, P, tiles_t, EV); } while (0)
+    if (ev && ev->gap) ECG_FFA(EPI_EVAL_GAP, *ev);
+    else if (ev) ECG_FFA(EPI_EVAL, *ev);
+    else if (partials) ECG_FFA(EPI_STATS, none);
+    else ECG_FFA(EPI_PLAIN, none);
+#undef ECG_FFA
 }
 
 static int mfma_fwd_any(const float *x, const float *wp, const float *bias, float *y,
                         float *partials, const EvalEpi *ev, int N, int Cin, int Cout, int L, int ldx,
                         int K, int pad, hipStream_t st) {
     const int Lo = L + 2 * pad - K + 1;
-    const FwdCfg c = fwd_cfg(N, Cout, Lo, ev == nullptr);
-    if (c.co_t == 64)
+    if (fwd_cfg(Cout).co_t == 64)
         launch_fwd<64, 128, 2, 2>(x, wp, bias, y, partials, ev, N, Cin, Cout, L, ldx, Lo, pad, st);
     else
         launch_fwd<32, 256, 1, 4>(x, wp, bias, y, partials, ev, N, Cin, Cout, L, ldx, Lo, pad, st);
-    return check_launch("conv1d_mfma_fwd_kernel");
+    return check_launch("conv1d_mfma_ffa_kernel");
 }
 
 // ldx >= L is the row stride of x (dgrad reads a row-padded dY through it)
@@ -799,7 +462,7 @@ int mfma_fwd_eval_pool(const float *x, const float *wp, const float *bias, const
 
 bool mfma_fwd_eval_gap_supported(int Cin, int Cout, int L, int K, int pad) {
     const int Lo = L + 2 * pad - K + 1;
-    return mfma_fwd_supported(Cin, Cout, K, pad) && Lo >= 2 && Lo <= fwd_cfg(1, Cout, Lo, false).stride;
+    return mfma_fwd_supported(Cin, Cout, K, pad) && Lo >= 2 && Lo <= fwd_cfg(Cout).stride;
 }
 
 // =======================================================================================
@@ -814,8 +477,8 @@ bool mfma_fwd_eval_gap_supported(int Cin, int Cout, int L, int K, int pad) {
 // (i+1)&1 (first half of the steps) and the loads of stage i+2 are issued (second half), one
 // staging operation per MFMA group; ONE barrier closes the stage.  Per-thread global offsets are
 // loop-invariant; a stage only moves uniform base pointers.
-// FL: two-level accumulation (see conv1d_mfma_wgrad_dma_kernel below).
-template <int M_T, int R_T, int WM, int WR, int WK, int T_T, int KK, int FL = 1>
+// Two-level accumulation: see conv1d_mfma_wgrad_dma_kernel below.
+template <int M_T, int R_T, int WM, int WR, int WK, int T_T, int KK>
 __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_kernel(
     const float *__restrict__ dy, const float *__restrict__ x, float *__restrict__ slab, int N,
     int Cin, int Cout, int L, int Lo, int ldy, int pad, int S) {
@@ -863,7 +526,7 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_kernel(
         xcol[j] = (ci - ci_base) * XS + (r - ci * KK);
     }
 
-    f32x16 acc[MC][MR], acc2[MC][MR];      // acc2: the second level (FL), dead otherwise
+    f32x16 acc[MC][MR], acc2[MC][MR];      // acc2: the second level
     f32x16 zero16;
 #pragma unroll
     for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
@@ -986,36 +649,33 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_kernel(
             }
             __builtin_amdgcn_sched_barrier(0);         // keep reads + staging ABOVE these MFMAs
 #pragma unroll
-            for (int i = 0; i < MC; ++i) bsum[i] = (FL && st == 0) ? a_c[i] : bsum[i] + a_c[i];   // bias-grad rides on the A fragments
+            for (int i = 0; i < MC; ++i) bsum[i] = (st == 0) ? a_c[i] : bsum[i] + a_c[i];   // bias-grad rides on the A fragments
 #pragma unroll
             for (int i = 0; i < MC; ++i)
 #pragma unroll
                 for (int j = 0; j < MR; ++j)
-                    acc[i][j] = mfma32(a_c[i], b_c[j], (FL && st == 0) ? zero16 : acc[i][j]);
+                    acc[i][j] = mfma32(a_c[i], b_c[j], (st == 0) ? zero16 : acc[i][j]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int i = 0; i < MC; ++i) a_c[i] = a_n[i];
 #pragma unroll
             for (int j = 0; j < MR; ++j) b_c[j] = b_n[j];
         }
-        if (FL) {               // second level: the stage's sums join the running totals
+        // second level: the stage's sums join the running totals
 #pragma unroll
-            for (int i = 0; i < MC; ++i)
+        for (int i = 0; i < MC; ++i)
 #pragma unroll
-                for (int j = 0; j < MR; ++j) acc2[i][j] += acc[i][j];
+            for (int j = 0; j < MR; ++j) acc2[i][j] += acc[i][j];
 #pragma unroll
-            for (int i = 0; i < MC; ++i) bsum2[i] += bsum[i];
-        }
+        for (int i = 0; i < MC; ++i) bsum2[i] += bsum[i];
         __syncthreads();      // image it&1 free again; image (it+1)&1 complete
     }
 
-    if (FL) {
 #pragma unroll
-        for (int i = 0; i < MC; ++i) {
-            bsum[i] = bsum2[i];
+    for (int i = 0; i < MC; ++i) {
+        bsum[i] = bsum2[i];
 #pragma unroll
-            for (int j = 0; j < MR; ++j) acc[i][j] = acc2[i][j];
-        }
+        for (int j = 0; j < MR; ++j) acc[i][j] = acc2[i][j];
     }
     // ---- combine the WK t-split waves through LDS (fixed order), then write the slab ---------
     if (WK > 1) {
@@ -1099,17 +759,17 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_kernel(
 //   kernel above and read at +4h+j.
 // grid = (ceil(R/R_T), Cout/M_T, S); T_T = 64; slab layout as above.
 //
-// TWO-LEVEL ACCUMULATION (FL != 0).  v_mfma_f32_32x32x2_f32 is one k-ordered fp32 fma chain, so a workgroup that
+// TWO-LEVEL ACCUMULATION.  v_mfma_f32_32x32x2_f32 is one k-ordered fp32 fma chain, so a workgroup that
 // multiplies `total` stages into one accumulator builds a chain of 64 * total terms (512 ... 1 900 at B = 256): its
 // rounding error grows with the square root of that length and at the headline batch exceeded what oneDNN's blocked
-// sums leave (tests/test_gpu_model.py: float64 trajectory).  With FL the first MFMA of every stage starts from the
+// sums leave (tests/test_gpu_model.py: float64 trajectory).  So the first MFMA of every stage starts from the
 // inline constant 0 and the stage's 64-term sum is added to a second register set at the end of the stage: chains of
 // 64 + total terms, fixed order (bitwise reproducible), no extra memory traffic; cost = one v_pk_add_f32 per two
 // accumulator registers per stage (32 MFMAs of 64 cycles per register pair).
 // T_T = 128 (round 5, the 64- and 32-channel tiles of blocks 0-1): a stage of 128 time steps — the fixed cost per stage (barrier,
 // drained waits, DMA issue, the second-level adds) is paid half as often on the layers whose stages are shortest; needs the
 // row stride to be a multiple of 128 floats, and two images of 38 KB still leave two workgroups per CU.
-template <int M_T, int R_T, int WM, int WR, int WK, int KK, int FL = 1, int T_T = 64>
+template <int M_T, int R_T, int WM, int WR, int WK, int KK, int T_T = 64>
 __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_dma_kernel(
     const float *__restrict__ dy, const float *__restrict__ x, float *__restrict__ slab, int N,
     int Cin, int Cout, int L, int Lo, int ldy, int pad, int S) {
@@ -1136,7 +796,7 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_dma_kernel(
     static_assert(NST >= 2 * XLOADS + DPW, "not enough steps to spread the staging over");
 
     __shared__ __attribute__((aligned(1024))) float lds[2 * IMG];
-    ECG_STAMP_AT(0);
+    ECG_STAMP_AT(g_stamps, 0);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, l31 = lane & 31;
@@ -1163,7 +823,7 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_dma_kernel(
         xcol[j] = (ci - ci_base) * XS + (r - ci * KK);
     }
 
-    f32x16 acc[MC][MR], acc2[MC][MR];      // acc2: the second level (FL), dead otherwise
+    f32x16 acc[MC][MR], acc2[MC][MR];      // acc2: the second level
     f32x16 zero16;
 #pragma unroll
     for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
@@ -1236,7 +896,7 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_dma_kernel(
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (the asm DMA pieces are not in hipcc's books)
     __syncthreads();
-    ECG_STAMP_AT(1);
+    ECG_STAMP_AT(g_stamps, 1);
 
     const int aoff = (wm0 + l31) * T_T, swz = (l31 & 15) << 2;
     for (int it = 0; it < total; ++it) {
@@ -1275,12 +935,12 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_dma_kernel(
             else if (st < 2 * XLOADS + DPW) dma_a(st - 2 * XLOADS, nxt);
             __builtin_amdgcn_sched_barrier(0);         // keep reads + staging ABOVE these MFMAs
 #pragma unroll
-            for (int i = 0; i < MC; ++i) bsum[i] = (FL && st == 0) ? aq_c[i][j4] : bsum[i] + aq_c[i][j4];
+            for (int i = 0; i < MC; ++i) bsum[i] = (st == 0) ? aq_c[i][j4] : bsum[i] + aq_c[i][j4];
 #pragma unroll
             for (int i = 0; i < MC; ++i)
 #pragma unroll
                 for (int j = 0; j < MR; ++j)
-                    acc[i][j] = mfma32(aq_c[i][j4], b_c[j], (FL && st == 0) ? zero16 : acc[i][j]);
+                    acc[i][j] = mfma32(aq_c[i][j4], b_c[j], (st == 0) ? zero16 : acc[i][j]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int j = 0; j < MR; ++j) b_c[j] = b_n[j];
@@ -1289,21 +949,20 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_dma_kernel(
                 for (int i = 0; i < MC; ++i) aq_c[i] = aq_n[i];
             }
         }
-        if (FL) {               // second level: the stage's sums join the running totals, in issue order of the MFMAs
+        // second level: the stage's sums join the running totals, in issue order of the MFMAs
 #pragma unroll
-            for (int i = 0; i < MC; ++i)
+        for (int i = 0; i < MC; ++i)
 #pragma unroll
-                for (int j = 0; j < MR; ++j) acc2[i][j] += acc[i][j];
+            for (int j = 0; j < MR; ++j) acc2[i][j] += acc[i][j];
 #pragma unroll
-            for (int i = 0; i < MC; ++i) bsum2[i] += bsum[i];
-        }
+        for (int i = 0; i < MC; ++i) bsum2[i] += bsum[i];
         dn = sn; dtt = stt;
         advance();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();      // image it&1 free again; image (it+1)&1 complete (vmcnt(0) + barrier)
-        if (it == 0) ECG_STAMP_AT(2);
+        if (it == 0) ECG_STAMP_AT(g_stamps, 2);
     }
-    ECG_STAMP_AT(3);
+    ECG_STAMP_AT(g_stamps, 3);
 #ifdef ECG_STAMP
     if (g_stamps && threadIdx.x == 0)          // stages | HW_ID (cu / sh / se) << 16 | XCC_ID << 48: which workgroups share a CU
         g_stamps[(size_t)blockIdx.x * 8 + 5] = (unsigned long long)(total & 0xFFFF) |
@@ -1311,13 +970,11 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_dma_kernel(
             ((unsigned long long)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xF) << 48);
 #endif
 
-    if (FL) {
 #pragma unroll
-        for (int i = 0; i < MC; ++i) {
-            bsum[i] = bsum2[i];
+    for (int i = 0; i < MC; ++i) {
+        bsum[i] = bsum2[i];
 #pragma unroll
-            for (int j = 0; j < MR; ++j) acc[i][j] = acc2[i][j];
-        }
+        for (int j = 0; j < MR; ++j) acc[i][j] = acc2[i][j];
     }
     if (want_bias) {
 #pragma unroll
@@ -1374,7 +1031,7 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_dma_kernel(
 #ifdef ECG_STAMP
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
-    ECG_STAMP_AT(4);
+    ECG_STAMP_AT(g_stamps, 4);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1393,7 +1050,7 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_dma_kernel(
 // Slab layout: [s][co][U columns ci*8+j | V columns ci*7+j | G columns ci*8+j] (+ the bias slab); wgrad_ffa_reduce_kernel
 // adds the slabs in double, in slab order, and forms the 15 taps.  Image, DMA, swizzle, two-level accumulation: as in
 // conv1d_mfma_wgrad_dma_kernel above.
-template <int M_T, int R_T, int WM, int WR, int FL, int T_T>
+template <int M_T, int R_T, int WM, int WR, int T_T>
 __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_ffa_kernel(
     const float *__restrict__ dy, const float *__restrict__ x, float *__restrict__ slab, int N,
     int Cin, int Cout, int L, int Lo, int ldy, int pad, int S) {
@@ -1417,7 +1074,7 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_ffa_kernel(
     static_assert(2 * IMG * 4 <= 80 * 1024, "two workgroups per CU");
 
     __shared__ __attribute__((aligned(1024))) float lds[2 * IMG];
-    ECG_STAMP_AT(0);
+    ECG_STAMP_AT(g_stamps, 0);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, l31 = lane & 31;
@@ -1509,7 +1166,7 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_ffa_kernel(
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    ECG_STAMP_AT(1);
+    ECG_STAMP_AT(g_stamps, 1);
 
     typedef float f32x2t __attribute__((ext_vector_type(2)));
     const int aoff = (wm0 + l31) * T_T, swz = (l31 & 15) << 2;
@@ -1578,13 +1235,13 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_ffa_kernel(
             __builtin_amdgcn_sched_barrier(0);
             if (FAM == 0) {
 #pragma unroll
-                for (int i = 0; i < MC; ++i) bsum[i] = (FL && st == 0) ? av[i] : bsum[i] + av[i];
+                for (int i = 0; i < MC; ++i) bsum[i] = (st == 0) ? av[i] : bsum[i] + av[i];
             }
 #pragma unroll
             for (int i = 0; i < MC; ++i)
 #pragma unroll
                 for (int j = 0; j < MR; ++j)
-                    acc[i][j] = mfma32(av[i], bv[j], (FL && st == 0) ? zero16 : acc[i][j]);
+                    acc[i][j] = mfma32(av[i], bv[j], (st == 0) ? zero16 : acc[i][j]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int j = 0; j < MR; ++j) b_c[j] = b_n[j];
@@ -1604,39 +1261,35 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_ffa_kernel(
                     acc[i][j] = mfma32(a, xs[xcol[j] - 8 * half + T_T + 1], acc[i][j]);
             }
         }
-        if (FL) {
 #pragma unroll
-            for (int i = 0; i < MC; ++i)
+        for (int i = 0; i < MC; ++i)
 #pragma unroll
-                for (int j = 0; j < MR; ++j) acc2[i][j] += acc[i][j];
-            if (FAM == 0) {
+            for (int j = 0; j < MR; ++j) acc2[i][j] += acc[i][j];
+        if (FAM == 0) {
 #pragma unroll
-                for (int i = 0; i < MC; ++i) bsum2[i] += bsum[i];
-            }
+            for (int i = 0; i < MC; ++i) bsum2[i] += bsum[i];
         }
         dn = sn; dtt = stt;
         advance();
         asm volatile("s_waitcnt vmcnt(%0)" :: "n"(XLOADS) : "memory");    // the DMA pieces are older than the x loads
         __syncthreads();
     };
-    if (fam == 0) { for (int it = 0; it < total; ++it) { stage(std::integral_constant<int, 0>{}, it); if (it == 0) ECG_STAMP_AT(2); } }
-    else if (fam == 1) { for (int it = 0; it < total; ++it) { stage(std::integral_constant<int, 1>{}, it); if (it == 0) ECG_STAMP_AT(2); } }
-    else { for (int it = 0; it < total; ++it) { stage(std::integral_constant<int, 2>{}, it); if (it == 0) ECG_STAMP_AT(2); } }
-    ECG_STAMP_AT(3);
+    if (fam == 0) { for (int it = 0; it < total; ++it) { stage(std::integral_constant<int, 0>{}, it); if (it == 0) ECG_STAMP_AT(g_stamps, 2); } }
+    else if (fam == 1) { for (int it = 0; it < total; ++it) { stage(std::integral_constant<int, 1>{}, it); if (it == 0) ECG_STAMP_AT(g_stamps, 2); } }
+    else { for (int it = 0; it < total; ++it) { stage(std::integral_constant<int, 2>{}, it); if (it == 0) ECG_STAMP_AT(g_stamps, 2); } }
+    ECG_STAMP_AT(g_stamps, 3);
 #ifdef ECG_STAMP
-    if (g_stamps && threadIdx.x == 0)          // stages | HW_ID << 16 | XCC_ID << 48 (as the direct kernel)
+    if (g_stamps && threadIdx.x == 0)          // stages | HW_ID << 16 | XCC_ID << 48 (as conv1d_mfma_wgrad_dma_kernel)
         g_stamps[(size_t)blockIdx.x * 8 + 5] = (unsigned long long)(total & 0xFFFF) |
             ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 16) |
             ((unsigned long long)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xF) << 48);
 #endif
 
-    if (FL) {
 #pragma unroll
-        for (int i = 0; i < MC; ++i) {
-            bsum[i] = bsum2[i];
+    for (int i = 0; i < MC; ++i) {
+        bsum[i] = bsum2[i];
 #pragma unroll
-            for (int j = 0; j < MR; ++j) acc[i][j] = acc2[i][j];
-        }
+        for (int j = 0; j < MR; ++j) acc[i][j] = acc2[i][j];
     }
     if (want_bias) {
 #pragma unroll
@@ -1665,7 +1318,7 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_ffa_kernel(
 #ifdef ECG_STAMP
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
-    ECG_STAMP_AT(4);
+    ECG_STAMP_AT(g_stamps, 4);
 }
 
 // dw[co][ci][k] from the S slabs of the kernel above: one lane per (co, ci, tap pair j) forms dW[2j] = U[j] - G[j] and
@@ -1673,7 +1326,6 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_ffa_kernel(
 // as in wgrad_reduce_kernel.  One wave per workgroup: the layers that take this form have >= 2 048 of them.
 __global__ __launch_bounds__(64) void wgrad_ffa_reduce_kernel(const float *__restrict__ slab, float *__restrict__ dw,
                                                               float *__restrict__ db, int Cin, int Cout, int S) {
-    constexpr int G = 1, w = 0;
     const int lane = threadIdx.x;
     const size_t i = (size_t)blockIdx.x * 64 + lane;
     const size_t npair = (size_t)Cout * Cin * 8, RVT = (size_t)Cin * 23, wslab = (size_t)Cout * RVT;
@@ -1692,12 +1344,12 @@ __global__ __launch_bounds__(64) void wgrad_ffa_reduce_kernel(const float *__res
             const float *pg = slab + (size_t)co * RVT + Cin * 15 + ci * 8 + j;
             const float *pv = slab + (size_t)co * RVT + Cin * 8 + ci * 7 + jv;
             const int g1 = j < 7 ? 1 : 0;
-            int s = w;
-            for (; s + 3 * G < S; s += 4 * G) {
+            int s = 0;
+            for (; s + 3 < S; s += 4) {
                 float v[4][4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    const size_t off = (size_t)(s + u * G) * wslab;
+                    const size_t off = (size_t)(s + u) * wslab;
                     v[u][0] = pu[off]; v[u][1] = pg[off]; v[u][2] = pv[off]; v[u][3] = pg[off + g1];
                 }
 #pragma unroll
@@ -1705,13 +1357,13 @@ __global__ __launch_bounds__(64) void wgrad_ffa_reduce_kernel(const float *__res
 #pragma unroll
                     for (int e = 0; e < 4; ++e) a[e] += (double)v[u][e];
             }
-            for (; s < S; s += G) {
+            for (; s < S; ++s) {
                 const size_t off = (size_t)s * wslab;
                 a[0] += (double)pu[off]; a[1] += (double)pg[off]; a[2] += (double)pv[off]; a[3] += (double)pg[off + g1];
             }
         } else {
             const float *src = slab + (size_t)S * wslab + (i - npair);
-            for (int s = w; s < S; s += G) a[0] += (double)src[(size_t)s * Cout];
+            for (int s = 0; s < S; ++s) a[0] += (double)src[(size_t)s * Cout];
         }
     }
     if (live) {
@@ -1726,9 +1378,6 @@ __global__ __launch_bounds__(64) void wgrad_ffa_reduce_kernel(const float *__res
 int wgrad_reduce(const float *ws, float *dw, float *db, size_t wslab, int Cout, int S,
                  hipStream_t st);
 
-#ifndef ECG_WG_FL
-#define ECG_WG_FL 1          // two-level accumulation; tools build -DECG_WG_FL=0 to A/B its cost and its effect on the error
-#endif
 struct WgCfg { int m_t, r_t, splits; };
 
 // Development knobs are COMPILE-TIME (A/B libraries: make VARIANT=x EXTRA="-DECG_WG_SLOTS=768"): the product library reads no
@@ -1736,25 +1385,21 @@ struct WgCfg { int m_t, r_t, splits; };
 #ifndef ECG_WG_SLOTS
 #define ECG_WG_SLOTS 512
 #endif
-#ifndef ECG_WG_RT
-#define ECG_WG_RT 0
-#endif
 #ifndef ECG_WG_TT128
 #define ECG_WG_TT128 1       // 128-step stages on the 64- / 32-channel tiles (A/B: -DECG_WG_TT128=0)
 #endif
 
 static WgCfg wgrad_cfg(int N, int Cin, int Cout, int Lo, bool dma, int tt = 64) {
     const int R = Cin * kKM;
-    constexpr int slots = ECG_WG_SLOTS, rt128 = ECG_WG_RT;
+    constexpr int slots = ECG_WG_SLOTS;
     WgCfg c;
-    // 128 x 192 tiles where 128-wide column tiles would leave a ragged last tile and 192 divide the columns (block 2:
-    // R = 960 = 5 x 192 instead of 7.5 x 128: 154.7 -> 150.3 us; block 3, R = 1920 = 15 x 128 = 10 x 192: 264.0 vs 267.5 us,
-    // stays at 128).  More, smaller workgroups (ECG_WG_SLOTS 768 / 1024: a second round in the slots the early finishers
+    // 128 x 128 tiles on the 128-channel layers.  (128 x 192 tiles, where 192 divide the columns and 128 leave a ragged last
+    // tile — block 2: R = 960 = 5 x 192 instead of 7.5 x 128 — measured 154.7 -> 150.3 us with single-level accumulation; with
+    // the two-level accumulation that tile needs 96 + 96 accumulator registers and spills, so it is not built: +3 us on
+    // block 2.  Block 3, R = 1920 = 15 x 128 = 10 x 192: 264.0 vs 267.5 us, 128 was the better tile anyway.)
+    // More, smaller workgroups (ECG_WG_SLOTS 768 / 1024: a second round in the slots the early finishers
     // free) measured 2-8 % SLOWER on every layer — the second prologue / slab costs more than the tail it evens out.
-    // (With the two-level accumulation the 128 x 192 tile needs 96 + 96 accumulator registers and spills: it is only
-    // instantiated in the single-level A/B build; block 2 then takes 128 x 128 tiles, +3 us.)
-    const bool wide = dma && !ECG_WG_FL && R % 192 == 0 && (rt128 == 192 || (rt128 == 0 && R % 128 != 0));
-    if (Cout % 128 == 0) c = {128, wide ? 192 : 128, 0};
+    if (Cout % 128 == 0) c = {128, 128, 0};
     else if (Cout % 64 == 0) c = {64, 128, 0};
     else c = {32, 192, 0};
     const int tiles = cdiv(R, c.r_t) * (Cout / c.m_t);
@@ -1770,18 +1415,15 @@ static WgCfg wgrad_cfg(int N, int Cin, int Cout, int Lo, bool dma, int tt = 64) 
     return c;
 }
 
-#ifndef ECG_WG_FFA
-#define ECG_WG_FFA 1         // fast-FIR weight gradient on the 64- / 128-channel tiles (A/B: -DECG_WG_FFA=0)
-#endif
-// fast-FIR form: column tiles of 128 over the three families (U: 8 C_in, V: 7 C_in, G: 8 C_in columns), 64-step stages
+// fast-FIR form: 128-channel tiles, column tiles of 128 over the three families (U: 8 C_in, V: 7 C_in, G: 8 C_in columns),
+// 64-step stages.
 // Measured (B = 256, 12x1000, same box): 128 -> 256 channels 290.3 -> 277.0 us; 64 -> 128 164.5 -> 164.8; 32 -> 64 88.9 -> 94.4 —
 // a stage is half as many MFMA steps between the same barrier, x commits and second-level adds (~2 000 cycles per stage
 // in both forms), and 128-step stages do not fit two workgroups per CU here: used where the column count makes it pay.
-static bool wgrad_ffa_ok(int Cin, int Cout, bool dma) { return ECG_WG_FFA && dma && Cout % 128 == 0 && Cin >= 128; }
+static bool wgrad_ffa_ok(int Cin, int Cout, bool dma) { return dma && Cout % 128 == 0 && Cin >= 128; }
+static int wgrad_ffa_tiles(int Cin, int Cout) { return (2 * cdiv(Cin * 8, 128) + cdiv(Cin * 7, 128)) * (Cout / 128); }
 static int wgrad_ffa_splits(int N, int Cin, int Cout, int Lo) {
-    const int m_t = Cout % 128 == 0 ? 128 : 64;
-    const int tiles = (2 * cdiv(Cin * 8, 128) + cdiv(Cin * 7, 128)) * (Cout / m_t);
-    long long s = ECG_WG_SLOTS / tiles;
+    long long s = ECG_WG_SLOTS / wgrad_ffa_tiles(Cin, Cout);
     const long long cap = (long long)N * cdiv(Lo, 64);
     if (s > cap) s = cap;
     if (s < 1) s = 1;
@@ -1793,7 +1435,7 @@ bool mfma_wgrad_dma_supported(int Cin, int Cout, int K);
 int mfma_multiplies_per_pair(int op, int Cin, int Cout, int K, int pad) {
     if (op == 2) return (K == kKM && wgrad_ffa_ok(Cin, Cout, mfma_wgrad_dma_supported(Cin, Cout, K))) ? 23 : 2 * K;
     const bool mfma = op == 1 ? mfma_fwd_supported(Cout, Cin, K, K - 1 - pad) : mfma_fwd_supported(Cin, Cout, K, pad);
-    return (mfma && (ECG_FWD_FFA & (op == 0 ? 1 : (op == 1 ? 2 : 4)))) ? 23 : 2 * K;
+    return mfma ? 23 : 2 * K;
 }
 
 bool mfma_wgrad_supported(int Cin, int Cout, int K, int pad) {
@@ -1827,15 +1469,10 @@ int mfma_wgrad(const float *dy, int ldy, const float *x, float *dw, float *db, f
     // 128-step stages for the small tiles (blocks 0-1) when the rows allow it (stride a multiple of 128 floats, zero pad to it)
     const bool tt128 = ECG_WG_TT128 && dma && Cout % 128 != 0 && ldy % 128 == 0 && ldy >= cdiv(Lo, 128) * 128;
     if (wgrad_ffa_ok(Cin, Cout, dma)) {
-        const int S = wgrad_ffa_splits(N, Cin, Cout, Lo), m_t = Cout % 128 == 0 ? 128 : 64;
-        const int tiles = (2 * cdiv(Cin * 8, 128) + cdiv(Cin * 7, 128)) * (Cout / m_t);
-        dim3 fgrid((unsigned)(tiles * S)), fblock(256);
-        if (m_t == 128)
-            hipLaunchKernelGGL((conv1d_mfma_wgrad_ffa_kernel<128, 128, 2, 2, ECG_WG_FL, 64>), fgrid, fblock, 0, st, dy, x, ws, N, Cin,
-                               Cout, L, Lo, ldy, pad, S);
-        else
-            hipLaunchKernelGGL((conv1d_mfma_wgrad_ffa_kernel<64, 128, 2, 2, ECG_WG_FL, 64>), fgrid, fblock, 0, st, dy, x, ws, N, Cin,
-                               Cout, L, Lo, ldy, pad, S);
+        const int S = wgrad_ffa_splits(N, Cin, Cout, Lo);
+        dim3 fgrid((unsigned)(wgrad_ffa_tiles(Cin, Cout) * S)), fblock(256);
+        hipLaunchKernelGGL((conv1d_mfma_wgrad_ffa_kernel<128, 128, 2, 2, 64>), fgrid, fblock, 0, st, dy, x, ws, N, Cin, Cout, L, Lo,
+                           ldy, pad, S);
         int frc = check_launch("conv1d_mfma_wgrad_ffa_kernel");
         if (frc) return frc;
         const size_t nout = (size_t)Cout * Cin * 8 + Cout;          // one lane per (co, ci, tap pair) + the bias row
@@ -1847,18 +1484,14 @@ int mfma_wgrad(const float *dy, int ldy, const float *x, float *dw, float *db, f
     dim3 grid((unsigned)(cdiv(R, c.r_t) * (Cout / c.m_t) * c.splits)), block(256);
 #define ECG_WG(KERNEL) \
     hipLaunchKernelGGL(KERNEL, grid, block, 0, st, dy, x, ws, N, Cin, Cout, L, Lo, ldy, pad, c.splits)
-#if !ECG_WG_FL
-    if (dma && c.m_t == 128 && c.r_t == 192) ECG_WG((conv1d_mfma_wgrad_dma_kernel<128, 192, 2, 2, 1, kKM, 0>));
-    else
-#endif
-    if (dma && c.m_t == 128) ECG_WG((conv1d_mfma_wgrad_dma_kernel<128, 128, 2, 2, 1, kKM, ECG_WG_FL>));
-    else if (tt128 && c.m_t == 64) ECG_WG((conv1d_mfma_wgrad_dma_kernel<64, 128, 2, 2, 1, kKM, ECG_WG_FL, 128>));
-    else if (tt128) ECG_WG((conv1d_mfma_wgrad_dma_kernel<32, 192, 1, 2, 2, kKM, ECG_WG_FL, 128>));
-    else if (dma && c.m_t == 64) ECG_WG((conv1d_mfma_wgrad_dma_kernel<64, 128, 2, 2, 1, kKM, ECG_WG_FL>));
-    else if (dma) ECG_WG((conv1d_mfma_wgrad_dma_kernel<32, 192, 1, 2, 2, kKM, ECG_WG_FL>));
-    else if (c.m_t == 128) ECG_WG((conv1d_mfma_wgrad_kernel<128, 128, 2, 2, 1, 64, kKM, ECG_WG_FL>));
-    else if (c.m_t == 64) ECG_WG((conv1d_mfma_wgrad_kernel<64, 128, 2, 2, 1, 64, kKM, ECG_WG_FL>));
-    else ECG_WG((conv1d_mfma_wgrad_kernel<32, 192, 1, 2, 2, 128, kKM, ECG_WG_FL>));
+    if (dma && c.m_t == 128) ECG_WG((conv1d_mfma_wgrad_dma_kernel<128, 128, 2, 2, 1, kKM>));
+    else if (tt128 && c.m_t == 64) ECG_WG((conv1d_mfma_wgrad_dma_kernel<64, 128, 2, 2, 1, kKM, 128>));
+    else if (tt128) ECG_WG((conv1d_mfma_wgrad_dma_kernel<32, 192, 1, 2, 2, kKM, 128>));
+    else if (dma && c.m_t == 64) ECG_WG((conv1d_mfma_wgrad_dma_kernel<64, 128, 2, 2, 1, kKM>));
+    else if (dma) ECG_WG((conv1d_mfma_wgrad_dma_kernel<32, 192, 1, 2, 2, kKM>));
+    else if (c.m_t == 128) ECG_WG((conv1d_mfma_wgrad_kernel<128, 128, 2, 2, 1, 64, kKM>));
+    else if (c.m_t == 64) ECG_WG((conv1d_mfma_wgrad_kernel<64, 128, 2, 2, 1, 64, kKM>));
+    else ECG_WG((conv1d_mfma_wgrad_kernel<32, 192, 1, 2, 2, 128, kKM>));
 #undef ECG_WG
     int rc = check_launch("conv1d_mfma_wgrad_kernel");
     if (rc) return rc;

@@ -14,29 +14,17 @@
 //
 // Replaces the ATen work behind ConvBlock.net[0] (reference src/models/ecg_cnn.py:13); the
 // reference itself has no mixed precision (`amp: true` in its YAML is a dead key).
-#include "common.h"
+#include "mfma_util.h"
 
 namespace ecg {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-
-// in-kernel stamps of the diagnostic build (make STAMP=1), as in conv1d_mfma.hip
+// in-kernel stamps of the diagnostic build (make STAMP=1): ECG_STAMP_AT(g_stamps_b, slot), mfma_util.h
 #ifdef ECG_STAMP
 __device__ unsigned long long *g_stamps_b = nullptr;
-#define ECG_STAMPB_AT(slot) do { if (g_stamps_b && threadIdx.x == 0) { \
-    g_stamps_b[(size_t)blockIdx.x * 8 + (slot)] = __builtin_amdgcn_s_memtime(); \
-    if ((slot) == 0) g_stamps_b[(size_t)blockIdx.x * 8 + 7] = __builtin_amdgcn_s_memrealtime(); \
-    if ((slot) == 4) g_stamps_b[(size_t)blockIdx.x * 8 + 6] = __builtin_amdgcn_s_memrealtime(); } } while (0)
-#else
-#define ECG_STAMPB_AT(slot) do { } while (0)
 #endif
 
 constexpr int kKB = 15;      // kernel size staged by this path
 constexpr int kCB = 16;      // input channels per MFMA (its K dimension)
-
-__device__ __forceinline__ int acc_row_b(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 // s_waitcnt vmcnt(N) with lgkmcnt / expcnt left at "no wait"
 template <int N>
@@ -115,13 +103,13 @@ __global__ void pack_weights_bf16_kernel(const float *__restrict__ w, u16 *__res
 //   * WRES: layers with at most two 16-channel chunks (blocks 0 and 1 forward) keep their whole weight slice
 //     resident — image 0 holds chunk 0, image 1 chunk 1 (or chunk 0 again), loaded once per workgroup; only x tiles
 //     stream after that.
-//   * YH: the OUTPUT is stored as bf16 ([N][C_out][ldyo] u16, row stride ldyo >= Lo) — bf16 activation storage of the
+//   * the OUTPUT is stored as bf16 ([N][C_out][ldyo] u16, row stride ldyo >= Lo) — bf16 activation storage of the
 //     train step: the BatchNorm passes then read half the bytes.  The statistics are taken over the ROUNDED values,
 //     i.e. exactly over the tensor the BatchNorm passes will read.
-template <int CO_T, int T_T, int WCO, int WT, bool STATS, bool XH = false, bool WRES = false, bool YH = false>
+template <int CO_T, int T_T, int WCO, int WT, bool STATS, bool XH = false, bool WRES = false>
 __global__ __launch_bounds__(64 * WCO * WT) __attribute__((amdgpu_waves_per_eu(2))) void conv1d_mfma_bf16_fwd_kernel(
     const float *__restrict__ x, const u16 *__restrict__ wb, const float *__restrict__ bias,
-    float *__restrict__ y, float *__restrict__ partials, int Cin, int Cout, int L, int Lo, int pad,
+    u16 *__restrict__ y, float *__restrict__ partials, int Cin, int Cout, int L, int Lo, int pad,
     int tiles_t, int N, int G, int ldx, int ldyo) {
     constexpr int NW = WCO * WT, NT = 64 * NW;
     static_assert(NW == 4 || NW == 8, "4 or 8 waves per workgroup");
@@ -150,14 +138,9 @@ __global__ __launch_bounds__(64 * WCO * WT) __attribute__((amdgpu_waves_per_eu(2
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, l31 = lane & 31;
-    ECG_STAMPB_AT(0);
-    // XCD-aware workgroup order (as conv1d_mfma.hip): the C_out tiles of one tile range read the same x panels
-    int wg;
-    {
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    ECG_STAMP_AT(g_stamps_b, 0);
+    // XCD-aware workgroup order: the C_out tiles of one tile range read the same x panels
+    const int wg = xcd_chunked(blockIdx.x, gridDim.x);
     const int CT = Cout / CO_T;
     const int tile_co = wg % CT, g = wg / CT;
     const int ntiles = N * tiles_t;
@@ -181,7 +164,7 @@ __global__ __launch_bounds__(64 * WCO * WT) __attribute__((amdgpu_waves_per_eu(2
     float p_b[MC], st_s[MC], st_q[MC];
 #pragma unroll
     for (int i = 0; i < MC; ++i) {
-        p_b[i] = bias ? bias[co0 + wco + 32 * i + acc_row_b(l31 & 15, half)] : 0.f;
+        p_b[i] = bias ? bias[co0 + wco + 32 * i + acc_row(l31 & 15, half)] : 0.f;
         st_s[i] = 0.f; st_q[i] = 0.f;
     }
 
@@ -284,7 +267,7 @@ __global__ __launch_bounds__(64 * WCO * WT) __attribute__((amdgpu_waves_per_eu(2
     };
 
     // ---- epilogue of a finished tile: one (accumulator row r, channel group i) item per call ---------
-    float *ytile = y;                    // (n, co0, t0) of the finished tile (YH: the same in u16 elements)
+    u16 *ytile = y;                      // (n, co0, t0) of the finished tile
     int pt0 = 0;
     const int ylane = (wco + 4 * half) * ldyo + wt + l31;
     auto epilogue_item = [&](int it) {
@@ -294,18 +277,15 @@ __global__ __launch_bounds__(64 * WCO * WT) __attribute__((amdgpu_waves_per_eu(2
         const float bhi = __int_as_float(__builtin_amdgcn_readlane(bi, r + 32));
         const float bv = half ? bhi : blo;
         const int yoff = (32 * i + (r & 3) + 8 * (r >> 2)) * ldyo + ylane;
-        float *yr = ytile + yoff;
-        u16 *yhr = reinterpret_cast<u16 *>(ytile) + yoff;
+        u16 *yr = ytile + yoff;
         float s = 0.f, q = 0.f;
 #pragma unroll
         for (int j = 0; j < MT; ++j) {
             float v = acc[i][j][r] + bv;
             if (pt0 + wt + 32 * j + l31 < Lo) {
-                if (YH) {
-                    const u16 h = __builtin_bit_cast(u16, (__bf16)v);
-                    yhr[32 * j] = h;
-                    v = __uint_as_float((unsigned)h << 16);
-                } else yr[32 * j] = v;
+                const u16 h = __builtin_bit_cast(u16, (__bf16)v);
+                yr[32 * j] = h;
+                v = __uint_as_float((unsigned)h << 16);
                 if (STATS) { s += v; q = __fmaf_rn(v, v, q); }
             }
         }
@@ -334,7 +314,7 @@ __global__ __launch_bounds__(64 * WCO * WT) __attribute__((amdgpu_waves_per_eu(2
     for (int j = 0; j < XL; ++j) load_x(j);
     ld_advance();
     __syncthreads();
-    ECG_STAMPB_AT(1);
+    ECG_STAMP_AT(g_stamps_b, 1);
 
     for (int q = 0; q < total; ++q) {        // one flat chunk: 15 tap steps
         const unsigned char *ws = lds + (q & 1) * IMGB, *xs = ws + WPADB;
@@ -392,11 +372,10 @@ __global__ __launch_bounds__(64 * WCO * WT) __attribute__((amdgpu_waves_per_eu(2
         // are the NEWEST 4*XL vector-memory operations of this wave (vmcnt counts in issue order), so wait for everything
         // older and let them fly; they are consumed by the commits of the next chunk.
         asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(4 * XL) : "memory");
-        if (q == 0) ECG_STAMPB_AT(2);
+        if (q == 0) ECG_STAMP_AT(g_stamps_b, 2);
         if (++cc == nchunks) {                     // tile complete: store it and go straight on
             cc = 0;
-            ytile = YH ? reinterpret_cast<float *>(reinterpret_cast<u16 *>(y) + ((size_t)cn * Cout + co0) * ldyo + ctt * T_T)
-                       : y + ((size_t)cn * Cout + co0) * ldyo + ctt * T_T;
+            ytile = y + ((size_t)cn * Cout + co0) * ldyo + ctt * T_T;
             pt0 = ctt * T_T;
             // only the x loads of the chunk after next are in flight here; the epilogue does not touch their registers
 #pragma unroll
@@ -410,7 +389,7 @@ __global__ __launch_bounds__(64 * WCO * WT) __attribute__((amdgpu_waves_per_eu(2
             if (++ctt == tiles_t) { ctt = 0; ++cn; }
         }
     }
-    ECG_STAMPB_AT(3);
+    ECG_STAMP_AT(g_stamps_b, 3);
     if (STATS) {
         float *red = reinterpret_cast<float *>(lds);      // all images are dead (last chunk's barrier)
         __syncthreads();
@@ -419,7 +398,7 @@ __global__ __launch_bounds__(64 * WCO * WT) __attribute__((amdgpu_waves_per_eu(2
             const float s = st_s[i] + __shfl_xor(st_s[i], 16, 64);
             const float q = st_q[i] + __shfl_xor(st_q[i], 16, 64);
             if (l31 < 16) {
-                const int lc2 = 32 * i + acc_row_b(l31, half);
+                const int lc2 = 32 * i + acc_row(l31, half);
                 red[(wave * (CO_T / WCO) + lc2) * 2] = s;
                 red[(wave * (CO_T / WCO) + lc2) * 2 + 1] = q;
             }
@@ -437,7 +416,7 @@ __global__ __launch_bounds__(64 * WCO * WT) __attribute__((amdgpu_waves_per_eu(2
 #ifdef ECG_STAMP
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
-    ECG_STAMPB_AT(4);
+    ECG_STAMP_AT(g_stamps_b, 4);
 }
 
 bool bf16_fwd_supported(int Cin, int Cout, int K, int pad) {
@@ -473,24 +452,23 @@ size_t bf16_packed_elems(int Cred, int Cout, int K) {       // reduction channel
 }
 
 template <int CO_T, int T_T, int WCO, int WT>
-static void launch_bf16(const void *x, int ldx, bool xh, const u16 *wb, const float *bias, float *y, int ldyo, bool yh,
+static void launch_bf16(const void *x, int ldx, bool xh, const u16 *wb, const float *bias, u16 *y, int ldyo,
                         float *partials, int N, int Cin, int Cout, int L, int Lo, int pad, int G, hipStream_t st) {
     const int tiles_t = cdiv(Lo, T_T);
     dim3 grid((unsigned)((size_t)(Cout / CO_T) * G)), block(64 * WCO * WT);
     const float *xf = static_cast<const float *>(x);
-#define ECG_BF(STATS, XH, WRES, YH)                                                                                    \
-    hipLaunchKernelGGL((conv1d_mfma_bf16_fwd_kernel<CO_T, T_T, WCO, WT, STATS, XH, WRES, YH>), grid, block, 0, st, xf, \
-                       wb, bias, y, partials, Cin, Cout, L, Lo, pad, tiles_t, N, G, ldx, ldyo)
+#define ECG_BF(STATS, XH, WRES)                                                                                     \
+    hipLaunchKernelGGL((conv1d_mfma_bf16_fwd_kernel<CO_T, T_T, WCO, WT, STATS, XH, WRES>), grid, block, 0, st, xf, wb, \
+                       bias, y, partials, Cin, Cout, L, Lo, pad, tiles_t, N, G, ldx, ldyo)
     // y / dx always leave as bf16 rows (round 5: the mixed-precision step has ONE form); x is the previous block's bf16
     // activation / this block's bf16 dY (xh), or the fp32 network input of the first block
-    (void)yh;
     if (xh) { // bf16 in, bf16 out: the train-mode forward of an inner block (statistics), or its input gradient (none)
-        if (!partials) ECG_BF(false, true, false, true);
-        else if (Cin <= 2 * kCB) ECG_BF(true, true, true, true);
-        else ECG_BF(true, true, false, true);
+        if (!partials) ECG_BF(false, true, false);
+        else if (Cin <= 2 * kCB) ECG_BF(true, true, true);
+        else ECG_BF(true, true, false);
     } else { // fp32 network input (train-mode forward: always with statistics)
-        if (Cin <= 2 * kCB) ECG_BF(true, false, true, true);
-        else ECG_BF(true, false, false, true);
+        if (Cin <= 2 * kCB) ECG_BF(true, false, true);
+        else ECG_BF(true, false, false);
     }
 #undef ECG_BF
 }
@@ -502,27 +480,26 @@ int bf16_ring_launch(const RingPlan &p, const void *x, int ldx, const void *wb, 
                      float *partials, int P_stride, int N, int Cin, int Cout, int L, int Lo, int pad, hipStream_t st);
 
 // x: fp32 [N][Cin][L] (xh false, ldx ignored) or bf16 [N][Cin][ldx] with rows zero-filled past L (xh true);
-// y: fp32 [N][Cout][ldyo] or (yh, with statistics) bf16 [N][Cout][ldyo]
-static int bf16_fwd_any(const void *x, int ldx, bool xh, const void *wb, const float *bias, float *y, int ldyo, bool yh,
+// y: bf16 [N][Cout][ldyo]
+static int bf16_fwd_any(const void *x, int ldx, bool xh, const void *wb, const float *bias, u16 *y, int ldyo,
                         float *partials, int N, int Cin, int Cout, int L, int K, int pad, hipStream_t st) {
     const int Lo = L + 2 * pad - K + 1;
     const u16 *w = static_cast<const u16 *>(wb);
-    if (yh) {
-        const RingPlan rp = bf16_ring_plan(N, Cin, Cout, Lo, K, pad, ldx, ldyo, !xh);
-        // The kernel is chosen by SHAPE only, so that ecg_conv1d_fwd_bf16_yh_stat_partials (which sees no pointers) always
-        // agrees with the launch about the number of partials; operands the chosen kernel cannot address are refused.
-        // (fp32 input: the rows are [L] floats read as aligned pairs; torch allocations and whole-sample slices satisfy both)
-        if (rp.ok)
-            ECG_REQUIRE(((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(wb)) & 15) == 0 &&
-                            (reinterpret_cast<uintptr_t>(x) & (xh ? 3 : 7)) == 0,
-                        "conv1d bf16 (long rows): y / packed weights must be 16-byte aligned, x %d-byte aligned", xh ? 4 : 8);
-        if (rp.ok) return bf16_ring_launch(rp, x, ldx, wb, bias, y, ldyo, partials, rp.G, N, Cin, Cout, L, Lo, pad, st);
+    const RingPlan rp = bf16_ring_plan(N, Cin, Cout, Lo, K, pad, ldx, ldyo, !xh);
+    // The kernel is chosen by SHAPE only, so that ecg_conv1d_fwd_bf16_yh_stat_partials (which sees no pointers) always
+    // agrees with the launch about the number of partials; operands the chosen kernel cannot address are refused.
+    // (fp32 input: the rows are [L] floats read as aligned pairs; torch allocations and whole-sample slices satisfy both)
+    if (rp.ok) {
+        ECG_REQUIRE(((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(wb)) & 15) == 0 &&
+                        (reinterpret_cast<uintptr_t>(x) & (xh ? 3 : 7)) == 0,
+                    "conv1d bf16 (long rows): y / packed weights must be 16-byte aligned, x %d-byte aligned", xh ? 4 : 8);
+        return bf16_ring_launch(rp, x, ldx, wb, bias, y, ldyo, partials, rp.G, N, Cin, Cout, L, Lo, pad, st);
     }
     const Bf16Cfg c = bf16_cfg(N, Cout, Lo);
-    if (c.co_t == 128) launch_bf16<128, 256, 2, 4>(x, ldx, xh, w, bias, y, ldyo, yh, partials, N, Cin, Cout, L, Lo, pad, c.G, st);
-    else if (c.co_t == 64 && c.t_t == 256) launch_bf16<64, 256, 1, 4>(x, ldx, xh, w, bias, y, ldyo, yh, partials, N, Cin, Cout, L, Lo, pad, c.G, st);
-    else if (c.co_t == 64) launch_bf16<64, 128, 2, 2>(x, ldx, xh, w, bias, y, ldyo, yh, partials, N, Cin, Cout, L, Lo, pad, c.G, st);
-    else launch_bf16<32, 256, 1, 4>(x, ldx, xh, w, bias, y, ldyo, yh, partials, N, Cin, Cout, L, Lo, pad, c.G, st);
+    if (c.co_t == 128) launch_bf16<128, 256, 2, 4>(x, ldx, xh, w, bias, y, ldyo, partials, N, Cin, Cout, L, Lo, pad, c.G, st);
+    else if (c.co_t == 64 && c.t_t == 256) launch_bf16<64, 256, 1, 4>(x, ldx, xh, w, bias, y, ldyo, partials, N, Cin, Cout, L, Lo, pad, c.G, st);
+    else if (c.co_t == 64) launch_bf16<64, 128, 2, 2>(x, ldx, xh, w, bias, y, ldyo, partials, N, Cin, Cout, L, Lo, pad, c.G, st);
+    else launch_bf16<32, 256, 1, 4>(x, ldx, xh, w, bias, y, ldyo, partials, N, Cin, Cout, L, Lo, pad, c.G, st);
     return check_launch("conv1d_mfma_bf16_fwd_kernel");
 }
 
@@ -603,7 +580,7 @@ ECG_API int ecg_conv1d_fwd_bf16_yh(const void *x, int x_bf16, int ldx, const voi
                 "conv1d_fwd_bf16_yh: needs an even row stride >= Lo and a 4-byte aligned y");
     ECG_REQUIRE(!x_bf16 || (ldx >= L && ldx % 2 == 0 && (pad & 1) == 1 && (reinterpret_cast<uintptr_t>(x) & 3) == 0),
                 "conv1d_fwd_bf16_yh: a bf16 x needs an even row stride >= L, odd pad and a 4-byte aligned base");
-    return bf16_fwd_any(x, x_bf16 ? ldx : L, x_bf16 != 0, wb_fwd, bias, static_cast<float *>(y_bf16), ldy, true,
+    return bf16_fwd_any(x, x_bf16 ? ldx : L, x_bf16 != 0, wb_fwd, bias, static_cast<u16 *>(y_bf16), ldy,
                         stat_partials, N, C_in, C_out, L, K, pad, as_stream(stream));
 }
 
@@ -621,7 +598,7 @@ ECG_API int ecg_conv1d_bwd_data_bf16hh(const void *dy_bf16, int ldy, const void 
                 "conv1d_bwd_data_bf16hh: needs an even row stride >= Lo, odd K-1-pad and a 4-byte aligned dY");
     ECG_REQUIRE(ldx >= L && ldx % 2 == 0 && (reinterpret_cast<uintptr_t>(dx_bf16) & 3) == 0,
                 "conv1d_bwd_data_bf16hh: needs an even dx row stride >= L and a 4-byte aligned dx");
-    return bf16_fwd_any(dy_bf16, ldy, true, wb_bwd, nullptr, static_cast<float *>(dx_bf16), ldx, true, nullptr, N, C_out,
+    return bf16_fwd_any(dy_bf16, ldy, true, wb_bwd, nullptr, static_cast<u16 *>(dx_bf16), ldx, nullptr, N, C_out,
                         C_in, Lo, K, padb, as_stream(stream));
 }
 

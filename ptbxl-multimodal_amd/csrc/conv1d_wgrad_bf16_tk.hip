@@ -18,7 +18,7 @@
 // A stage is (sample n, 128 time steps) = 8 MFMA k-steps; workgroup tile M_T (co) x 512 columns (32 input channels: two per
 // 32-lane column block, 15 taps each), eight waves,
 // one workgroup per CU, two dY images and two x images in LDS:
-//   dY tile [M_T][128] bf16 (32 KB at M_T = 128) streams global -> LDS by DMA (asm, see conv1d_bf16_ring.hip), rows of 16
+//   dY tile [M_T][128] bf16 (32 KB at M_T = 128) streams global -> LDS by DMA (glds16, mfma_util.h), rows of 16
 //     16-byte slots with slot s of row co stored at s ^ (co & 15) (conflict-free A reads) — needs dY rows zero-filled to a
 //     multiple of 128 (ecg_conv1d_bf16_tk_dy_stride), which is what makes a ragged last tile harmless;
 //   x tile [NCI][152] bf16 is register-staged one stage ahead (zero padding by mask, the four copies written with four
@@ -28,15 +28,11 @@
 // gradient on the dY fragments.
 // Exact on bf16-rounded operands up to fp32 accumulation order (tests/test_gpu_ops.py::test_bf16_tk_*).
 // Replaces autograd's conv weight-gradient (reference src/models/ecg_cnn.py:13 via loss.backward()).
-#include "common.h"
+#include "mfma_util.h"
 
 namespace ecg {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4t __attribute__((ext_vector_type(4)));
 
 namespace tk {
 
@@ -48,8 +44,6 @@ constexpr int XRS = 320;         // x row stride in bytes: 80 dwords = 16 banks 
 constexpr int XCOPY_PAD[4] = {0, 32, 128, 160};   // the four shifted copies start 0 / 8 / 32 / 40 banks into a bank row: the
                                                   // (channel, copy) windows of 8 banks that the 32 lanes of a half-wave
                                                   // read then overlap only between channel c and c + 2
-
-__device__ __forceinline__ int acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 __device__ __forceinline__ unsigned pack2(float lo, float hi) {
     const u16 a = __builtin_bit_cast(u16, (__bf16)lo), b = __builtin_bit_cast(u16, (__bf16)hi);
@@ -93,12 +87,8 @@ __global__ __launch_bounds__(512) void conv1d_wgrad_bf16_tk_kernel(
     const int half = lane >> 5, l31 = lane & 31;
     const int R = Cin * KK;
     const int RT = (Cin + CPT - 1) / CPT, CT = Cout / M_T;
-    int tile;
-    {       // XCD-aware order (conv1d_mfma.hip): the R tiles of one (C_out tile, split) share a dY slice
-        const int nwg = gridDim.x, bid = blockIdx.x;
-        const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    // XCD-aware order: the R tiles of one (C_out tile, split) share a dY slice
+    const int tile = xcd_chunked(blockIdx.x, gridDim.x);
     const int tile_r = tile % RT, tile_cs = tile / RT;
     const int co0 = (tile_cs % CT) * M_T, s = tile_cs / CT;
     const int wk = wave % WK, wr = (wave / WK) % WR, wm = wave / (WK * WR);
@@ -145,10 +135,7 @@ __global__ __launch_bounds__(512) void conv1d_wgrad_bf16_tk_kernel(
     }
     const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char *)lds;
     auto glds = [&](const u16 *base, unsigned voff, unsigned dst_off) __attribute__((always_inline)) {
-        const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_base + dst_off));
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
+        glds16(base, voff, (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_base + dst_off)));
     };
 
     // ---- x staging geometry ------------------------------------------------------------------------------
@@ -187,9 +174,9 @@ __global__ __launch_bounds__(512) void conv1d_wgrad_bf16_tk_kernel(
             const float *xr = static_cast<const float *>(xin) + (size_t)xn * Cin * ldx + xrow[j];
             // (host: L % 8 == 0, so a chunk is inside the row or outside it as a whole; the clamp only keeps the load in bounds)
             const int gc = min(max(g0, 0), L - 8);
-            const f32x4t a = *reinterpret_cast<const f32x4t *>(xr + gc), b = *reinterpret_cast<const f32x4t *>(xr + gc + 4);
+            const f32x4 a = *reinterpret_cast<const f32x4 *>(xr + gc), b = *reinterpret_cast<const f32x4 *>(xr + gc + 4);
             const int gn = min(max(g0 + 8, 0), L - 4);
-            const f32x4t nx = *reinterpret_cast<const f32x4t *>(xr + gn);
+            const f32x4 nx = *reinterpret_cast<const f32x4 *>(xr + gn);
             const bool ok = g0 >= 0 && g0 < L;
             float v[8];
 #pragma unroll

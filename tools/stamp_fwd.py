@@ -5,7 +5,8 @@ start / end of prologue / end of first chunk / end of main loop / end of epilogu
 in microseconds (s_memtime ticks at the shader clock; s_memrealtime, 100 MHz, anchors it).  --bf16 stamps the
 mixed-precision forward kernel, --long uses 12x5000 windows, --wgrad stamps the fp32 weight-gradient kernel (start / end of
 prologue / end of first stage / end of the stage loop / slab written; stages per workgroup in slot 5).
-The fast-FIR kernels (round 5) carry the same stamps; EXTRA='-DECG_FWD_FFA=0 -DECG_WG_FFA=0' on the make line stamps the direct form.
+The fast-FIR kernels (round 5) carry the same stamps; the direct form they replaced is stamped from a checkout of the last
+revision that has it (profiles/EXPERIMENTS.md I7).
 """
 import ctypes
 import json
