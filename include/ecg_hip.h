@@ -121,6 +121,14 @@ int ecg_conv1d_bwd_data_ld(const float *dy, int ldy, const float *w_bwd, float *
 int ecg_conv1d_bwd_weight_bias_ld(const float *dy, int ldy, const float *x, float *dw, float *db,
                                   float *ws, int N, int C_in, int C_out, int L, int K, int pad,
                                   ecg_stream_t stream);
+/* ecg_conv1d_bwd_weight_bias_ld followed by ecg_conv1d_bwd_data_ld on the same dY, as one call: where the input gradient
+ * runs on the fast-FIR matrix-core kernel, the fixed-order slab reduce of the weight gradient is carried by extra workgroups
+ * of the input-gradient launch instead of a launch of its own in front of it (a memory-bound pass beside a matrix-bound
+ * kernel); elsewhere the sequence of the two calls.  dw, db (nullable) and dx are bit-identical to the two calls';
+ * ws as for ecg_conv1d_bwd_weight_bias (ecg_conv1d_bwd_weight_ws_floats). */
+int ecg_conv1d_bwd_weight_data_ld(const float *dy, int ldy, const float *x, const float *w_bwd,
+                                  float *dw, float *db, float *dx, float *ws, int N, int C_in,
+                                  int C_out, int L, int K, int pad, ecg_stream_t stream);
 
 /* Workspace (floats) for ecg_conv1d_bwd_weight_bias. */
 size_t ecg_conv1d_bwd_weight_ws_floats(int N, int C_in, int C_out, int L, int K, int pad);

@@ -1,6 +1,7 @@
 // conv1d_api.hip — C-ABI entry points for Conv1d and the shape dispatch between the
 // MFMA implicit-GEMM kernels (conv1d_mfma.hip) and the direct VALU kernels (conv1d_direct.hip).
 #include "common.h"
+#include "wgrad_reduce.h"
 
 namespace ecg {
 // conv1d_direct.hip
@@ -10,6 +11,8 @@ int direct_fwd(const float *x, const float *wp, const float *bias, float *y, flo
 size_t direct_wgrad_ws_floats(int N, int Cin, int Cout, int K);
 int direct_wgrad(const float *dy, const float *x, float *dw, float *db, float *ws, int N, int Cin,
                  int Cout, int L, int K, int pad, hipStream_t st);
+int direct_wgrad_slabs(const float *dy, const float *x, float *dw, float *db, float *ws, int N, int Cin,
+                       int Cout, int L, int K, int pad, hipStream_t st, WgradReduce *red);
 int pack_weights(const float *w, float *w_fwd, float *w_bwd, int Co, int Ci, int K,
                  hipStream_t st);
 int pack_weights_grouped(const float *const *w, float *const *w_fwd, float *const *w_bwd, void *const *wb_fwd,
@@ -29,6 +32,11 @@ bool mfma_wgrad_dma_supported(int Cin, int Cout, int K);
 int mfma_multiplies_per_pair(int op, int Cin, int Cout, int K, int pad);
 int mfma_wgrad(const float *dy, int ldy, const float *x, float *dw, float *db, float *ws, int N,
                int Cin, int Cout, int L, int K, int pad, hipStream_t st);
+int mfma_wgrad_slabs(const float *dy, int ldy, const float *x, float *dw, float *db, float *ws, int N,
+                     int Cin, int Cout, int L, int K, int pad, hipStream_t st, WgradReduce *red);
+int mfma_wgrad_reduce(const WgradReduce &red, hipStream_t st);
+int mfma_fwd_rider(const float *x, int ldx, const float *wp, float *y, int N, int Cin, int Cout, int L, int K, int pad,
+                   WgradReduce red, hipStream_t st);
 
 static int check_conv_shape(int N, int Cin, int Cout, int L, int K, int pad) {
     ECG_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && L > 0, "conv1d: N=%d C_in=%d C_out=%d L=%d must be > 0",
@@ -160,6 +168,31 @@ ECG_API int ecg_conv1d_bwd_weight_bias(const float *dy, const float *x, float *d
                                        ecg_stream_t stream) {
     return ecg_conv1d_bwd_weight_bias_ld(dy, L + 2 * pad - K + 1, x, dw, db, ws, N, C_in, C_out, L, K,
                                          pad, stream);
+}
+
+// Weight, bias and input gradient of one layer: the slab kernel, then the input gradient with the slab reduce riding on its
+// launch (conv1d_mfma.hip: RIDER).  Where the input gradient takes the direct kernel there is nothing to ride on: standalone
+// reduce, then the direct input gradient — the sequence of the two entry points above.  Same results bit for bit either way.
+ECG_API int ecg_conv1d_bwd_weight_data_ld(const float *dy, int ldy, const float *x, const float *w_bwd,
+                                          float *dw, float *db, float *dx, float *ws, int N, int C_in,
+                                          int C_out, int L, int K, int pad, ecg_stream_t stream) {
+    int rc = check_conv_shape(N, C_in, C_out, L, K, pad);
+    if (rc) return rc;
+    ECG_REQUIRE(dy && x && w_bwd && dw && dx && ws, "conv1d_bwd_weight_data: null pointer");
+    const int Lo = L + 2 * pad - K + 1, padb = K - 1 - pad;
+    ECG_REQUIRE(ldy >= Lo, "conv1d_bwd_weight_data: dY row stride %d < row length %d", ldy, Lo);
+    const bool wg_mfma = mfma_wgrad_supported(C_in, C_out, K, pad), dg_mfma = mfma_fwd_supported(C_out, C_in, K, padb);
+    ECG_REQUIRE((wg_mfma && dg_mfma) || ldy == Lo, "conv1d_bwd_weight_data: this shape needs dense dY rows (stride %d != %d); "
+                "use the stride ecg_conv1d_dy_row_stride returns", ldy, Lo);
+    hipStream_t st = as_stream(stream);
+    WgradReduce red;
+    rc = wg_mfma ? mfma_wgrad_slabs(dy, ldy, x, dw, db, ws, N, C_in, C_out, L, K, pad, st, &red)
+                 : direct_wgrad_slabs(dy, x, dw, db, ws, N, C_in, C_out, L, K, pad, st, &red);
+    if (rc) return rc;
+    if (dg_mfma) return mfma_fwd_rider(dy, ldy, w_bwd, dx, N, C_out, C_in, Lo, K, padb, red, st);
+    rc = mfma_wgrad_reduce(red, st);
+    if (rc) return rc;
+    return direct_fwd(dy, w_bwd, nullptr, dx, nullptr, N, C_out, C_in, Lo, K, padb, st);
 }
 
 ECG_API int ecg_conv1d_bn_relu_pool_eval_supported(int C_in, int C_out, int K, int pad) {

@@ -12,6 +12,7 @@
 // workgroup needs are contiguous and wave-uniform, so they arrive through the scalar cache
 // (s_load_dwordx8/x16) and feed v_fma_f32 as SGPR operands — one LDS read of x feeds CO_T FMAs.
 #include "common.h"
+#include "wgrad_reduce.h"
 #include <cstdlib>
 
 namespace ecg {
@@ -262,20 +263,9 @@ __global__ __launch_bounds__(64 * G) void wgrad_reduce_kernel(const float *__res
     __shared__ double part[G][64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const size_t i = (size_t)blockIdx.x * 64 + lane;
-    const size_t total = wslab + Cout;
-    const bool live = i < total && (i < wslab || db);
+    const bool live = wgrad_reduce_live(i, wslab, Cout, db);
     double a = 0.0;
-    if (live) {
-        const float *src = i < wslab ? slab + i : slab + (size_t)S * wslab + (i - wslab);
-        const size_t stride = i < wslab ? wslab : (size_t)Cout;
-        int s = w;
-        for (; s + 3 * G < S; s += 4 * G) {
-            const float v0 = src[(size_t)s * stride], v1 = src[(size_t)(s + G) * stride];
-            const float v2 = src[(size_t)(s + 2 * G) * stride], v3 = src[(size_t)(s + 3 * G) * stride];
-            a += (double)v0; a += (double)v1; a += (double)v2; a += (double)v3;
-        }
-        for (; s < S; s += G) a += (double)src[(size_t)s * stride];
-    }
+    if (live) a = wgrad_reduce_part(slab, wslab, Cout, S, i, w, G);
     if (G > 1) {
         part[w][lane] = a;
         __syncthreads();
@@ -283,9 +273,7 @@ __global__ __launch_bounds__(64 * G) void wgrad_reduce_kernel(const float *__res
 #pragma unroll
         for (int g = 1; g < G; ++g) a += part[g][lane];
     }
-    if (live) {
-        if (i < wslab) dw[i] = (float)a; else db[i - wslab] = (float)a;
-    }
+    if (live) wgrad_reduce_store(dw, db, wslab, i, a);
 }
 
 // The same sums, four consecutive outputs per lane (16-byte loads: a quarter of the load instructions, four times the
@@ -297,39 +285,9 @@ __global__ __launch_bounds__(64 * G) void wgrad_reduce4_kernel(const float *__re
     __shared__ double part[G][64][4];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const size_t i = ((size_t)blockIdx.x * 64 + lane) * 4;
-    const size_t total = wslab + Cout;
-    const bool live = i < total && (i < wslab || db);
+    const bool live = wgrad_reduce_live(i, wslab, Cout, db);
     double a[4] = {0.0, 0.0, 0.0, 0.0};
-    if (live) {
-        const float *src = i < wslab ? slab + i : slab + (size_t)S * wslab + (i - wslab);
-        const size_t stride = i < wslab ? wslab : (size_t)Cout;
-        int s = w;
-        // eight slabs in flight per lane (8 KB per wave; with four a CU held ~30 KB in flight — short of what HBM latency
-        // needs — and the pass ran at 3.4-4.6 TB/s); the additions stay in slab order: bit-identical sums
-        for (; s + 7 * G < S; s += 8 * G) {
-            float4 v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4 *>(src + (size_t)(s + u * G) * stride);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                a[0] += (double)v[u].x; a[1] += (double)v[u].y; a[2] += (double)v[u].z; a[3] += (double)v[u].w;
-            }
-        }
-        for (; s + 3 * G < S; s += 4 * G) {
-            const float4 v0 = *reinterpret_cast<const float4 *>(src + (size_t)s * stride);
-            const float4 v1 = *reinterpret_cast<const float4 *>(src + (size_t)(s + G) * stride);
-            const float4 v2 = *reinterpret_cast<const float4 *>(src + (size_t)(s + 2 * G) * stride);
-            const float4 v3 = *reinterpret_cast<const float4 *>(src + (size_t)(s + 3 * G) * stride);
-            a[0] += (double)v0.x; a[0] += (double)v1.x; a[0] += (double)v2.x; a[0] += (double)v3.x;
-            a[1] += (double)v0.y; a[1] += (double)v1.y; a[1] += (double)v2.y; a[1] += (double)v3.y;
-            a[2] += (double)v0.z; a[2] += (double)v1.z; a[2] += (double)v2.z; a[2] += (double)v3.z;
-            a[3] += (double)v0.w; a[3] += (double)v1.w; a[3] += (double)v2.w; a[3] += (double)v3.w;
-        }
-        for (; s < S; s += G) {
-            const float4 v = *reinterpret_cast<const float4 *>(src + (size_t)s * stride);
-            a[0] += (double)v.x; a[1] += (double)v.y; a[2] += (double)v.z; a[3] += (double)v.w;
-        }
-    }
+    if (live) wgrad_reduce4_part(slab, wslab, Cout, S, i, w, G, a);
     if (G > 1) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) part[w][lane][e] = a[e];
@@ -340,29 +298,38 @@ __global__ __launch_bounds__(64 * G) void wgrad_reduce4_kernel(const float *__re
 #pragma unroll
             for (int e = 0; e < 4; ++e) a[e] += part[g][lane][e];
     }
-    if (live) {
-        const float4 o = make_float4((float)a[0], (float)a[1], (float)a[2], (float)a[3]);
-        if (i < wslab) *reinterpret_cast<float4 *>(dw + i) = o; else *reinterpret_cast<float4 *>(db + (i - wslab)) = o;
-    }
+    if (live) wgrad_reduce4_store(dw, db, wslab, i, a);
 }
 
-int wgrad_reduce(const float *ws, float *dw, float *db, size_t wslab, int Cout, int S,
-                 hipStream_t st) {
+// Which form sums S slabs of wslab floats (+ the bias rows): shared by the standalone launch below and by the launch that
+// carries the reduce as rider workgroups of the input gradient (conv1d_mfma.hip), so both take the same form for the same call.
+WgradReduce wgrad_reduce_describe(const float *ws, float *dw, float *db, size_t wslab, int Cin, int Cout, int S) {
+    WgradReduce r{ws, dw, db, wslab, Cin, Cout, S, WGR_GROUPED, 1, 0};
     const size_t total = wslab + Cout;
     // the float4 form pays where a workgroup is ONE wave walking few, large slabs (blocks 2-3 of the model: block 3
     // 262 -> 259 us per weight-gradient call); with G > 1 (many small slabs) its LDS combine is four times larger and it
     // measured 2-3 us slower on block 0
     if (wslab % 4 == 0 && Cout % 4 == 0 && (size_t)cdiv(total, 64) >= 1024 &&
         ((reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(dw) | reinterpret_cast<uintptr_t>(db)) & 15) == 0) {
-        hipLaunchKernelGGL((wgrad_reduce4_kernel<1>), dim3(cdiv(total / 4, 64)), dim3(64), 0, st, ws, dw, db, wslab, Cout, S);
+        r.form = WGR_FLOAT4;
+        return r;
+    }
+    // enough waves to fill the chip (~1024) without going below 8 slabs per wave
+    const size_t groups = cdiv(total, 64);
+    int G = 1;
+    while (G < 16 && groups * G < 1024 && S / (2 * G) >= 8) G *= 2;
+    r.G = G;
+    return r;
+}
+
+int wgrad_reduce_launch(const WgradReduce &r, hipStream_t st) {
+    const dim3 grid((unsigned)wgrad_reduce_groups(r));
+    if (r.form == WGR_FLOAT4) {
+        hipLaunchKernelGGL((wgrad_reduce4_kernel<1>), grid, dim3(64), 0, st, r.slab, r.dw, r.db, r.stride, r.Cout, r.S);
         return check_launch("wgrad_reduce4_kernel");
     }
-    const dim3 grid(cdiv(total, 64));
-    // enough waves to fill the chip (~1024) without going below 8 slabs per wave
-    int G = 1;
-    while (G < 16 && (size_t)grid.x * G < 1024 && S / (2 * G) >= 8) G *= 2;
-#define ECG_RED(GG) hipLaunchKernelGGL((wgrad_reduce_kernel<GG>), grid, dim3(64 * GG), 0, st, ws, dw, db, wslab, Cout, S)
-    switch (G) {
+#define ECG_RED(GG) hipLaunchKernelGGL((wgrad_reduce_kernel<GG>), grid, dim3(64 * GG), 0, st, r.slab, r.dw, r.db, r.stride, r.Cout, r.S)
+    switch (r.G) {
         case 1: ECG_RED(1); break;
         case 2: ECG_RED(2); break;
         case 4: ECG_RED(4); break;
@@ -371,6 +338,11 @@ int wgrad_reduce(const float *ws, float *dw, float *db, size_t wslab, int Cout, 
     }
 #undef ECG_RED
     return check_launch("wgrad_reduce_kernel");
+}
+
+int wgrad_reduce(const float *ws, float *dw, float *db, size_t wslab, int Cout, int S,
+                 hipStream_t st) {
+    return wgrad_reduce_launch(wgrad_reduce_describe(ws, dw, db, wslab, 0, Cout, S), st);
 }
 
 static bool wgrad_fast_ok(int Cout, int K) { return K == 15 && Cout % 8 == 0; }
@@ -389,8 +361,10 @@ size_t direct_wgrad_ws_floats(int N, int Cin, int Cout, int K) {
     return (size_t)S * ((size_t)Cout * Cin * K + Cout);
 }
 
-int direct_wgrad(const float *dy, const float *x, float *dw, float *db, float *ws, int N, int Cin,
-                 int Cout, int L, int K, int pad, hipStream_t st) {
+// launches the slab kernel and describes the reduce that has to follow it (standalone: wgrad_reduce_launch; or as rider
+// workgroups of the input-gradient launch)
+int direct_wgrad_slabs(const float *dy, const float *x, float *dw, float *db, float *ws, int N, int Cin,
+                       int Cout, int L, int K, int pad, hipStream_t st, WgradReduce *red) {
     const int Lo = L + 2 * pad - K + 1;
     const int S = direct_wgrad_splits(N, Cin, Cout, K);
     const size_t wslab = (size_t)Cout * Cin * K;
@@ -403,9 +377,16 @@ int direct_wgrad(const float *dy, const float *x, float *dw, float *db, float *w
         hipLaunchKernelGGL(conv1d_wgrad_generic_kernel, grid, block, 0, st, dy, x, ws, N, Cin,
                            Cout, L, Lo, K, pad);
     }
-    int rc = check_launch("conv1d_wgrad kernel");
+    *red = wgrad_reduce_describe(ws, dw, db, wslab, Cin, Cout, S);
+    return check_launch("conv1d_wgrad kernel");
+}
+
+int direct_wgrad(const float *dy, const float *x, float *dw, float *db, float *ws, int N, int Cin,
+                 int Cout, int L, int K, int pad, hipStream_t st) {
+    WgradReduce red;
+    int rc = direct_wgrad_slabs(dy, x, dw, db, ws, N, Cin, Cout, L, K, pad, st, &red);
     if (rc) return rc;
-    return wgrad_reduce(ws, dw, db, wslab, Cout, S, st);
+    return wgrad_reduce_launch(red, st);
 }
 
 int pack_weights(const float *w, float *w_fwd, float *w_bwd, int Co, int Ci, int K, hipStream_t st);

@@ -19,7 +19,9 @@
 // Replaces the ATen work behind ConvBlock.net[0] (reference src/models/ecg_cnn.py:13) and its
 // backward (src/training/loop.py:33).
 #include "mfma_util.h"
+#include "wgrad_reduce.h"
 #include <cstdlib>
+#include <tuple>
 #include <type_traits>
 
 namespace ecg {
@@ -124,11 +126,29 @@ struct EvalEpi { const float *gamma, *beta, *mean, *var; float eps; int gap; };
 #ifndef ECG_FFA_FLP2
 #define ECG_FFA_FLP2 64      // one second-level add per TWO chunks where C_in % 8 == 0 and C_in >= this (0: per chunk everywhere)
 #endif
-template <int CO_T, int M_T, int WCO, int WT, int EPI, int CI_C = 4, int FLP = 1>
+//
+// RIDER (input gradient only, EPI_PLAIN): the launch also carries the slab reduce of the same block's weight gradient.  That
+// reduce is a memory-bound pass (block 3: 38.6 MB of slabs, 9.4 us on its own) which otherwise runs, with the matrix pipe idle,
+// between the weight-gradient kernel and this one, and this kernel needs nothing it produces.  The grid is the conv's own
+// workgroups followed by rd.riders more; a workgroup behind the conv's count runs wgrad_reduce_rider for its slice (same
+// loads, same double sums in slab order as the standalone kernels: bit-identical dw / db) and returns.  The branch is
+// uniform per workgroup; riders use the static LDS image for the wave combine of the grouped form and nothing beyond it.
+// Riders go LAST in the grid: workgroups are dispatched in index order, so the conv workgroups — the critical path — get
+// their slots first and keep their index, tile mapping and XCD chunks (xcd_chunked sees the conv's count, not gridDim.x);
+// the riders fall into whatever slots the conv workgroups leave free, or into the ones freed first.  (At 142-161 registers
+// and 25-35 KB of LDS a CU takes three of these workgroups; the model's input gradients are 512 conv workgroups on 256 CUs, so
+// a third slot per CU is free from the start and the launches grow by 0-1.5 us for 5-9 us of reduce: EXPERIMENTS J.)  Riders
+// placed first would hold up to a whole round of slots while every conv workgroup waits behind them.
+// The descriptor is a trailing parameter PACK — empty (RIDER false) or one WgradReduce (RIDER true) — so that the kernels
+// without a rider keep their argument block, hence every instruction (an empty struct would still move the hidden arguments).
+template <int CO_T, int M_T, int WCO, int WT, int EPI, int CI_C = 4, int FLP = 1, class... RD>
 __global__ __launch_bounds__(256, ECG_FFA_MINB) void conv1d_mfma_ffa_kernel(
     const float *__restrict__ x, const float *__restrict__ wp, const float *__restrict__ bias,
     float *__restrict__ y, float *__restrict__ partials, int Cin, int Cout, int L, int ldx, int Lo,
-    int pad, int P, int tiles_t, EvalEpi ev) {
+    int pad, int P, int tiles_t, EvalEpi ev, RD... rdp) {
+    constexpr bool RIDER = sizeof...(RD) != 0;
+    static_assert(!RIDER || (EPI == EPI_PLAIN && sizeof...(RD) == 1 && (std::is_same<RD, WgradReduce>::value && ...)),
+                  "the reduce rides on the input gradient only");
     constexpr bool STATS = (EPI == EPI_STATS), GAP = (EPI == EPI_EVAL_GAP);
     constexpr bool EVALM = (EPI == EPI_EVAL || EPI == EPI_EVAL_GAP);
     static_assert(WCO * WT == 4, "4 waves per workgroup");
@@ -151,11 +171,21 @@ __global__ __launch_bounds__(256, ECG_FFA_MINB) void conv1d_mfma_ffa_kernel(
 
     __shared__ __attribute__((aligned(1024))) float lds[2 * IMG];
 
+    int nconv = gridDim.x;
+    if constexpr (RIDER) {
+        static_assert(2 * IMG * sizeof(float) >= 16 * 64 * sizeof(double), "wave combine of the grouped reduce (G <= 16)");
+        const WgradReduce &rd = std::get<0>(std::tie(rdp...));
+        nconv -= rd.riders;
+        if ((int)blockIdx.x >= nconv) {
+            wgrad_reduce_rider(rd, (int)blockIdx.x - nconv, reinterpret_cast<double *>(lds));
+            return;
+        }
+    }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, l31 = lane & 31;
     ECG_STAMP_AT(g_stamps, 0);
     const int CT = Cout / CO_T;
-    const int tile = xcd_chunked(blockIdx.x, gridDim.x);
+    const int tile = xcd_chunked(blockIdx.x, nconv);
     const int tile_co = tile % CT, tile_nt = tile / CT;
     const int tile_t = tile_nt % tiles_t, n = tile_nt / tiles_t;
     const int t0 = tile_t * TS, co0 = tile_co * CO_T;
@@ -407,7 +437,7 @@ int mfma_fwd_stat_partials(int N, int Cin, int Cout, int Lo) {
 template <int CO_T, int T_T, int WCO, int WT>
 static void launch_fwd(const float *x, const float *wp, const float *bias, float *y,
                        float *partials, const EvalEpi *ev, int N, int Cin, int Cout, int L, int ldx,
-                       int Lo, int pad, hipStream_t st) {
+                       int Lo, int pad, hipStream_t st, const WgradReduce *rider = nullptr) {
     const int tiles_t = cdiv(Lo, T_T - 2);
     dim3 grid((unsigned)((size_t)tiles_t * (Cout / CO_T) * N)), block(256);
     const int P = N * tiles_t;
@@ -426,6 +456,16 @@ static void launch_fwd(const float *x, const float *wp, const float *bias, float
     else \
         hipLaunchKernelGGL((conv1d_mfma_ffa_kernel<CO_T, T_T / 2, WCO, WT, MODE>), grid, block, 0, st, x, wp, bias, y, \
                            partials, Cin, Cout, L, ldx, Lo, pad, P, tiles_t, EV); } while (0)
+    if (rider) {        // plain epilogue + the riding slab reduce: rider->riders workgroups behind the conv's own
+        const dim3 rgrid(grid.x + (unsigned)rider->riders);
+        if (ECG_FFA_FLP2 && Cin % 8 == 0 && Cin >= ECG_FFA_FLP2)
+            hipLaunchKernelGGL((conv1d_mfma_ffa_kernel<CO_T, T_T / 2, WCO, WT, EPI_PLAIN, 4, 2, WgradReduce>), rgrid, block, 0, st, x,
+                               wp, bias, y, partials, Cin, Cout, L, ldx, Lo, pad, P, tiles_t, none, *rider);
+        else
+            hipLaunchKernelGGL((conv1d_mfma_ffa_kernel<CO_T, T_T / 2, WCO, WT, EPI_PLAIN, 4, 1, WgradReduce>), rgrid, block, 0, st, x,
+                               wp, bias, y, partials, Cin, Cout, L, ldx, Lo, pad, P, tiles_t, none, *rider);
+        return;
+    }
     if (ev && ev->gap) ECG_FFA(EPI_EVAL_GAP, *ev);
     else if (ev) ECG_FFA(EPI_EVAL, *ev);
     else if (partials) ECG_FFA(EPI_STATS, none);
@@ -435,12 +475,12 @@ static void launch_fwd(const float *x, const float *wp, const float *bias, float
 
 static int mfma_fwd_any(const float *x, const float *wp, const float *bias, float *y,
                         float *partials, const EvalEpi *ev, int N, int Cin, int Cout, int L, int ldx,
-                        int K, int pad, hipStream_t st) {
+                        int K, int pad, hipStream_t st, const WgradReduce *rider = nullptr) {
     const int Lo = L + 2 * pad - K + 1;
     if (fwd_cfg(Cout).co_t == 64)
-        launch_fwd<64, 128, 2, 2>(x, wp, bias, y, partials, ev, N, Cin, Cout, L, ldx, Lo, pad, st);
+        launch_fwd<64, 128, 2, 2>(x, wp, bias, y, partials, ev, N, Cin, Cout, L, ldx, Lo, pad, st, rider);
     else
-        launch_fwd<32, 256, 1, 4>(x, wp, bias, y, partials, ev, N, Cin, Cout, L, ldx, Lo, pad, st);
+        launch_fwd<32, 256, 1, 4>(x, wp, bias, y, partials, ev, N, Cin, Cout, L, ldx, Lo, pad, st, rider);
     return check_launch("conv1d_mfma_ffa_kernel");
 }
 
@@ -448,6 +488,17 @@ static int mfma_fwd_any(const float *x, const float *wp, const float *bias, floa
 int mfma_fwd(const float *x, int ldx, const float *wp, const float *bias, float *y, float *partials,
              int N, int Cin, int Cout, int L, int K, int pad, hipStream_t st) {
     return mfma_fwd_any(x, wp, bias, y, partials, nullptr, N, Cin, Cout, L, ldx, K, pad, st);
+}
+
+// Input gradient (the plain forward of dY with the packed backward weights) with the slab reduce of the same block's weight
+// gradient riding on the launch.  The rider count: one 64-lane group per rider wave at most, never more than 1024 workgroups
+// (the groups are dealt over the workgroups first: wgrad_reduce_rider) — block 3: 1024 riders for 4 100 groups, block 2 and
+// block 1: 481 riders of one busy wave / one four-wave group each.
+int mfma_fwd_rider(const float *x, int ldx, const float *wp, float *y, int N, int Cin, int Cout, int L, int K, int pad,
+                   WgradReduce red, hipStream_t st) {
+    const size_t groups = wgrad_reduce_groups(red);
+    red.riders = (int)(groups < 1024 ? groups : 1024);
+    return mfma_fwd_any(x, wp, nullptr, y, nullptr, nullptr, N, Cin, Cout, L, ldx, K, pad, st, &red);
 }
 
 // eval-mode ConvBlock in one launch: p = MaxPool2(ReLU(BN_running(conv(x))))
@@ -1326,57 +1377,12 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_ffa_kernel(
 // as in wgrad_reduce_kernel.  One wave per workgroup: the layers that take this form have >= 2 048 of them.
 __global__ __launch_bounds__(64) void wgrad_ffa_reduce_kernel(const float *__restrict__ slab, float *__restrict__ dw,
                                                               float *__restrict__ db, int Cin, int Cout, int S) {
-    const int lane = threadIdx.x;
-    const size_t i = (size_t)blockIdx.x * 64 + lane;
-    const size_t npair = (size_t)Cout * Cin * 8, RVT = (size_t)Cin * 23, wslab = (size_t)Cout * RVT;
-    const bool live = i < npair + Cout && (i < npair || db);
-    double a[4] = {0.0, 0.0, 0.0, 0.0};            // U[j], G[j], V[j], G[j+1]  |  bias
-    int j = 0;
-    size_t o = 0;
-    if (live) {
-        if (i < npair) {
-            const int co = (int)(i / ((size_t)Cin * 8)), rem = (int)(i - (size_t)co * Cin * 8);
-            const int ci = rem >> 3;
-            j = rem & 7;
-            o = ((size_t)co * Cin + ci) * 15 + 2 * j;
-            const int jv = j < 7 ? j : 6;           // (tap 15 does not exist: the lane of j = 7 re-reads valid columns and drops them)
-            const float *pu = slab + (size_t)co * RVT + ci * 8 + j;
-            const float *pg = slab + (size_t)co * RVT + Cin * 15 + ci * 8 + j;
-            const float *pv = slab + (size_t)co * RVT + Cin * 8 + ci * 7 + jv;
-            const int g1 = j < 7 ? 1 : 0;
-            int s = 0;
-            for (; s + 3 < S; s += 4) {
-                float v[4][4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const size_t off = (size_t)(s + u) * wslab;
-                    v[u][0] = pu[off]; v[u][1] = pg[off]; v[u][2] = pv[off]; v[u][3] = pg[off + g1];
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) a[e] += (double)v[u][e];
-            }
-            for (; s < S; ++s) {
-                const size_t off = (size_t)s * wslab;
-                a[0] += (double)pu[off]; a[1] += (double)pg[off]; a[2] += (double)pv[off]; a[3] += (double)pg[off + g1];
-            }
-        } else {
-            const float *src = slab + (size_t)S * wslab + (i - npair);
-            for (int s = 0; s < S; ++s) a[0] += (double)src[(size_t)s * Cout];
-        }
-    }
-    if (live) {
-        if (i < npair) {
-            dw[o] = (float)(a[0] - a[1]);
-            if (j < 7) dw[o + 1] = (float)(a[2] + a[3]);
-        } else db[i - npair] = (float)a[0];
-    }
+    wgrad_ffa_reduce_lane(slab, dw, db, Cin, Cout, S, (size_t)blockIdx.x * 64 + threadIdx.x);
 }
 
-// conv1d_direct.hip: dw[i] = sum_s slab[s][i] in fixed order
-int wgrad_reduce(const float *ws, float *dw, float *db, size_t wslab, int Cout, int S,
-                 hipStream_t st);
+// conv1d_direct.hip: dw[i] = sum_s slab[s][i] in fixed order — which form sums a slab set, and its standalone launch
+WgradReduce wgrad_reduce_describe(const float *ws, float *dw, float *db, size_t wslab, int Cin, int Cout, int S);
+int wgrad_reduce_launch(const WgradReduce &r, hipStream_t st);
 
 struct WgCfg { int m_t, r_t, splits; };
 
@@ -1460,8 +1466,9 @@ bool mfma_wgrad_dma_supported(int Cin, int Cout, int K) {
     return K == kKM && Cout % 32 == 0;
 }
 
-int mfma_wgrad(const float *dy, int ldy, const float *x, float *dw, float *db, float *ws, int N,
-               int Cin, int Cout, int L, int K, int pad, hipStream_t st) {
+// launches the slab kernel and describes the reduce that has to follow it
+int mfma_wgrad_slabs(const float *dy, int ldy, const float *x, float *dw, float *db, float *ws, int N,
+                     int Cin, int Cout, int L, int K, int pad, hipStream_t st, WgradReduce *red) {
     const int Lo = L + 2 * pad - K + 1;
     const int R = Cin * K;
     const bool dma = mfma_wgrad_dma_supported(Cin, Cout, K) && ldy % 64 == 0 && ldy >= cdiv(Lo, 64) * 64 &&
@@ -1473,12 +1480,8 @@ int mfma_wgrad(const float *dy, int ldy, const float *x, float *dw, float *db, f
         dim3 fgrid((unsigned)(wgrad_ffa_tiles(Cin, Cout) * S)), fblock(256);
         hipLaunchKernelGGL((conv1d_mfma_wgrad_ffa_kernel<128, 128, 2, 2, 64>), fgrid, fblock, 0, st, dy, x, ws, N, Cin, Cout, L, Lo,
                            ldy, pad, S);
-        int frc = check_launch("conv1d_mfma_wgrad_ffa_kernel");
-        if (frc) return frc;
-        const size_t nout = (size_t)Cout * Cin * 8 + Cout;          // one lane per (co, ci, tap pair) + the bias row
-        const dim3 rgrid((unsigned)cdiv(nout, (size_t)64));
-        hipLaunchKernelGGL(wgrad_ffa_reduce_kernel, rgrid, dim3(64), 0, st, ws, dw, db, Cin, Cout, S);
-        return check_launch("wgrad_ffa_reduce_kernel");
+        *red = WgradReduce{ws, dw, db, (size_t)Cout * Cin * 23, Cin, Cout, S, WGR_FFA, 1, 0};
+        return check_launch("conv1d_mfma_wgrad_ffa_kernel");
     }
     const WgCfg c = wgrad_cfg(N, Cin, Cout, Lo, dma, tt128 ? 128 : 64);
     dim3 grid((unsigned)(cdiv(R, c.r_t) * (Cout / c.m_t) * c.splits)), block(256);
@@ -1493,9 +1496,27 @@ int mfma_wgrad(const float *dy, int ldy, const float *x, float *dw, float *db, f
     else if (c.m_t == 64) ECG_WG((conv1d_mfma_wgrad_kernel<64, 128, 2, 2, 1, 64, kKM>));
     else ECG_WG((conv1d_mfma_wgrad_kernel<32, 192, 1, 2, 2, 128, kKM>));
 #undef ECG_WG
-    int rc = check_launch("conv1d_mfma_wgrad_kernel");
+    *red = wgrad_reduce_describe(ws, dw, db, (size_t)Cout * R, Cin, Cout, c.splits);
+    return check_launch("conv1d_mfma_wgrad_kernel");
+}
+
+// the standalone reduce of a described slab set
+int mfma_wgrad_reduce(const WgradReduce &red, hipStream_t st) {
+    if (red.form == WGR_FFA) {
+        // one lane per (co, ci, tap pair) + the bias row
+        hipLaunchKernelGGL(wgrad_ffa_reduce_kernel, dim3((unsigned)wgrad_reduce_groups(red)), dim3(64), 0, st, red.slab, red.dw,
+                           red.db, red.Cin, red.Cout, red.S);
+        return check_launch("wgrad_ffa_reduce_kernel");
+    }
+    return wgrad_reduce_launch(red, st);
+}
+
+int mfma_wgrad(const float *dy, int ldy, const float *x, float *dw, float *db, float *ws, int N,
+               int Cin, int Cout, int L, int K, int pad, hipStream_t st) {
+    WgradReduce red;
+    int rc = mfma_wgrad_slabs(dy, ldy, x, dw, db, ws, N, Cin, Cout, L, K, pad, st, &red);
     if (rc) return rc;
-    return wgrad_reduce(ws, dw, db, (size_t)Cout * R, Cout, c.splits, st);
+    return mfma_wgrad_reduce(red, st);
 }
 
 }  // namespace ecg
