@@ -26,9 +26,9 @@ int mfma_fwd_eval_pool(const float *x, const float *wp, const float *bias, const
                        const float *beta, const float *mean, const float *var, float eps, float *p,
                        int N, int Cin, int Cout, int L, int K, int pad, hipStream_t st, int gap);
 bool mfma_fwd_eval_gap_supported(int Cin, int Cout, int L, int K, int pad);
-bool mfma_wgrad_supported(int Cin, int Cout, int K, int pad);
+bool mfma_wgrad_supported(int Cin, int Cout, int K);
 size_t mfma_wgrad_ws_floats(int N, int Cin, int Cout, int L, int K, int pad);
-bool mfma_wgrad_dma_supported(int Cin, int Cout, int K);
+int mfma_wgrad_dma_stride(int Lo, int tt);
 int mfma_multiplies_per_pair(int op, int Cin, int Cout, int K, int pad);
 int mfma_wgrad(const float *dy, int ldy, const float *x, float *dw, float *db, float *ws, int N,
                int Cin, int Cout, int L, int K, int pad, hipStream_t st);
@@ -45,6 +45,18 @@ static int check_conv_shape(int N, int Cin, int Cout, int L, int K, int pad) {
     ECG_REQUIRE(pad >= 0 && pad < K, "conv1d: padding %d outside [0,K)", pad);
     ECG_REQUIRE(L + 2 * pad - K + 1 > 0, "conv1d: empty output (L=%d K=%d pad=%d)", L, K, pad);
     ECG_REQUIRE(N <= 65535, "conv1d: N=%d exceeds grid.z limit 65535", N);
+    return ECG_OK;
+}
+
+// shape, pointers and dY row stride of the gradient entry points; `strided`: every kernel the call takes reads padded dY rows
+static int check_conv_grad(const char *who, bool ptrs, int ldy, bool strided, int N, int Cin, int Cout, int L, int K, int pad) {
+    int rc = check_conv_shape(N, Cin, Cout, L, K, pad);
+    if (rc) return rc;
+    const int Lo = L + 2 * pad - K + 1;
+    ECG_REQUIRE(ptrs, "%s: null pointer", who);
+    ECG_REQUIRE(ldy >= Lo, "%s: dY row stride %d < row length %d", who, ldy, Lo);
+    ECG_REQUIRE(strided || ldy == Lo, "%s: this shape needs dense dY rows (stride %d != %d); "
+                "use the stride ecg_conv1d_dy_row_stride returns", who, ldy, Lo);
     return ECG_OK;
 }
 }  // namespace ecg
@@ -112,8 +124,8 @@ ECG_API int ecg_conv1d_dy_row_stride(int N, int C_in, int C_out, int L, int K, i
     const int Lo = L + 2 * pad - K + 1;
     if (Lo <= 0) return Lo;
     // the input gradient (when it is wanted at all: not for the first layer) must understand the stride too
-    if (mfma_wgrad_dma_supported(C_in, C_out, K) && (!need_dx || mfma_fwd_supported(C_out, C_in, K, K - 1 - pad)))
-        return cdiv(Lo, 64) * 64;
+    if (mfma_wgrad_supported(C_in, C_out, K) && (!need_dx || mfma_fwd_supported(C_out, C_in, K, K - 1 - pad)))
+        return mfma_wgrad_dma_stride(Lo, 64);
     return Lo;
 }
 
@@ -126,15 +138,11 @@ ECG_API int ecg_conv1d_multiplies_per_output_pair(int op, int C_in, int C_out, i
 // (w_bwd [K][C_out][C_in]) and padding K-1-pad: roles of C_in / C_out swap.
 ECG_API int ecg_conv1d_bwd_data_ld(const float *dy, int ldy, const float *w_bwd, float *dx, int N,
                                    int C_in, int C_out, int L, int K, int pad, ecg_stream_t stream) {
-    int rc = check_conv_shape(N, C_in, C_out, L, K, pad);
-    if (rc) return rc;
-    ECG_REQUIRE(dy && w_bwd && dx, "conv1d_bwd_data: null pointer");
     const int Lo = L + 2 * pad - K + 1, padb = K - 1 - pad;
-    ECG_REQUIRE(ldy >= Lo, "conv1d_bwd_data: dY row stride %d < row length %d", ldy, Lo);
-    if (mfma_fwd_supported(C_out, C_in, K, padb))
-        return mfma_fwd(dy, ldy, w_bwd, nullptr, dx, nullptr, N, C_out, C_in, Lo, K, padb, as_stream(stream));
-    ECG_REQUIRE(ldy == Lo, "conv1d_bwd_data: this shape needs dense dY rows (stride %d != %d); "
-                "use the stride ecg_conv1d_dy_row_stride returns", ldy, Lo);
+    const bool mfma = mfma_fwd_supported(C_out, C_in, K, padb);
+    int rc = check_conv_grad("conv1d_bwd_data", dy && w_bwd && dx, ldy, mfma, N, C_in, C_out, L, K, pad);
+    if (rc) return rc;
+    if (mfma) return mfma_fwd(dy, ldy, w_bwd, nullptr, dx, nullptr, N, C_out, C_in, Lo, K, padb, as_stream(stream));
     return direct_fwd(dy, w_bwd, nullptr, dx, nullptr, N, C_out, C_in, Lo, K, padb, as_stream(stream));
 }
 
@@ -144,22 +152,17 @@ ECG_API int ecg_conv1d_bwd_data(const float *dy, const float *w_bwd, float *dx, 
 }
 
 ECG_API size_t ecg_conv1d_bwd_weight_ws_floats(int N, int C_in, int C_out, int L, int K, int pad) {
-    if (mfma_wgrad_supported(C_in, C_out, K, pad)) return mfma_wgrad_ws_floats(N, C_in, C_out, L, K, pad);
+    if (mfma_wgrad_supported(C_in, C_out, K)) return mfma_wgrad_ws_floats(N, C_in, C_out, L, K, pad);
     return direct_wgrad_ws_floats(N, C_in, C_out, K);
 }
 
 ECG_API int ecg_conv1d_bwd_weight_bias_ld(const float *dy, int ldy, const float *x, float *dw,
                                           float *db, float *ws, int N, int C_in, int C_out, int L,
                                           int K, int pad, ecg_stream_t stream) {
-    int rc = check_conv_shape(N, C_in, C_out, L, K, pad);
+    const bool mfma = mfma_wgrad_supported(C_in, C_out, K);
+    int rc = check_conv_grad("conv1d_bwd_weight_bias", dy && x && dw && ws, ldy, mfma, N, C_in, C_out, L, K, pad);
     if (rc) return rc;
-    ECG_REQUIRE(dy && x && dw && ws, "conv1d_bwd_weight_bias: null pointer");
-    const int Lo = L + 2 * pad - K + 1;
-    ECG_REQUIRE(ldy >= Lo, "conv1d_bwd_weight_bias: dY row stride %d < row length %d", ldy, Lo);
-    if (mfma_wgrad_supported(C_in, C_out, K, pad))
-        return mfma_wgrad(dy, ldy, x, dw, db, ws, N, C_in, C_out, L, K, pad, as_stream(stream));
-    ECG_REQUIRE(ldy == Lo, "conv1d_bwd_weight_bias: this shape needs dense dY rows (stride %d != %d); "
-                "use the stride ecg_conv1d_dy_row_stride returns", ldy, Lo);
+    if (mfma) return mfma_wgrad(dy, ldy, x, dw, db, ws, N, C_in, C_out, L, K, pad, as_stream(stream));
     return direct_wgrad(dy, x, dw, db, ws, N, C_in, C_out, L, K, pad, as_stream(stream));
 }
 
@@ -176,14 +179,11 @@ ECG_API int ecg_conv1d_bwd_weight_bias(const float *dy, const float *x, float *d
 ECG_API int ecg_conv1d_bwd_weight_data_ld(const float *dy, int ldy, const float *x, const float *w_bwd,
                                           float *dw, float *db, float *dx, float *ws, int N, int C_in,
                                           int C_out, int L, int K, int pad, ecg_stream_t stream) {
-    int rc = check_conv_shape(N, C_in, C_out, L, K, pad);
-    if (rc) return rc;
-    ECG_REQUIRE(dy && x && w_bwd && dw && dx && ws, "conv1d_bwd_weight_data: null pointer");
     const int Lo = L + 2 * pad - K + 1, padb = K - 1 - pad;
-    ECG_REQUIRE(ldy >= Lo, "conv1d_bwd_weight_data: dY row stride %d < row length %d", ldy, Lo);
-    const bool wg_mfma = mfma_wgrad_supported(C_in, C_out, K, pad), dg_mfma = mfma_fwd_supported(C_out, C_in, K, padb);
-    ECG_REQUIRE((wg_mfma && dg_mfma) || ldy == Lo, "conv1d_bwd_weight_data: this shape needs dense dY rows (stride %d != %d); "
-                "use the stride ecg_conv1d_dy_row_stride returns", ldy, Lo);
+    const bool wg_mfma = mfma_wgrad_supported(C_in, C_out, K), dg_mfma = mfma_fwd_supported(C_out, C_in, K, padb);
+    int rc = check_conv_grad("conv1d_bwd_weight_data", dy && x && w_bwd && dw && dx && ws, ldy, wg_mfma && dg_mfma, N, C_in, C_out,
+                             L, K, pad);
+    if (rc) return rc;
     hipStream_t st = as_stream(stream);
     WgradReduce red;
     rc = wg_mfma ? mfma_wgrad_slabs(dy, ldy, x, dw, db, ws, N, C_in, C_out, L, K, pad, st, &red)

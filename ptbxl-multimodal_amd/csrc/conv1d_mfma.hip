@@ -1384,8 +1384,6 @@ __global__ __launch_bounds__(64) void wgrad_ffa_reduce_kernel(const float *__res
 WgradReduce wgrad_reduce_describe(const float *ws, float *dw, float *db, size_t wslab, int Cin, int Cout, int S);
 int wgrad_reduce_launch(const WgradReduce &r, hipStream_t st);
 
-struct WgCfg { int m_t, r_t, splits; };
-
 // Development knobs are COMPILE-TIME (A/B libraries: make VARIANT=x EXTRA="-DECG_WG_SLOTS=768"): the product library reads no
 // environment variable.
 #ifndef ECG_WG_SLOTS
@@ -1395,108 +1393,103 @@ struct WgCfg { int m_t, r_t, splits; };
 #define ECG_WG_TT128 1       // 128-step stages on the 64- / 32-channel tiles (A/B: -DECG_WG_TT128=0)
 #endif
 
-static WgCfg wgrad_cfg(int N, int Cin, int Cout, int Lo, bool dma, int tt = 64) {
-    const int R = Cin * kKM;
-    constexpr int slots = ECG_WG_SLOTS;
-    WgCfg c;
+bool mfma_wgrad_supported(int Cin, int Cout, int K) { return K == kKM && Cout % 32 == 0; }
+
+// dY rows the DMA kernels can stream in tt-float stages: a stride that is a multiple of tt, zero pad up to it (see the kernel)
+int mfma_wgrad_dma_stride(int Lo, int tt) { return cdiv(Lo, tt) * tt; }
+static bool wgrad_dma_rows(int ldy, int Lo, int tt) { return ldy % tt == 0 && ldy >= mfma_wgrad_dma_stride(Lo, tt); }
+
+// THE weight-gradient decision: which kernel runs, on which tile, and how many slabs it writes.  mfma_wgrad_slabs launches
+// from it, mfma_wgrad_ws_floats sizes from it, mfma_multiplies_per_pair reports its form.
+enum WgForm { WG_FFA, WG_DMA, WG_REG };         // fast-FIR / LDS-DMA / register-staged
+struct WgPlan {
+    WgForm form;
+    int m_t, r_t, tt;           // channel tile, column tile, steps per stage (DMA forms)
+    int tiles, splits;          // grid = tiles * splits; the kernel writes `splits` slabs
+    size_t slab_floats;         // one weight slab (the bias slab, C_out floats per split, sits behind them)
+};
+
+// `dma`: the dY rows can be streamed in 64-float stages (wgrad_dma_rows, 16-byte base); `tt128`: in 128-float stages too.
+// `ffa` = false asks for the 15-tap DMA form at a fast-FIR shape: never launched, only sized (mfma_wgrad_ws_floats).
+static WgPlan wgrad_plan(int N, int Cin, int Cout, int Lo, int K, bool dma, bool tt128, bool ffa = true) {
+    WgPlan p;
     // 128 x 128 tiles on the 128-channel layers.  (128 x 192 tiles, where 192 divide the columns and 128 leave a ragged last
     // tile — block 2: R = 960 = 5 x 192 instead of 7.5 x 128 — measured 154.7 -> 150.3 us with single-level accumulation; with
     // the two-level accumulation that tile needs 96 + 96 accumulator registers and spills, so it is not built: +3 us on
     // block 2.  Block 3, R = 1920 = 15 x 128 = 10 x 192: 264.0 vs 267.5 us, 128 was the better tile anyway.)
     // More, smaller workgroups (ECG_WG_SLOTS 768 / 1024: a second round in the slots the early finishers
     // free) measured 2-8 % SLOWER on every layer — the second prologue / slab costs more than the tail it evens out.
-    if (Cout % 128 == 0) c = {128, 128, 0};
-    else if (Cout % 64 == 0) c = {64, 128, 0};
-    else c = {32, 192, 0};
-    const int tiles = cdiv(R, c.r_t) * (Cout / c.m_t);
-    int s = slots / tiles;             // fill, but never exceed, the 2 x 256 resident-workgroup slots:
-                                       // one workgroup over and the launch takes two rounds.
-                                       // (64-channel tiles at 4 workgroups per CU measured no better here; nor did
-                                       // 128 x 256 column tiles for block 3: 273 vs 271 us, 236 VGPRs.)
-    // the DMA kernel splits over stages (n, 64- or 128-wide t tile), the register-staged one over samples
-    const long long cap = dma ? (long long)N * cdiv(Lo, tt) : N;
-    if (s > cap) s = (int)cap;
-    if (s < 1) s = 1;
-    c.splits = s;
-    return c;
+    p.m_t = Cout % 128 == 0 ? 128 : Cout % 64 == 0 ? 64 : 32;
+    p.r_t = p.m_t == 32 ? 192 : 128;
+    // fast-FIR form: 128-channel tiles, column tiles of 128 over the three families (U: 8 C_in, V: 7 C_in, G: 8 C_in columns),
+    // 64-step stages.
+    // Measured (B = 256, 12x1000, same box): 128 -> 256 channels 290.3 -> 277.0 us; 64 -> 128 164.5 -> 164.8; 32 -> 64 88.9 -> 94.4 —
+    // a stage is half as many MFMA steps between the same barrier, x commits and second-level adds (~2 000 cycles per stage
+    // in both forms), and 128-step stages do not fit two workgroups per CU here: used where the column count makes it pay.
+    p.form = !dma ? WG_REG : (ffa && p.m_t == 128 && Cin >= 128) ? WG_FFA : WG_DMA;
+    // 128-step stages for the small tiles (blocks 0-1) when the rows allow it
+    p.tt = (ECG_WG_TT128 && tt128 && p.form == WG_DMA && p.m_t != 128) ? 128 : 64;
+    const int cols = p.form == WG_FFA ? 23 : K;
+    p.tiles = (p.form == WG_FFA ? 2 * cdiv(Cin * 8, 128) + cdiv(Cin * 7, 128) : cdiv(Cin * K, p.r_t)) * (Cout / p.m_t);
+    p.slab_floats = (size_t)Cout * Cin * cols;
+    // fill, but never exceed, the 2 x 256 resident-workgroup slots: one workgroup over and the launch takes two rounds.
+    // (64-channel tiles at 4 workgroups per CU measured no better here; nor did 128 x 256 column tiles for block 3:
+    // 273 vs 271 us, 236 VGPRs.)
+    // the DMA kernels split over stages (n, 64- or 128-wide t tile), the register-staged one over samples
+    const long long cap = p.form == WG_REG ? N : (long long)N * cdiv(Lo, p.tt);
+    const long long s = ECG_WG_SLOTS / p.tiles;
+    p.splits = (int)(s > cap ? cap : s < 1 ? 1 : s);
+    return p;
 }
 
-// fast-FIR form: 128-channel tiles, column tiles of 128 over the three families (U: 8 C_in, V: 7 C_in, G: 8 C_in columns),
-// 64-step stages.
-// Measured (B = 256, 12x1000, same box): 128 -> 256 channels 290.3 -> 277.0 us; 64 -> 128 164.5 -> 164.8; 32 -> 64 88.9 -> 94.4 —
-// a stage is half as many MFMA steps between the same barrier, x commits and second-level adds (~2 000 cycles per stage
-// in both forms), and 128-step stages do not fit two workgroups per CU here: used where the column count makes it pay.
-static bool wgrad_ffa_ok(int Cin, int Cout, bool dma) { return dma && Cout % 128 == 0 && Cin >= 128; }
-static int wgrad_ffa_tiles(int Cin, int Cout) { return (2 * cdiv(Cin * 8, 128) + cdiv(Cin * 7, 128)) * (Cout / 128); }
-static int wgrad_ffa_splits(int N, int Cin, int Cout, int Lo) {
-    long long s = ECG_WG_SLOTS / wgrad_ffa_tiles(Cin, Cout);
-    const long long cap = (long long)N * cdiv(Lo, 64);
-    if (s > cap) s = cap;
-    if (s < 1) s = 1;
-    return (int)s;
-}
-
-bool mfma_wgrad_dma_supported(int Cin, int Cout, int K);
-// what ecg_conv1d_multiplies_per_output_pair reports: mirrors the dispatch of launch_fwd / mfma_wgrad
+// what ecg_conv1d_multiplies_per_output_pair reports: the form launch_fwd takes (ops 0, 1, 3) and the weight-gradient plan
+// for the rows ecg_conv1d_dy_row_stride asks for (op 2)
 int mfma_multiplies_per_pair(int op, int Cin, int Cout, int K, int pad) {
-    if (op == 2) return (K == kKM && wgrad_ffa_ok(Cin, Cout, mfma_wgrad_dma_supported(Cin, Cout, K))) ? 23 : 2 * K;
+    if (op == 2) return (mfma_wgrad_supported(Cin, Cout, K) && wgrad_plan(1, Cin, Cout, 1, K, true, true).form == WG_FFA) ? 23 : 2 * K;
     const bool mfma = op == 1 ? mfma_fwd_supported(Cout, Cin, K, K - 1 - pad) : mfma_fwd_supported(Cin, Cout, K, pad);
     return mfma ? 23 : 2 * K;
 }
 
-bool mfma_wgrad_supported(int Cin, int Cout, int K, int pad) {
-    (void)pad; (void)Cin;
-    return K == kKM && Cout % 32 == 0;
-}
-
+// the largest slab set over the dY layouts a caller may pass: dense rows, 64-float and 128-float multiples
 size_t mfma_wgrad_ws_floats(int N, int Cin, int Cout, int L, int K, int pad) {
     const int Lo = L + 2 * pad - K + 1;
-    const WgCfg a = wgrad_cfg(N, Cin, Cout, Lo, false), b = wgrad_cfg(N, Cin, Cout, Lo, true);      // (128-step stages: never more splits)
-    size_t need = (size_t)(a.splits > b.splits ? a.splits : b.splits) * ((size_t)Cout * Cin * K + Cout);
-    if (wgrad_ffa_ok(Cin, Cout, true)) {
-        const size_t ffa = (size_t)wgrad_ffa_splits(N, Cin, Cout, Lo) * ((size_t)Cout * Cin * 23 + Cout);
-        if (ffa > need) need = ffa;
+    const WgPlan plans[] = {wgrad_plan(N, Cin, Cout, Lo, K, false, false), wgrad_plan(N, Cin, Cout, Lo, K, true, false),
+                            wgrad_plan(N, Cin, Cout, Lo, K, true, true),
+                            // (the 15-tap slabs of a fast-FIR shape: part of the size ever since that form came)
+                            wgrad_plan(N, Cin, Cout, Lo, K, true, false, false)};
+    size_t need = 0;
+    for (const WgPlan &p : plans) {
+        const size_t f = (size_t)p.splits * (p.slab_floats + Cout);
+        if (f > need) need = f;
     }
     return need;
-}
-
-// dY rows that the DMA kernel can stream: 64-float multiples with a zero pad (see the kernel)
-bool mfma_wgrad_dma_supported(int Cin, int Cout, int K) {
-    (void)Cin;
-    return K == kKM && Cout % 32 == 0;
 }
 
 // launches the slab kernel and describes the reduce that has to follow it
 int mfma_wgrad_slabs(const float *dy, int ldy, const float *x, float *dw, float *db, float *ws, int N,
                      int Cin, int Cout, int L, int K, int pad, hipStream_t st, WgradReduce *red) {
     const int Lo = L + 2 * pad - K + 1;
-    const int R = Cin * K;
-    const bool dma = mfma_wgrad_dma_supported(Cin, Cout, K) && ldy % 64 == 0 && ldy >= cdiv(Lo, 64) * 64 &&
-                     (reinterpret_cast<uintptr_t>(dy) & 15) == 0;
-    // 128-step stages for the small tiles (blocks 0-1) when the rows allow it (stride a multiple of 128 floats, zero pad to it)
-    const bool tt128 = ECG_WG_TT128 && dma && Cout % 128 != 0 && ldy % 128 == 0 && ldy >= cdiv(Lo, 128) * 128;
-    if (wgrad_ffa_ok(Cin, Cout, dma)) {
-        const int S = wgrad_ffa_splits(N, Cin, Cout, Lo);
-        dim3 fgrid((unsigned)(wgrad_ffa_tiles(Cin, Cout) * S)), fblock(256);
-        hipLaunchKernelGGL((conv1d_mfma_wgrad_ffa_kernel<128, 128, 2, 2, 64>), fgrid, fblock, 0, st, dy, x, ws, N, Cin, Cout, L, Lo,
-                           ldy, pad, S);
-        *red = WgradReduce{ws, dw, db, (size_t)Cout * Cin * 23, Cin, Cout, S, WGR_FFA, 1, 0};
+    const bool dma = wgrad_dma_rows(ldy, Lo, 64) && (reinterpret_cast<uintptr_t>(dy) & 15) == 0;
+    const WgPlan p = wgrad_plan(N, Cin, Cout, Lo, K, dma, wgrad_dma_rows(ldy, Lo, 128));
+    dim3 grid((unsigned)(p.tiles * p.splits)), block(256);
+#define ECG_WG(KERNEL) \
+    hipLaunchKernelGGL(KERNEL, grid, block, 0, st, dy, x, ws, N, Cin, Cout, L, Lo, ldy, pad, p.splits)
+    if (p.form == WG_FFA) {
+        ECG_WG((conv1d_mfma_wgrad_ffa_kernel<128, 128, 2, 2, 64>));
+        *red = WgradReduce{ws, dw, db, p.slab_floats, Cin, Cout, p.splits, WGR_FFA, 1, 0};
         return check_launch("conv1d_mfma_wgrad_ffa_kernel");
     }
-    const WgCfg c = wgrad_cfg(N, Cin, Cout, Lo, dma, tt128 ? 128 : 64);
-    dim3 grid((unsigned)(cdiv(R, c.r_t) * (Cout / c.m_t) * c.splits)), block(256);
-#define ECG_WG(KERNEL) \
-    hipLaunchKernelGGL(KERNEL, grid, block, 0, st, dy, x, ws, N, Cin, Cout, L, Lo, ldy, pad, c.splits)
-    if (dma && c.m_t == 128) ECG_WG((conv1d_mfma_wgrad_dma_kernel<128, 128, 2, 2, 1, kKM>));
-    else if (tt128 && c.m_t == 64) ECG_WG((conv1d_mfma_wgrad_dma_kernel<64, 128, 2, 2, 1, kKM, 128>));
-    else if (tt128) ECG_WG((conv1d_mfma_wgrad_dma_kernel<32, 192, 1, 2, 2, kKM, 128>));
-    else if (dma && c.m_t == 64) ECG_WG((conv1d_mfma_wgrad_dma_kernel<64, 128, 2, 2, 1, kKM>));
-    else if (dma) ECG_WG((conv1d_mfma_wgrad_dma_kernel<32, 192, 1, 2, 2, kKM>));
-    else if (c.m_t == 128) ECG_WG((conv1d_mfma_wgrad_kernel<128, 128, 2, 2, 1, 64, kKM>));
-    else if (c.m_t == 64) ECG_WG((conv1d_mfma_wgrad_kernel<64, 128, 2, 2, 1, 64, kKM>));
+    if (p.form == WG_DMA) {
+        if (p.m_t == 128) ECG_WG((conv1d_mfma_wgrad_dma_kernel<128, 128, 2, 2, 1, kKM>));
+        else if (p.m_t == 64 && p.tt == 128) ECG_WG((conv1d_mfma_wgrad_dma_kernel<64, 128, 2, 2, 1, kKM, 128>));
+        else if (p.tt == 128) ECG_WG((conv1d_mfma_wgrad_dma_kernel<32, 192, 1, 2, 2, kKM, 128>));
+        else if (p.m_t == 64) ECG_WG((conv1d_mfma_wgrad_dma_kernel<64, 128, 2, 2, 1, kKM>));
+        else ECG_WG((conv1d_mfma_wgrad_dma_kernel<32, 192, 1, 2, 2, kKM>));
+    } else if (p.m_t == 128) ECG_WG((conv1d_mfma_wgrad_kernel<128, 128, 2, 2, 1, 64, kKM>));
+    else if (p.m_t == 64) ECG_WG((conv1d_mfma_wgrad_kernel<64, 128, 2, 2, 1, 64, kKM>));
     else ECG_WG((conv1d_mfma_wgrad_kernel<32, 192, 1, 2, 2, 128, kKM>));
 #undef ECG_WG
-    *red = wgrad_reduce_describe(ws, dw, db, (size_t)Cout * R, Cin, Cout, c.splits);
+    *red = wgrad_reduce_describe(ws, dw, db, p.slab_floats, Cin, Cout, p.splits);
     return check_launch("conv1d_mfma_wgrad_kernel");
 }
 

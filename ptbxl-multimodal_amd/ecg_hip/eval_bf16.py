@@ -1,7 +1,7 @@
 """The bf16 inference form of a ConvBlock (inference_precision("bf16")): ONE launch of the ring kernel with an eval
 epilogue — conv on bf16 operands (fp32 accumulate), eval BatchNorm folded with the bias, ReLU, MaxPool(2) [, global
-average pool] — include/ecg_hip.h, ecg_conv1d_bn_relu_pool_eval_fwd_bf16.  ConvBlockFn picks it; this module holds the
-geometry test and the launch.
+average pool] — include/ecg_hip.h, ecg_conv1d_bn_relu_pool_eval_fwd_bf16.  functional.block_form picks it; this module holds
+the launch.
 
 Activations between two such blocks are bf16 rows [N][C][ldp] zero-filled past the pooled length (the row contract of the
 mixed-precision training form, with the same carry of the true length); the network input is read as fp32 and rounded
@@ -9,26 +9,6 @@ while it is staged; the last block of a chain writes fp32 (the global average po
 import torch
 
 from . import _lib as L
-
-
-def covered(Ci, Co, K, pad, Lin, gap, x_bf16):
-    """Does the one-launch bf16 eval kernel take this block: bit 0 of the geometry query for a bf16 input, bit 1 for fp32."""
-    if K > 15 or Lin <= 0:
-        return False
-    return bool(L.query("ecg_conv1d_bn_relu_pool_eval_bf16_supported", Ci, Co, Lin, K, pad, 1 if gap else 0)
-                & (1 if x_bf16 else 2))
-
-
-def packable(Ci, Co, K, pad):
-    """Geometry-only test for the weight packer (the row length is not known there)."""
-    return K <= 15 and bool(L.query("ecg_conv1d_bn_relu_pool_eval_bf16_supported", Ci, Co, 256, K, pad, 0))
-
-
-def takes(x, Ci, Co, K, pad, Lin, gap):
-    """The block form test for an actual input: a bf16 activation, or an fp32 tensor the kernel reads in place."""
-    if x.dtype == torch.bfloat16:
-        return covered(Ci, Co, K, pad, Lin, gap, True)
-    return x.dtype == torch.float32 and x.data_ptr() % 8 == 0 and covered(Ci, Co, K, pad, Lin, gap, False)
 
 
 def forward(x, wb, w_shape, b, gamma, beta, running_mean, running_var, eps, pad, gap, Lin, next_bf16):

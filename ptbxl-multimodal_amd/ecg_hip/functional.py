@@ -4,6 +4,8 @@ Each Function's forward/backward is a straight sequence of libecg_hip.so launche
 torch's current stream; torch only owns the memory.  Hand-written backward formulas are
 the ones restated (and pinned against the reference) in oracle/ecg_oracle.c.
 """
+import functools
+
 import torch
 
 from . import _lib as L
@@ -198,9 +200,8 @@ def conv1d_pack(w, need_bwd=True):
 # K = 15, pad = 7, channel counts the bf16 MFMA kernels tile) runs its three convs on bf16 operands with fp32 accumulation
 # and keeps every tensor between its kernels as bf16 rows [N][C][ld] — y, the pooled activation handed to the next
 # block, dY and the input gradient handed back — while parameters, statistics, gradients of parameters, the network
-# input, the tail and the optimizer stay fp32.  A block that does not fit that form (frozen or eval-mode BatchNorm, no
-# gradient wanted, other kernel sizes or channel counts) runs the exact fp32 kernels instead, and tensors crossing between the
-# two forms are fp32.  Inference has its own knob, below.
+# input, the tail and the optimizer stay fp32.  A block that does not fit that form (block_form) runs the exact fp32 kernels
+# instead, and tensors crossing between the two forms are fp32.  Inference has its own knob, below.
 # ECG_HIP_CONV_PRECISION sets the process default.
 # --------------------------------------------------------------------------------------
 _conv_precision = _os.environ.get("ECG_HIP_CONV_PRECISION", "fp32")
@@ -262,13 +263,13 @@ class inference_precision(conv_precision):
         return False
 
 
+def _bf16_operand(w, Ci, Co, K):
+    return torch.empty(_query("ecg_conv1d_bf16_packed_elems", Ci, Co, K), dtype=torch.bfloat16, device=w.device)
+
+
 def conv1d_pack_bf16(w, need_bwd=True):
     Co, Ci, K = w.shape
-    nf = _query("ecg_conv1d_bf16_packed_elems", Ci, Co, K)
-    wb_fwd = torch.empty(nf, dtype=torch.bfloat16, device=w.device)
-    wb_bwd = None
-    if need_bwd:
-        wb_bwd = torch.empty(_query("ecg_conv1d_bf16_packed_elems", Co, Ci, K), dtype=torch.bfloat16, device=w.device)
+    wb_fwd, wb_bwd = _bf16_operand(w, Ci, Co, K), _bf16_operand(w, Co, Ci, K) if need_bwd else None
     _call("ecg_conv1d_pack_weights_bf16", _f32(w), L.ptr(wb_fwd), L.ptr(wb_bwd), Co, Ci, K, _st())
     return wb_fwd, wb_bwd
 
@@ -291,35 +292,31 @@ class WeightPacker:
     def __setstate__(self, state):
         self._key = None
 
-    def pack(self, convs, linears, need_bwd):
-        """-> (conv_packs, linear_T); conv_packs[i] = (w_fwd, w_bwd) fp32 operands, or in bf16 mode, for a conv the
-        bf16 kernels take, (w_fwd, w_bwd, wb_fwd, wb_bwd) with the fp32 pair None — the bf16 operands come out of the
-        same launch (one launch per step instead of one per layer plus the fp32 one)."""
+    def pack(self, convs, linears, need_bwd, x=None, bns=None):
+        """-> (conv_packs, linear_T); conv_packs[i] = (w_fwd, w_bwd) fp32 operands, or where the block takes a bf16 form
+        (None, None, wb_fwd, wb_bwd), out of the same launch.  With `x` (the tensor entering convs[0]) and `bns` (each conv's
+        BatchNorm) the convs are the chain a model's forward runs, the last one under the global average pool: every block gets
+        exactly the operands its form reads (_operand_kinds).  Without: every conv alone, the shortest row that pools."""
         srcs = [c.weight for c in convs] + [l.weight for l in linears]
-        mixed = _conv_precision == "bf16" and bool(need_bwd)       # (without gradients every block runs the fp32 kernels)
-        infer = _inference_precision == "bf16" and not need_bwd     # bf16 eval blocks: wb_fwd only
-        key = (need_bwd, mixed, infer) + tuple((w.data_ptr(), tuple(w.shape)) for w in srcs)
+        shapes = tuple(w.shape for w in srcs)
+        geo = tuple((sh, c.padding[0]) for sh, c in zip(shapes, convs))
+        chain, need_bwd = x is not None, bool(need_bwd)
+        batch = tuple(bn.training or bn.running_mean is None for bn in bns) if chain else (need_bwd,) * len(convs)
+        kinds = _operand_kinds(geo, _x_kind(x) if chain else _X_F32, x.shape[2] if chain else None, batch, need_bwd,
+                               chain and need_bwd and x.requires_grad, _conv_precision, _inference_precision)
+        key = kinds + shapes + tuple(w.data_ptr() for w in srcs)
         if key != self._key:
             self._key = key
             self.conv_packs, self.linear_T, fw, bw, hf, hb, co, ci, kk = [], [], [], [], [], [], [], [], []
-            for i, c in enumerate(convs):
+            for c, (h, want_bwd) in zip(convs, kinds):
                 w = _contig(c.weight)
                 Co, Ci, K = w.shape
-                want_bwd = need_bwd and i > 0                # block 0 has no input-grad
-                # (bf16 operands for a conv whose geometry fits the mixed-precision form; whether the block really takes it
-                # is decided per call — a block that does not repacks its fp32 operands itself, ConvBlockFn._weights)
-                if (mixed and _bf16_block_ok(Ci, Co, K, c.padding[0], 16, want_bwd)) or (infer and _EB.packable(Ci, Co, K,
-                                                                                                    c.padding[0])):
-                    wf = wb = None
-                    hwf = torch.empty(_query("ecg_conv1d_bf16_packed_elems", Ci, Co, K), dtype=torch.bfloat16, device=w.device)
-                    hwb = (torch.empty(_query("ecg_conv1d_bf16_packed_elems", Co, Ci, K), dtype=torch.bfloat16,
-                                       device=w.device) if want_bwd else None)
-                    self.conv_packs.append((None, None, hwf, hwb))
+                wf = wb = hwf = hwb = None
+                if h:
+                    hwf, hwb = _bf16_operand(w, Ci, Co, K), _bf16_operand(w, Co, Ci, K) if want_bwd else None
                 else:
-                    hwf = hwb = None
-                    wf = torch.empty_like(w).view(K, Ci, Co)
-                    wb = torch.empty_like(w).view(K, Co, Ci) if want_bwd else None
-                    self.conv_packs.append((wf, wb))
+                    wf, wb = torch.empty_like(w).view(K, Ci, Co), torch.empty_like(w).view(K, Co, Ci) if want_bwd else None
+                self.conv_packs.append((None, None, hwf, hwb) if h else (wf, wb))
                 fw.append(wf); bw.append(wb); hf.append(hwf); hb.append(hwb); co.append(Co); ci.append(Ci); kk.append(K)
             for l in linears:
                 w = _contig(l.weight)
@@ -419,27 +416,65 @@ def _bn_momentum(momentum, nbt):
 # --------------------------------------------------------------------------------------
 # Fused ConvBlock: Conv1d -> BatchNorm1d -> ReLU -> MaxPool1d(2)
 # --------------------------------------------------------------------------------------
-def _bf16_block_ok(Ci, Co, K, pad, Lin, need_dx):
-    """Geometry test of the mixed-precision block form: the bf16 forward (bit 0 of ecg_conv1d_bf16_supported), the time-on-K
-    weight gradient (bit 2: K == 15, pad == 7, C_out % 32 == 0 — which also gives the odd pad / odd K-1-pad the position-pair
-    staging of bf16 rows needs), the bf16 input gradient when one is wanted (bit 1), and a pooled row that is not empty."""
-    if K > 15:
-        return False
-    sup = _query("ecg_conv1d_bf16_supported", Ci, Co, K, pad)
-    return bool((sup & 1) and (sup & 4) and (not need_dx or (sup & 2)) and Lin + 2 * pad - K + 1 >= 2)
-
-
 _EVAL, _FP32, _BF16, _EVAL_BF16 = "eval", "fp32", "bf16", "eval_bf16"
+_BF16_FORMS = (_BF16, _EVAL_BF16)       # the forms that read bf16 operands and take / hand on bf16 rows
+_X_OTHER, _X_F32, _X_BF16 = 0, 1, 2     # input kinds: fp32 the kernels cannot read in place / fp32 they can / bf16 rows
+
+
+def _x_kind(x):         # (fp32 read in place: 8-byte aligned, or about to be copied into a fresh tensor by _contig)
+    if x.dtype == torch.bfloat16:
+        return _X_BF16
+    return _X_F32 if x.dtype == torch.float32 and (x.data_ptr() % 8 == 0 or not x.is_contiguous()) else _X_OTHER
+
+
+@functools.lru_cache(maxsize=4096)
+def block_form(Ci, Co, K, pad, Lin, gap, x_kind, batch_stats, need_grad, need_dx, conv_prec, infer_prec):
+    """THE form of a ConvBlock, from ints and bools only (memoised like _lib.query): asked by the block for itself, by
+    conv_block_chain for the block that consumes its output, by WeightPacker for the operands to pack.
+      bf16       the mixed-precision training form: batch statistics, a gradient wanted, conv precision "bf16", a pooled row
+                 that is not empty, and ecg_conv1d_bf16_supported has the forward (bit 0), the time-on-K weight gradient (bit 2:
+                 K == 15, pad == 7, C_out % 32 == 0) and the input gradient if one is wanted (bit 1)
+      eval_bf16  one launch on bf16 operands: running statistics, no gradient, inference precision "bf16", and the bf16 eval
+                 kernel covers the block for this input (bit 0 of its geometry query: bf16 rows, bit 1: fp32 read in place)
+      eval       conv + folded BN + ReLU + pool [+ GAP] in one fp32 launch: running statistics, no gradient, a shape it tiles
+      fp32       everything else — the parity path.  bf16 rows (x_kind) into `eval` or `fp32` cannot run: the caller raises."""
+    if batch_stats != need_grad:
+        return _FP32
+    if batch_stats:
+        ok = conv_prec == "bf16" and K <= 15 and Lin + 2 * pad - K + 1 >= 2
+        sup = _query("ecg_conv1d_bf16_supported", Ci, Co, K, pad) if ok else 0
+        return _BF16 if (sup & 1) and (sup & 4) and (not need_dx or (sup & 2)) else _FP32
+    if (infer_prec == "bf16" and x_kind != _X_OTHER and K <= 15 and Lin > 0 and (1 if x_kind == _X_BF16 else 2)
+            & _query("ecg_conv1d_bn_relu_pool_eval_bf16_supported", Ci, Co, Lin, K, pad, int(gap))):
+        return _EVAL_BF16
+    ok = (_query("ecg_conv1d_bn_relu_pool_gap_eval_supported", Ci, Co, Lin, K, pad) if gap else
+          _query("ecg_conv1d_bn_relu_pool_eval_supported", Ci, Co, K, pad))
+    return _EVAL if ok else _FP32
+
+
+@functools.lru_cache(maxsize=256)
+def _operand_kinds(geo, kind, Lin, batch, need_bwd, dx0, conv_prec, infer_prec):
+    """Per conv of a chain ((C_out, C_in, K), pad) the operands its block reads, as (bf16 operands, input-gradient operand):
+    block_form asked along the chain as conv_block_chain asks it — `kind` / `Lin`: the input of block 0, `batch`: who uses
+    batch statistics, `dx0`: block 0 owes an input gradient.  Lin None: no chain, every conv alone on the shortest row."""
+    chain, n, out = Lin is not None, len(geo), []
+
+    def bf16(i, kind):          # does block i, fed `kind` rows, take a form that reads bf16 operands
+        (Co, Ci, K), pad = geo[i]
+        return block_form(Ci, Co, K, pad, Lin if chain else K + 1 - 2 * pad, chain and i == n - 1, kind, batch[i], need_bwd,
+                          need_bwd and (i > 0 or dx0), conv_prec, infer_prec) in _BF16_FORMS
+    for i, ((_, _, K), pad) in enumerate(geo):
+        out.append((bf16(i, kind), need_bwd and (i > 0 or dx0)))
+        if chain:
+            Lin = (Lin + 2 * pad - K + 1) // 2
+            kind = _X_BF16 if out[i][0] and i + 1 < n and bf16(i + 1, _X_BF16) else _X_F32
+    return tuple(out)
 
 
 class ConvBlockFn(torch.autograd.Function):
     """reference src/models/ecg_cnn.py:12-17 as 3 launches forward (conv + BN-statistics epilogue, statistics combine +
-    BN-apply + ReLU + pool) and 3-4 backward.  ONE dispatch at the top picks the form of the block, recorded in ctx.mode and
-    reused by backward:
-      eval   inference (running statistics, no gradient wanted): conv + folded BN + ReLU + pool [+ GAP] in one launch
-      bf16   the mixed-precision training form (set_conv_precision("bf16"), see _bf16_block_ok): bf16 rows between the kernels
-      eval_bf16  inference under set_inference_precision("bf16") where the bf16 eval kernel covers the block: one launch
-      fp32   everything else — the parity path"""
+    BN-apply + ReLU + pool) and 3-4 backward.  block_form picks the form (eval / bf16 / eval_bf16 / fp32), recorded in ctx.mode
+    and reused by backward."""
 
     @staticmethod
     def forward(ctx, x, w, b, gamma, beta, running_mean, running_var, nbt, training, momentum,
@@ -459,14 +494,9 @@ class ConvBlockFn(torch.autograd.Function):
         Lo = Lin + 2 * pad - K + 1
         if Lo <= 0:
             raise L.EcgHipError(f"conv1d: empty output for L={Lin}, K={K}, pad={pad}")
-        mode = _FP32
-        if _conv_precision == "bf16" and use_batch and need_grad and _bf16_block_ok(Ci, Co, K, pad, Lin, need_dx):
-            mode = _BF16
-        elif not use_batch and not need_grad:
-            mode = _EVAL
-            if _inference_precision == "bf16" and _EB.takes(x, Ci, Co, K, pad, Lin, gap):
-                mode = _EVAL_BF16
-        if x_h and mode not in (_BF16, _EVAL_BF16):
+        mode = block_form(Ci, Co, K, pad, Lin, bool(gap), _x_kind(x), bool(use_batch), bool(need_grad), need_dx, _conv_precision,
+                          _inference_precision)
+        if x_h and mode not in _BF16_FORMS:
             # the producer wrote p as bf16 because this block looked able to read it: the precision was switched, or a
             # BatchNorm frozen, between the two calls
             raise L.EcgHipError("ConvBlock: input arrived as a bf16 activation but this block does not take the mixed-"
@@ -476,11 +506,13 @@ class ConvBlockFn(torch.autograd.Function):
         if mode == _EVAL_BF16:
             wb, _ = ConvBlockFn._weights(w, packed, True, False)
             return _EB.forward(x, wb, w.shape, b, gamma, beta, running_mean, running_var, eps, pad, gap, Lin, next_bf16)
-        if mode == _EVAL:
-            p = ConvBlockFn._fwd_eval(x, w, b, gamma, beta, running_mean, running_var, eps, pad, gap, packed)
-            if p is not None:
-                return p
-            ctx.mode = mode = _FP32            # (a shape the one-launch kernel does not tile: the three-launch sequence)
+        if mode == _EVAL:              # one launch, y never written
+            w_fwd, _ = ConvBlockFn._weights(w, packed, False, False)
+            out = _empty(x, x.shape[0], Co) if gap else _empty(x, x.shape[0], Co, Lo // 2)
+            _call("ecg_conv1d_bn_relu_pool_gap_eval_fwd" if gap else "ecg_conv1d_bn_relu_pool_eval_fwd", _f32(x), _f32(w_fwd),
+                  _f32(b), _f32(gamma), _f32(beta), _f32(running_mean), _f32(running_var), float(eps), _f32(out), x.shape[0],
+                  Ci, Co, Lin, K, pad, _st())
+            return out
         if mode == _BF16:
             return ConvBlockFn._fwd_bf16(ctx, x, w, b, gamma, beta, running_mean, running_var, nbt, training, momentum, eps,
                                          packed, need_dx, next_bf16)
@@ -490,33 +522,10 @@ class ConvBlockFn(torch.autograd.Function):
     # ---- weights: from the model's grouped repack when it holds what this form needs, else packed here -------------------
     @staticmethod
     def _weights(w, packed, bf16, need_bwd):
-        if bf16:
-            if packed is not None and len(packed) == 4 and packed[2] is not None and (packed[3] is not None or not need_bwd):
-                return packed[2], packed[3]
-            return conv1d_pack_bf16(w, need_bwd=need_bwd)
-        if packed is not None and packed[0] is not None and (packed[1] is not None or not need_bwd):
-            return packed[0], packed[1]
-        return conv1d_pack(w, need_bwd=need_bwd)
-
-    # ---- eval: one launch, y never written --------------------------------------------------------------------------
-    @staticmethod
-    def _fwd_eval(x, w, b, gamma, beta, running_mean, running_var, eps, pad, gap, packed):
-        N, Ci, Lin = x.shape
-        Co, _, K = w.shape
-        Lo = Lin + 2 * pad - K + 1
-        if not gap and _query("ecg_conv1d_bn_relu_pool_eval_supported", Ci, Co, K, pad):
-            w_fwd, _ = ConvBlockFn._weights(w, packed, False, False)
-            p = _empty(x, N, Co, Lo // 2)
-            _call("ecg_conv1d_bn_relu_pool_eval_fwd", _f32(x), _f32(w_fwd), _f32(b), _f32(gamma), _f32(beta),
-                  _f32(running_mean), _f32(running_var), float(eps), _f32(p), N, Ci, Co, Lin, K, pad, _st())
-            return p
-        if gap and _query("ecg_conv1d_bn_relu_pool_gap_eval_supported", Ci, Co, Lin, K, pad):
-            w_fwd, _ = ConvBlockFn._weights(w, packed, False, False)
-            g = _empty(x, N, Co)
-            _call("ecg_conv1d_bn_relu_pool_gap_eval_fwd", _f32(x), _f32(w_fwd), _f32(b), _f32(gamma), _f32(beta),
-                  _f32(running_mean), _f32(running_var), float(eps), _f32(g), N, Ci, Co, Lin, K, pad, _st())
-            return g
-        return None
+        pk = () if packed is None else (packed[2:4] if bf16 else packed[:2])       # (fwd, bwd) of the asked kind, if packed
+        if pk and pk[0] is not None and (pk[1] is not None or not need_bwd):
+            return pk
+        return (conv1d_pack_bf16 if bf16 else conv1d_pack)(w, need_bwd=need_bwd)
 
     # ---- fp32: the parity path ----------------------------------------------------------------------------------------
     @staticmethod
@@ -730,29 +739,17 @@ def conv_block_chain(x, conv, bn, gap=False, packed=None, carry=None, next_conv=
     a bf16 activation [N][C][ld] (rows zero-filled past the pooled length) when the NEXT block of the chain (next_conv /
     next_bn given; next_gap: it is the last one, with the global average pool) takes that form too; the carry is then the
     true pooled length, to be handed to the next call — only the next block of the chain may consume such a tensor."""
-    nxt = False
-    if next_conv is not None and not gap:
-        x_len = carry if x.dtype == torch.bfloat16 else x.shape[2]
-        Lo = x_len + 2 * conv.padding[0] - conv.kernel_size[0] + 1
-        nK, npad = next_conv.kernel_size[0], next_conv.padding[0]
-        if _conv_precision == "bf16":
-            nxt = bool(next_bn is not None and (next_bn.training or next_bn.running_mean is None)
-                       and torch.is_grad_enabled()
-                       and _bf16_block_ok(conv.out_channels, next_conv.out_channels, nK, npad, Lo // 2, True))
-        if not nxt and _inference_precision == "bf16" and not torch.is_grad_enabled():
-            # this block and the next both take the bf16 eval form
-            nxt = bool(not (bn.training or bn.running_mean is None) and next_bn is not None
-                       and not (next_bn.training or next_bn.running_mean is None)
-                       and _EB.takes(x, conv.in_channels, conv.out_channels, conv.kernel_size[0], conv.padding[0], x_len,
-                                     False)
-                       and _EB.covered(conv.out_channels, next_conv.out_channels, nK, npad, Lo // 2, next_gap, True))
+    x_len, grad = carry if x.dtype == torch.bfloat16 else x.shape[2], torch.is_grad_enabled()
+    Lo = x_len + 2 * conv.padding[0] - conv.kernel_size[0] + 1
+    # does the consumer take bf16 rows = its own form asked with a bf16 input (grad mode as here); skipped while no knob is "bf16"
+    nxt = bool(next_conv is not None and next_bn is not None and not gap
+               and "bf16" in (_conv_precision, _inference_precision)) and block_form(
+        conv.out_channels, next_conv.out_channels, next_conv.kernel_size[0], next_conv.padding[0], Lo // 2, bool(next_gap),
+        _X_BF16, bool(next_bn.training or next_bn.running_mean is None), grad, grad, _conv_precision,
+        _inference_precision) in _BF16_FORMS
     p = ConvBlockFn.apply(x, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                          bn.num_batches_tracked, bn.training, bn.momentum, bn.eps, conv.padding[0], gap, packed,
-                          torch.is_grad_enabled(), carry, nxt)
-    if p.dtype == torch.bfloat16:
-        x_len = carry if x.dtype == torch.bfloat16 else x.shape[2]
-        return p, (x_len + 2 * conv.padding[0] - conv.kernel_size[0] + 1) // 2
-    return p, None
+                          bn.num_batches_tracked, bn.training, bn.momentum, bn.eps, conv.padding[0], gap, packed, grad, carry, nxt)
+    return p, (Lo // 2 if p.dtype == torch.bfloat16 else None)
 
 
 class TailFn(torch.autograd.Function):

@@ -62,7 +62,8 @@ def fused_forward(packer, backbone, gap, x, x_demo, proj, head, mlp0=None, mlp2=
     the fused tail, with all weight repacking done by one grouped launch."""
     blocks = list(backbone)
     linears = [proj] if x_demo is None else [proj, film_gen]
-    packs, transposed = packer.pack([b.net[0] for b in blocks], linears, torch.is_grad_enabled())
+    packs, transposed = packer.pack([b.net[0] for b in blocks], linears, torch.is_grad_enabled(), x=x,
+                                    bns=[b.net[1] for b in blocks])
     carry = None           # mixed precision only: the true row length of a bf16 activation handed from block to block
     for i, blk in enumerate(blocks):
         last = i == len(blocks) - 1

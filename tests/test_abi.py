@@ -116,6 +116,63 @@ def test_one_launch_batchnorm_backward_is_decided_per_call_from_the_parameters(m
     assert not F.bn_backward_one_launch_allowed(a.data_ptr())
 
 
+# (setting, variant) -> per T the four blocks as "<input kind>:<form>"; input kinds: f = fp32 the kernels read in place,
+# o = other fp32 (not 8-byte aligned), h = bf16 rows handed on by the block before
+_BLOCK_FORMS = {
+    ("train", "plain"): {1000: "f:fp32 f:fp32 f:fp32 f:fp32", 5000: "f:fp32 f:fp32 f:fp32 f:fp32", 12000: "f:fp32 f:fp32 f:fp32 f:fp32"},
+    ("train", "bn2_frozen"): {1000: "f:fp32 f:fp32 f:fp32 f:fp32", 5000: "f:fp32 f:fp32 f:fp32 f:fp32", 12000: "f:fp32 f:fp32 f:fp32 f:fp32"},
+    ("train", "dx0"): {1000: "f:fp32 f:fp32 f:fp32 f:fp32", 5000: "f:fp32 f:fp32 f:fp32 f:fp32", 12000: "f:fp32 f:fp32 f:fp32 f:fp32"},
+    ("train", "unaligned"): {1000: "o:fp32 f:fp32 f:fp32 f:fp32", 5000: "o:fp32 f:fp32 f:fp32 f:fp32", 12000: "o:fp32 f:fp32 f:fp32 f:fp32"},
+    ("eval", "plain"): {1000: "f:eval f:eval f:eval f:eval", 5000: "f:eval f:eval f:eval f:fp32", 12000: "f:eval f:eval f:eval f:fp32"},
+    ("eval", "unaligned"): {1000: "o:eval f:eval f:eval f:eval", 5000: "o:eval f:eval f:eval f:fp32", 12000: "o:eval f:eval f:eval f:fp32"},
+    ("bf16_train", "plain"): {1000: "f:bf16 h:bf16 h:bf16 h:bf16", 5000: "f:bf16 h:bf16 h:bf16 h:bf16", 12000: "f:bf16 h:bf16 h:bf16 h:bf16"},
+    ("bf16_train", "bn2_frozen"): {1000: "f:bf16 h:bf16 f:fp32 f:bf16", 5000: "f:bf16 h:bf16 f:fp32 f:bf16", 12000: "f:bf16 h:bf16 f:fp32 f:bf16"},
+    ("bf16_train", "dx0"): {1000: "f:fp32 f:bf16 h:bf16 h:bf16", 5000: "f:fp32 f:bf16 h:bf16 h:bf16", 12000: "f:fp32 f:bf16 h:bf16 h:bf16"},
+    ("bf16_train", "unaligned"): {1000: "o:bf16 h:bf16 h:bf16 h:bf16", 5000: "o:bf16 h:bf16 h:bf16 h:bf16", 12000: "o:bf16 h:bf16 h:bf16 h:bf16"},
+    ("bf16_eval", "plain"): {1000: "f:eval_bf16 h:eval_bf16 h:eval_bf16 h:eval_bf16", 5000: "f:eval_bf16 h:eval_bf16 h:eval_bf16 h:eval_bf16",
+                             12000: "f:eval_bf16 h:eval_bf16 h:eval_bf16 f:fp32"},
+    ("bf16_eval", "unaligned"): {1000: "o:eval f:eval f:eval f:eval", 5000: "o:eval f:eval f:eval f:fp32", 12000: "o:eval f:eval f:eval f:fp32"},
+}
+
+
+def test_block_form_table(lib):
+    """functional.block_form for the four model layers (12 -> 32 -> 64 -> 128 -> 256, K = 15, pad = 7; the last one under the
+    global average pool) at T = 1000 / 5000 / 12000: default training and evaluation, conv_precision("bf16") training,
+    inference_precision("bf16") evaluation, with the BatchNorm of block 2 frozen, an input gradient wanted on block 0, and
+    an fp32 input that is not 8-byte aligned.  The table was NOT written from block_form: it is what the predicates that
+    block_form replaced gave for these inputs at the commit before it — _bf16_block_ok, eval_bf16.takes / covered, the
+    ecg_conv1d_bn_relu_pool[_gap]_eval_supported queries and conv_block_chain's look-ahead, walked along the chain by a
+    script (all pure host calls).  The input kind of a block is part of the table: h where the block before it took a bf16
+    form AND the look-ahead said this block takes bf16 rows.  The same table pins the packer's walk of the chain
+    (_operand_kinds): bf16 operands exactly for the blocks whose form reads them."""
+    from ecg_hip import functional as F
+    ch = (12, 32, 64, 128, 256)
+    kinds = {"o": F._X_OTHER, "f": F._X_F32, "h": F._X_BF16}
+    knobs = {"train": ("fp32", "fp32", True), "eval": ("fp32", "fp32", False), "bf16_train": ("bf16", "fp32", True),
+             "bf16_eval": ("fp32", "bf16", False)}
+    for (setting, variant), per_T in _BLOCK_FORMS.items():
+        conv_prec, infer_prec, train = knobs[setting]
+        for T, want in per_T.items():
+            want, Lin = [w.split(":") for w in want.split()], T
+            # ... and the packer's walk of the chain packs what these forms read: bf16 operands where the table says a bf16
+            # form, the input-gradient operand where the block owes an input gradient
+            geo = tuple(((ch[i + 1], ch[i], 15), 7) for i in range(4))
+            packed = F._operand_kinds(geo, kinds[want[0][0]], T, tuple(train and not (variant == "bn2_frozen" and i == 2)
+                                                                       for i in range(4)), train, variant == "dx0" and train,
+                                      conv_prec, infer_prec)
+            assert packed == tuple((f in F._BF16_FORMS, train and (i > 0 or variant == "dx0")) for i, (_, f) in enumerate(want))
+            for i, (kind, form) in enumerate(want):
+                batch = train and not (variant == "bn2_frozen" and i == 2)
+                need_dx = train and (i > 0 or variant == "dx0")
+                ask = lambda k: F.block_form(ch[i], ch[i + 1], 15, 7, Lin, i == 3, kinds[k], batch, train, need_dx,   # noqa: E731
+                                             conv_prec, infer_prec)
+                assert ask(kind) == form, (setting, variant, T, i, ask(kind), form)
+                if i:       # the look-ahead of the block before: this block asked with bf16 rows
+                    handed = want[i - 1][1] in F._BF16_FORMS and ask("h") in F._BF16_FORMS
+                    assert handed == (kind == "h"), (setting, variant, T, i)
+                Lin //= 2
+
+
 def test_library_reads_no_environment_and_allocates_nothing():
     """include/ecg_hip.h: "never allocates", "no global mutable state", "reads no environment variable" — checked on the
     dynamic symbol table of the built library (what it would have to import to break the promise)."""

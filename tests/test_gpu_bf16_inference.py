@@ -317,6 +317,31 @@ def test_bf16_activation_into_a_block_that_cannot_take_it_still_raises(hip):
             F.conv_block_chain(p, blocks[1].net[0], blocks[1].net[1], carry=carry)
 
 
+@pytest.mark.parametrize("case", [("fp32_train", 2, 1000), ("bf16_infer", 2, 1000), ("bf16_infer", 2, 12000),
+                                  ("bf16_train_bn2_eval", 6, 1000)], ids=lambda c: f"{c[0]}_B{c[1]}_T{c[2]}")
+def test_one_repack_launch_per_fused_forward(hip, case):
+    """The model's packer packs exactly what each block reads: one grouped repack per forward and no per-layer repack out
+    of ConvBlockFn._weights — also where blocks of one chain take different forms: T = 12000 under bf16 inference (block 3's
+    row of 1500 exceeds the 1280-step tile of the one-launch global average: fp32 operands for it alone) and a bf16
+    training step with the BatchNorm of block 2 in eval mode (fp32 operands for block 2 alone)."""
+    from ecg_hip import functional as F
+    kind, B, T = case
+    m = _model("cnn5").to(DEV)
+    x = R.synthetic_batch(B, T, 5)[0].to(DEV)
+    if kind == "bf16_infer":
+        with torch.no_grad(), F.inference_precision("bf16"):
+            _, names = _launches(hip, lambda: m(x))
+    else:
+        m.train()
+        if kind == "bf16_train_bn2_eval":
+            m.backbone[2].net[1].eval()
+        with F.conv_precision("bf16" if kind.startswith("bf16") else "fp32"):
+            _, names = _launches(hip, lambda: m(x))
+    grouped = [n for n in names if n in ("ecg_pack_weights_grouped", "ecg_pack_weights_grouped_mixed")]
+    assert len(grouped) == 1, names
+    assert "ecg_conv1d_pack_weights" not in names and "ecg_conv1d_pack_weights_bf16" not in names, names
+
+
 # ---- determinism -----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("T", [1000, 5000])
 def test_bitwise_deterministic_and_batch_independent(hip, T):
