@@ -517,6 +517,24 @@ int ecg_wfdb16_zscore(const int16_t *d, const double *gain, const int *baseline,
 /* Per-lead z-score, (x-mean)/(std+1e-6) with population std.  x [rows][T] -> out [rows][T] (in place
  * allowed); stats [rows][2] receives (mean, std + 1e-6) per row. */
 int ecg_zscore_rows(const float *x, float *out, float *stats, int rows, int T, ecg_stream_t stream);
+/* The same step for CONTINUOUS recordings d [R][Ttot][leads], read in place: window w of recording r starts at sample
+ * first + w*hop — or at last_start when last_start >= 0 and w == W-1 (the "shifted tail" window that ends with the
+ * recording; -1: none).  gain / baseline [R][leads]; out [R][W][leads][T]; stats [R*W*leads][2], or NULL to stop at the
+ * physical signal.  Window (r, w) is bit-identical to ecg_wfdb16_zscore / ecg_wfdb16_physical on a copy of its slice: the
+ * two entry points above are the Ttot == T, W == 1 callers of the same kernels.  Starts are arbitrary sample indices (the
+ * source is read as int16).  ECG_EINVAL before any launch unless hop >= 1, W >= 1, 1 <= T <= Ttot, every start lies in
+ * [0, Ttot-T], leads in [1,16], R*W <= 65535 (and R*W*leads <= 65535 where the window does not fit the fused kernel). */
+int ecg_wfdb16_windows(const int16_t *d, const double *gain, const int *baseline, float *out, float *stats,
+                       int R, int Ttot, int leads, int T, int first, int hop, int W, int last_start,
+                       ecg_stream_t stream);
+/* Per-window time series back onto the recording's axis: v [R][W][K][T] (K series per window, windows placed by the
+ * rule above) -> out [R][K][Ttot], the mean over the windows that cover a sample:
+ *     acc = 0.0f;  for w ascending with start(w) <= t < start(w)+T:  acc = acc + v[r][w][k][t - start(w)]
+ *     out[r][k][t] = acc / (float)count      (0 where no window covers t)
+ * One lane owns one output and adds in that order — no atomics, reproducible bit for bit.  cover [Ttot] (nullable)
+ * receives the count.  Same argument checks; R*K <= 65535. */
+int ecg_windows_overlap_mean(const float *v, float *out, float *cover, int R, int K, int T, int Ttot,
+                             int first, int hop, int W, int last_start, ecg_stream_t stream);
 /* HOST side of the same step — what torch's DataLoader collate does for the reference (one `Dataset.__getitem__` per record,
  * src/datasets/ptbxl.py:25,122-127, stacked into a batch): rows `rows[0..n)` of a row-major host table (row_bytes each, e.g.
  * the int16 records of a memory-mapped pack) copied to consecutive rows of `dst` (the pinned staging slot).  Plain memcpy

@@ -33,21 +33,44 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int kTT = 256;        // time samples per transpose tile
 constexpr int kMaxLeads = 16;
 
+// Where the windows of a launch lie in their recordings d [R][Ttot][leads]: window b = r*W + w of the
+// grid starts at sample first + w*hop of recording r — or at last_start when that is >= 0 and w is the
+// last window (the "shifted tail" that ends with the recording).  Pre-cut windows [B][T][leads] are the
+// case Ttot == T, W == 1.  A start is any sample index: the source is only ever read as int16.
+struct WindowSrc {
+    long long Ttot;
+    int W, first, hop, last_start;
+};
+
+__device__ __forceinline__ long long window_start(const WindowSrc &s, int w) {
+    return (s.last_start >= 0 && w == s.W - 1) ? (long long)s.last_start : s.first + (long long)w * s.hop;
+}
+
+// -> recording index r (gain / baseline row); src = first sample of the window
+__device__ __forceinline__ int window_source(const WindowSrc &s, int b, int leads, const int16_t *d,
+                                             const int16_t *&src) {
+    const int r = b / s.W;
+    src = d + ((size_t)r * s.Ttot + window_start(s, b - r * s.W)) * leads;
+    return r;
+}
+
 __global__ __launch_bounds__(256) void wfdb16_physical_kernel(
     const int16_t *__restrict__ d, const double *__restrict__ gain, const int *__restrict__ baseline,
-    float *__restrict__ out, int T, int leads) {
+    float *__restrict__ out, int T, int leads, WindowSrc ws) {
     __shared__ int16_t tile[kTT * kMaxLeads];
     const int b = blockIdx.y, t0 = blockIdx.x * kTT, tid = threadIdx.x;
     const int nt = min(kTT, T - t0);
-    const int16_t *src = d + ((size_t)b * T + t0) * leads;     // nt*leads contiguous samples
+    const int16_t *src;
+    const int r = window_source(ws, b, leads, d, src);
+    src += (size_t)t0 * leads;                                  // nt*leads contiguous samples
     const int count = nt * leads;
     for (int e = tid; e < count; e += 256) tile[e] = src[e];
     __syncthreads();
     if (tid < nt) {
         for (int l = 0; l < leads; ++l) {
             const int v = tile[tid * leads + l];
-            const double g = gain[(size_t)b * leads + l];
-            const int base = baseline[(size_t)b * leads + l];
+            const double g = gain[(size_t)r * leads + l];
+            const int base = baseline[(size_t)r * leads + l];
             // format 16 reserves -32768 as "invalid sample": wfdb returns NaN for it
             const float p = (v == -32768) ? __builtin_nanf("") : (float)((double)(v - base) / g);
             out[((size_t)b * leads + l) * T + t0 + tid] = p;
@@ -137,19 +160,21 @@ __device__ __forceinline__ void row_stats_vec(const float *__restrict__ r, int T
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void wfdb16_zscore_fused_kernel(
     const int16_t *__restrict__ d, const double *__restrict__ gain, const int *__restrict__ baseline,
-    float *__restrict__ out, float *__restrict__ stats, int T, int leads, int G, int Tpad) {
+    float *__restrict__ out, float *__restrict__ stats, int T, int leads, int G, int Tpad, WindowSrc ws) {
     extern __shared__ __attribute__((aligned(16))) float phys[];      // [G][Tpad] (+ 2*G stats behind)
     const int b = blockIdx.y, l0 = blockIdx.x * G, tid = threadIdx.x;
     const int nl = min(G, leads - l0);
     float *st = phys + (size_t)G * Tpad;
     __shared__ double sg[kMaxLeads];
     __shared__ int sb[kMaxLeads];
+    const int16_t *src;
+    const int r = window_source(ws, b, leads, d, src);
+    src += l0;
     if (tid < nl) {
-        sg[tid] = gain[(size_t)b * leads + l0 + tid];
-        sb[tid] = baseline[(size_t)b * leads + l0 + tid];
+        sg[tid] = gain[(size_t)r * leads + l0 + tid];
+        sb[tid] = baseline[(size_t)r * leads + l0 + tid];
     }
     __syncthreads();
-    const int16_t *src = d + (size_t)b * T * leads + l0;
     for (int t = tid; t < T; t += 256) {               // thread <-> time sample: nl consecutive int16
         const int16_t *p = src + (size_t)t * leads;
         for (int l = 0; l < nl; ++l) {
@@ -239,20 +264,41 @@ __global__ __launch_bounds__(256) void zscore_apply_kernel(const float *__restri
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// Overlap mean: per-window time series v [R][W][K][T] back onto the recording's axis, out [R][K][Ttot].
+// Gather form — one lane owns one output sample and adds the windows that cover it in ascending w, so
+// the fp32 sum has ONE order (no atomics) and a numpy loop reproduces it bit for bit.  The windows
+// over t follow from the window rule: the regular ones are w in [ceil((t-first-T+1)/hop),
+// floor((t-first)/hop)], then the shifted tail (the last index).  Loads of one w are coalesced along t.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void windows_overlap_mean_kernel(const float *__restrict__ v,
+                                                                  float *__restrict__ out,
+                                                                  float *__restrict__ cover, int K, int T,
+                                                                  WindowSrc ws) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= ws.Ttot) return;
+    const int rk = blockIdx.y, r = rk / K, k = rk - r * K;
+    const int wreg = ws.last_start >= 0 ? ws.W - 1 : ws.W;        // windows on the first + w*hop lattice
+    const long long rel = t - ws.first;
+    long long lo = rel - T + 1 <= 0 ? 0 : (rel - T + ws.hop) / ws.hop;
+    long long hi = rel < 0 ? -1 : rel / ws.hop;
+    if (hi > wreg - 1) hi = wreg - 1;
+    const float *vr = v + ((size_t)r * ws.W * K + k) * T;         // (r, w = 0, k); one w further: K*T floats
+    float acc = 0.f;
+    int n = 0;
+    for (long long w = lo; w <= hi; ++w, ++n)
+        acc = acc + vr[(size_t)w * K * T + (size_t)(rel - w * ws.hop)];
+    if (ws.last_start >= 0 && t >= ws.last_start && t < (long long)ws.last_start + T) {
+        acc = acc + vr[(size_t)(ws.W - 1) * K * T + (size_t)(t - ws.last_start)];
+        ++n;
+    }
+    out[(size_t)rk * ws.Ttot + t] = n ? acc / (float)n : 0.f;
+    if (cover && rk == 0) cover[t] = (float)n;
+}
+
 }  // namespace ecg
 
 using namespace ecg;
-
-ECG_API int ecg_wfdb16_physical(const int16_t *d, const double *gain, const int *baseline, float *out,
-                                int B, int T, int leads, ecg_stream_t stream) {
-    ECG_REQUIRE(d && gain && baseline && out, "wfdb16_physical: null pointer");
-    ECG_REQUIRE(B > 0 && T > 0, "wfdb16_physical: B=%d T=%d must be > 0", B, T);
-    ECG_REQUIRE(leads >= 1 && leads <= kMaxLeads, "wfdb16_physical: leads=%d outside [1,%d]", leads, kMaxLeads);
-    ECG_REQUIRE(B <= 65535, "wfdb16_physical: B=%d exceeds grid.y limit 65535", B);
-    hipLaunchKernelGGL(wfdb16_physical_kernel, dim3(cdiv(T, kTT), B), dim3(256), 0, as_stream(stream), d,
-                       gain, baseline, out, T, leads);
-    return check_launch("wfdb16_physical_kernel");
-}
 
 ECG_API int ecg_zscore_rows(const float *x, float *out, float *stats, int rows, int T,
                             ecg_stream_t stream) {
@@ -273,14 +319,29 @@ ECG_API int ecg_zscore_rows(const float *x, float *out, float *stats, int rows, 
     return check_launch("zscore_apply_kernel");
 }
 
-// Fused int16 -> z-scored fp32 (the LDS-resident kernel above) when a whole window fits in LDS,
-// otherwise the three streaming launches.  stats [B*leads][2] receives (mean, std + 1e-6).
-ECG_API int ecg_wfdb16_zscore(const int16_t *d, const double *gain, const int *baseline, float *out,
-                              float *stats, int B, int T, int leads, ecg_stream_t stream) {
-    ECG_REQUIRE(d && gain && baseline && out && stats, "wfdb16_zscore: null pointer");
-    ECG_REQUIRE(B > 0 && T > 0, "wfdb16_zscore: B=%d T=%d must be > 0", B, T);
-    ECG_REQUIRE(leads >= 1 && leads <= kMaxLeads, "wfdb16_zscore: leads=%d outside [1,%d]", leads, kMaxLeads);
-    ECG_REQUIRE(B <= 65535, "wfdb16_zscore: B=%d exceeds grid.y limit 65535", B);
+// The window rule on the host: every start inside [0, Ttot - T], checked before any launch.
+static int check_windows(const char *who, int R, int Ttot, int T, int first, int hop, int W, int last_start) {
+    ECG_REQUIRE(R > 0 && T > 0, "%s: R=%d T=%d must be > 0", who, R, T);
+    ECG_REQUIRE(hop >= 1 && W >= 1, "%s: hop=%d W=%d must be >= 1", who, hop, W);
+    ECG_REQUIRE(T <= Ttot, "%s: window T=%d longer than the recording Ttot=%d", who, T, Ttot);
+    ECG_REQUIRE(last_start >= -1 && last_start <= Ttot - T, "%s: last_start=%d outside [-1, Ttot-T=%d]", who,
+                last_start, Ttot - T);
+    const int wreg = last_start >= 0 ? W - 1 : W;       // windows on the first + w*hop lattice
+    ECG_REQUIRE(first >= 0, "%s: first=%d must be >= 0", who, first);
+    ECG_REQUIRE(wreg == 0 || first + (long long)(wreg - 1) * hop <= Ttot - T,
+                "%s: window %d starts at %lld, past Ttot-T=%d", who, wreg - 1, first + (long long)(wreg - 1) * hop,
+                Ttot - T);
+    return ECG_OK;
+}
+
+// One plan for pre-cut windows and for windows read in place out of recordings: the fused int16 -> z-scored
+// fp32 kernel when a whole window fits in LDS, otherwise the three streaming launches; stats == NULL stops
+// at the physical signal.  NW = R*W windows.
+static int wfdb16_windows_launch(const char *who, const int16_t *d, const double *gain, const int *baseline, float *out,
+                                 float *stats, int R, int T, int leads, const WindowSrc &ws, ecg_stream_t stream) {
+    ECG_REQUIRE(leads >= 1 && leads <= kMaxLeads, "%s: leads=%d outside [1,%d]", who, leads, kMaxLeads);
+    const long long NW = (long long)R * ws.W;
+    ECG_REQUIRE(NW <= 65535, "%s: %lld windows exceed grid.y limit 65535", who, NW);
     int Tpad = (T + 3) / 4 * 4;
     Tpad += (4 - Tpad % 64 + 64) % 64;                 // row stride == 4 (mod 64 banks)
     const size_t row_bytes = (size_t)Tpad * 4;
@@ -289,16 +350,55 @@ ECG_API int ecg_wfdb16_zscore(const int16_t *d, const double *gain, const int *b
     // split the leads over workgroups; LDS then caps the rows resident per CU below what the chains
     // need to overlap (12x5000: 220 us fused with 3 leads per workgroup vs 138 us streamed), so they
     // take the three streaming launches instead.
-    const int G = (row_bytes * leads + (size_t)leads * 8 <= 64u * 1024u) ? leads : 0;
+    const int G = (stats && row_bytes * leads + (size_t)leads * 8 <= 64u * 1024u) ? leads : 0;
     if (G == 0) {
-        int rc = ecg_wfdb16_physical(d, gain, baseline, out, B, T, leads, stream);
-        if (rc) return rc;
-        ECG_REQUIRE((long long)B * leads <= 65535, "wfdb16_zscore: B*leads=%lld exceeds 65535 rows for T=%d",
-                    (long long)B * leads, T);
-        return ecg_zscore_rows(out, out, stats, B * leads, T, stream);
+        ECG_REQUIRE(!stats || NW * leads <= 65535, "%s: windows*leads=%lld exceeds 65535 rows for T=%d", who, NW * leads, T);
+        hipLaunchKernelGGL(wfdb16_physical_kernel, dim3(cdiv(T, kTT), (int)NW), dim3(256), 0, as_stream(stream), d,
+                           gain, baseline, out, T, leads, ws);
+        int rc = check_launch("wfdb16_physical_kernel");
+        if (rc || !stats) return rc;
+        return ecg_zscore_rows(out, out, stats, (int)NW * leads, T, stream);
     }
     const size_t lds = (size_t)G * row_bytes + (size_t)G * 2 * sizeof(float);
-    hipLaunchKernelGGL(wfdb16_zscore_fused_kernel, dim3(cdiv(leads, G), B), dim3(256), lds, as_stream(stream), d,
-                       gain, baseline, out, stats, T, leads, G, Tpad);
+    hipLaunchKernelGGL(wfdb16_zscore_fused_kernel, dim3(cdiv(leads, G), (int)NW), dim3(256), lds, as_stream(stream), d,
+                       gain, baseline, out, stats, T, leads, G, Tpad, ws);
     return check_launch("wfdb16_zscore_fused_kernel");
+}
+
+ECG_API int ecg_wfdb16_physical(const int16_t *d, const double *gain, const int *baseline, float *out,
+                                int B, int T, int leads, ecg_stream_t stream) {
+    ECG_REQUIRE(d && gain && baseline && out, "wfdb16_physical: null pointer");
+    ECG_REQUIRE(B > 0 && T > 0, "wfdb16_physical: B=%d T=%d must be > 0", B, T);
+    return wfdb16_windows_launch("wfdb16_physical", d, gain, baseline, out, nullptr, B, T, leads,
+                                 WindowSrc{T, 1, 0, 1, -1}, stream);
+}
+
+ECG_API int ecg_wfdb16_zscore(const int16_t *d, const double *gain, const int *baseline, float *out,
+                              float *stats, int B, int T, int leads, ecg_stream_t stream) {
+    ECG_REQUIRE(d && gain && baseline && out && stats, "wfdb16_zscore: null pointer");
+    ECG_REQUIRE(B > 0 && T > 0, "wfdb16_zscore: B=%d T=%d must be > 0", B, T);
+    return wfdb16_windows_launch("wfdb16_zscore", d, gain, baseline, out, stats, B, T, leads,
+                                 WindowSrc{T, 1, 0, 1, -1}, stream);
+}
+
+ECG_API int ecg_wfdb16_windows(const int16_t *d, const double *gain, const int *baseline, float *out, float *stats,
+                               int R, int Ttot, int leads, int T, int first, int hop, int W, int last_start,
+                               ecg_stream_t stream) {
+    ECG_REQUIRE(d && gain && baseline && out, "wfdb16_windows: null pointer");
+    int rc = check_windows("wfdb16_windows", R, Ttot, T, first, hop, W, last_start);
+    if (rc) return rc;
+    return wfdb16_windows_launch("wfdb16_windows", d, gain, baseline, out, stats, R, T, leads,
+                                 WindowSrc{Ttot, W, first, hop, last_start}, stream);
+}
+
+ECG_API int ecg_windows_overlap_mean(const float *v, float *out, float *cover, int R, int K, int T, int Ttot,
+                                     int first, int hop, int W, int last_start, ecg_stream_t stream) {
+    ECG_REQUIRE(v && out, "windows_overlap_mean: null pointer");
+    ECG_REQUIRE(K >= 1, "windows_overlap_mean: K=%d must be >= 1", K);
+    int rc = check_windows("windows_overlap_mean", R, Ttot, T, first, hop, W, last_start);
+    if (rc) return rc;
+    ECG_REQUIRE((long long)R * K <= 65535, "windows_overlap_mean: R*K=%lld exceeds grid.y limit 65535", (long long)R * K);
+    hipLaunchKernelGGL(windows_overlap_mean_kernel, dim3(cdiv(Ttot, 256), R * K), dim3(256), 0, as_stream(stream), v, out,
+                       cover, K, T, WindowSrc{Ttot, W, first, hop, last_start});
+    return check_launch("windows_overlap_mean_kernel");
 }

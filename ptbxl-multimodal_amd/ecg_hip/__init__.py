@@ -7,6 +7,7 @@ one-collective-per-step data-parallel wrapper.  CUDA(HIP) tensors always take th
 (a missing shared library raises `EcgHipError`, never a silent fallback); CPU tensors take the
 stock torch layers the modules inherit from, as the reference does on a GPU-less box.
 `ecg_hip.grad_cam` is batched Grad-CAM at the last Conv1d: a closed form on the GPU, the hook algorithm elsewhere.
+`ecg_hip.score_recording` scores a continuous recording of any length: sliding windows read in place, stitched CAMs.
 """
 from ._lib import EcgHipError, LIB_PATH, load  # noqa: F401
 
@@ -17,4 +18,10 @@ def grad_cam(*args, **kwargs):
     return _grad_cam(*args, **kwargs)
 
 
-__all__ = ["EcgHipError", "LIB_PATH", "load", "grad_cam"]
+def score_recording(*args, **kwargs):
+    """ecg_hip.recording.score_recording (imported on first use, as grad_cam)."""
+    from .recording import score_recording as _score_recording
+    return _score_recording(*args, **kwargs)
+
+
+__all__ = ["EcgHipError", "LIB_PATH", "load", "grad_cam", "score_recording"]

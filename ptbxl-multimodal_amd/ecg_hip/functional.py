@@ -896,4 +896,53 @@ def wfdb16_to_windows(d, gain, baseline, normalize=True, return_stats=False):
     return (x, stats) if return_stats else x
 
 
+def wfdb16_windows(d, gain, baseline, window, first, hop, W, last_start=-1, normalize=True, return_stats=False):
+    """Windows read IN PLACE out of continuous recordings d int16 [R, Ttot, leads] (gain float64 / baseline int32
+    [R, leads]): window w of every recording starts at sample first + w*hop, the last one at `last_start` when that is
+    >= 0.  -> fp32 [R, W, leads, window], each window bit-identical to wfdb16_to_windows on a copy of its slice
+    (stats [R*W*leads, 2] likewise).  The raw form under wfdb16_to_windows_sliding, for callers that chunk a plan."""
+    if d.dtype != torch.int16 or gain.dtype != torch.float64 or baseline.dtype != torch.int32:
+        raise L.EcgHipError("wfdb16_windows: d must be int16, gain float64, baseline int32")
+    if d.dim() != 3:
+        raise L.EcgHipError("wfdb16_windows: d must be [R, Ttot, leads]")
+    d, gain, baseline = _contig(d), _contig(gain), _contig(baseline)
+    R, Ttot, leads = d.shape
+    if tuple(gain.shape) != (R, leads) or tuple(baseline.shape) != (R, leads):
+        raise L.EcgHipError("wfdb16_windows: gain/baseline must be [R, leads]")
+    x = torch.empty(R, W, leads, window, dtype=torch.float32, device=d.device)
+    stats = _empty(x, R * W * leads, 2) if normalize else None
+    _call("ecg_wfdb16_windows", L.ptr(d), L.ptr(gain), L.ptr(baseline), _f32(x), _f32(stats), R, Ttot, leads, int(window),
+          int(first), int(hop), int(W), int(last_start), _st())
+    return (x, stats) if normalize and return_stats else x
+
+
+def wfdb16_to_windows_sliding(d, gain, baseline, window, hop, tail="shift", normalize=True, return_stats=False):
+    """wfdb16_to_windows for recordings longer than one window: d int16 [R, Ttot, leads] is cut into the windows of
+    recording.window_plan(Ttot, window, hop, tail) without an overlapping copy ever existing.
+    -> (x [R, W, leads, window], plan), or (x, stats, plan) with return_stats."""
+    from .recording import window_plan
+    if d.dim() != 3:
+        raise L.EcgHipError("wfdb16_to_windows_sliding: d must be [R, Ttot, leads]")
+    plan = window_plan(d.shape[1], window, hop, tail)
+    first, hop, W, last_start, _ = plan
+    out = wfdb16_windows(d, gain, baseline, window, first, hop, W, last_start, normalize, return_stats)
+    return (*out, plan) if isinstance(out, tuple) else (out, plan)
+
+
+def overlap_mean(v, plan, Ttot, return_cover=False):
+    """Per-window time series v fp32 [R, W, K, T] (windows placed by `plan`, a window_plan result) -> [R, K, Ttot]: at
+    every sample the mean of the windows that cover it, added in ascending window order by the one lane that owns the
+    sample (reproducible bit for bit; 0 where nothing covers).  return_cover: also the count per sample, fp32 [Ttot]."""
+    first, hop, W, last_start, _ = plan
+    if v.dim() != 4 or v.shape[1] != W:
+        raise L.EcgHipError(f"overlap_mean: v must be [R, W={W}, K, T], got {tuple(v.shape)}")
+    v = _contig(v)
+    R, _, K, T = v.shape
+    out = _empty(v, R, K, Ttot)
+    cover = _empty(v, Ttot) if return_cover else None
+    _call("ecg_windows_overlap_mean", _f32(v), _f32(out), _f32(cover), R, K, T, int(Ttot), int(first), int(hop), int(W),
+          int(last_start), _st())
+    return (out, cover) if return_cover else out
+
+
 from .leaves import BatchNormFn, Conv1dFn, FilmFn, GapFn, LinearFn, MaxPool2Fn, ReLUFn  # noqa: E402,F401

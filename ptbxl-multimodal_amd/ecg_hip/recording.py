@@ -1,0 +1,161 @@
+"""Scoring a continuous recording: any WFDB format-16 signal longer than one training window (a rhythm strip, a Holter
+export) -> per-window logits, record-level probabilities and Grad-CAMs on the recording's own time axis.
+
+The recording stays on the device as the int16 samples of its .dat file.  `ecg_wfdb16_windows` cuts the z-scored windows
+straight out of it (no overlapping copy), the windows go through the model's eval forward (or `ecg_hip.grad_cam`) in chunks
+of at most `batch_size`, and `ecg_windows_overlap_mean` averages the per-window CAMs where windows overlap.
+
+Window rule (shared with the C ABI): window w starts at sample first + w*hop; with tail="shift" a recording whose length
+is not first + k*hop + window gets one more window that ENDS with the recording (start Ttot - window), so that every
+sample is scored; tail="drop" leaves the remainder unscored.
+"""
+import torch
+
+from . import _lib as L
+from . import functional as hipF
+
+
+def window_plan(Ttot, window, hop, tail="shift"):
+    """-> (first, hop, W, last_start, starts): the arguments of ecg_wfdb16_windows / ecg_windows_overlap_mean for a recording
+    of Ttot samples, and the W start samples as a tuple.  last_start is -1 when there is no shifted tail window."""
+    Ttot, window, hop = int(Ttot), int(window), int(hop)
+    if tail not in ("shift", "drop"):
+        raise ValueError(f"tail={tail!r}: 'shift' or 'drop'")
+    if window < 1 or hop < 1:
+        raise ValueError(f"window={window} and hop={hop} must be >= 1")
+    if Ttot < window:
+        raise ValueError(f"the recording has {Ttot} samples, fewer than one window of {window}")
+    W = (Ttot - window) // hop + 1
+    starts = [w * hop for w in range(W)]
+    last_start = -1
+    if tail == "shift" and (Ttot - window) % hop != 0:
+        last_start = Ttot - window
+        starts.append(last_start)
+        W += 1
+    return 0, hop, W, last_start, tuple(starts)
+
+
+def plan_chunks(R, plan, batch_size):
+    """The calls one plan is scored in, as (r0, r1, w0, first, W, last_start): recordings r0..r1 and their windows
+    w0..w0+W of the plan, cut by (first, hop, W, last_start).  More windows per recording than batch_size: one recording
+    per call, chunked over w, the shifted tail only in the chunk that holds the final window.  Otherwise batch_size // W
+    whole recordings per call."""
+    first, hop, W, last_start, _ = plan
+    if batch_size < 1:
+        raise ValueError(f"batch_size={batch_size}")
+    if W > batch_size:
+        return [(r, r + 1, w0, first + w0 * hop, min(batch_size, W - w0), last_start if w0 + batch_size >= W else -1)
+                for r in range(R) for w0 in range(0, W, batch_size)]
+    g = batch_size // W
+    return [(r0, min(R, r0 + g), 0, first, W, last_start) for r0 in range(0, R, g)]
+
+
+class RecordingScore:
+    """starts (W start samples); logits, prob [R, W, C]; finite [R, W]; prob_max, prob_mean [R, C] over the finite windows
+    (NaN where a recording has none); with CAMs: cam [R, K, Ttot], cover [Ttot] (windows over each sample)."""
+    __slots__ = ("starts", "logits", "prob", "finite", "prob_max", "prob_mean", "cam", "cover")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def _record_level(prob, finite):
+    """amax / mean of prob [R, W, C] over the windows flagged finite, as torch computes them on those windows."""
+    pmax, pmean = prob.amax(1), prob.mean(1)
+    for r in torch.nonzero(~finite.all(1)).flatten().tolist():
+        sel = prob[r][finite[r]]
+        if sel.shape[0]:
+            pmax[r], pmean[r] = sel.amax(0), sel.mean(0)
+        else:
+            pmax[r], pmean[r] = float("nan"), float("nan")
+    return pmax, pmean
+
+
+def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift", batch_size=256, x_demo=None,
+                    cam_classes=None, cam_normalize=None):
+    """Score recordings d int16 [Ttot, leads] or [R, Ttot, leads] (on the GPU, the .dat layout) with `model` in eval mode.
+
+    gain float64 / baseline int32 [leads] or [R, leads]; window: samples per model input; hop: default window // 2;
+    tail: see window_plan; x_demo [R, D] (ECGMultimodal) is repeated for every window of its recording.
+    Windows are produced and consumed in chunks of at most batch_size (plan_chunks), through `model(x)` under the caller's
+    inference_precision — or, with cam_classes (a list of class indices), through ecg_hip.grad_cam(class_idx=cam_classes,
+    signal_length=window, normalize=None), whose logits are used.  The raw per-window CAMs are stitched by overlap_mean;
+    cam_normalize="record" then min-max normalises every (recording, class) row over its covered samples (divided only
+    where the maximum is > 0).  The CAM path keeps K x W x window floats per recording until the stitch.
+
+    `finite[r, w]` is False when a logit of the window is not finite or the window holds an invalid sample (-32768, a
+    NaN lead): the fused eval blocks take max(., 0) after BatchNorm, which drops a NaN, so such a window has finite but
+    meaningless logits and is kept out of prob_max / prob_mean by its input statistics.
+    -> RecordingScore."""
+    if not (torch.is_tensor(d) and d.is_cuda):
+        raise L.EcgHipError("score_recording: a CPU tensor reached the HIP input step; d must be on the GPU "
+                            "(there is no CPU form of the sliding input step)")
+    if model.training:
+        raise ValueError("score_recording needs model.eval()")
+    if cam_normalize not in (None, "record"):
+        raise ValueError(f"cam_normalize={cam_normalize!r}: None or 'record'")
+    if d.dim() == 2:
+        d = d[None]
+    if d.dim() != 3:
+        raise L.EcgHipError("score_recording: d must be [Ttot, leads] or [R, Ttot, leads]")
+    R, Ttot, leads = d.shape
+    dev = d.device
+    gain = torch.as_tensor(gain, dtype=torch.float64).to(dev).reshape(-1, leads)
+    baseline = torch.as_tensor(baseline, dtype=torch.int32).to(dev).reshape(-1, leads)
+    if gain.shape[0] != R or baseline.shape[0] != R:
+        raise L.EcgHipError("score_recording: gain/baseline must be [leads] or [R, leads]")
+    if x_demo is not None and x_demo.shape[0] != R:
+        raise ValueError(f"x_demo has {x_demo.shape[0]} rows for {R} recordings")
+    window = int(window)
+    plan = window_plan(Ttot, window, window // 2 if hop is None else hop, tail)
+    _, hop, W, _, starts = plan
+    cams = None if cam_classes is None else [int(k) for k in cam_classes]
+    d = hipF._contig(d)
+
+    logits = v = None
+    ok = torch.empty(R, W, dtype=torch.bool, device=dev)
+    for r0, r1, w0, first, Wc, last in plan_chunks(R, plan, int(batch_size)):
+        x, stats = hipF.wfdb16_windows(d[r0:r1], gain[r0:r1], baseline[r0:r1], window, first, hop, Wc, last,
+                                       return_stats=True)
+        n = (r1 - r0) * Wc
+        x = x.view(n, leads, window)
+        xd = None if x_demo is None else x_demo[r0:r1].repeat_interleave(Wc, dim=0)
+        if cams is None:
+            with torch.no_grad():
+                lg = model(x) if xd is None else model(x, xd)
+        else:       # (not under no_grad: where the fused path does not apply, grad_cam differentiates the logits)
+            from .gradcam import grad_cam
+            cam, lg = grad_cam(model, x, xd, class_idx=cams, signal_length=window, normalize=None, return_logits=True)
+            if v is None:
+                v = hipF._empty(x, R, W, len(cams), window)
+            v[r0:r1, w0:w0 + Wc] = cam.reshape(r1 - r0, Wc, len(cams), window)
+        if logits is None:
+            logits = hipF._empty(x, R, W, lg.shape[1])
+        logits[r0:r1, w0:w0 + Wc] = lg.reshape(r1 - r0, Wc, -1)
+        ok[r0:r1, w0:w0 + Wc] = torch.isfinite(stats).view(r1 - r0, Wc, -1).all(-1)
+    finite = ok & torch.isfinite(logits).all(-1)
+    prob = hipF.sigmoid(logits)
+    pmax, pmean = _record_level(prob, finite)
+    cam = cover = None
+    if cams is not None:
+        cam, cover = hipF.overlap_mean(v, plan, Ttot, return_cover=True)
+        if cam_normalize == "record":
+            covered = (cover > 0)[None, None, :]
+            big = torch.finfo(cam.dtype).max
+            c = cam - torch.where(covered, cam, cam.new_full((), big)).amin(-1, keepdim=True)
+            mx = torch.where(covered, c, cam.new_full((), -big)).amax(-1, keepdim=True)
+            c = torch.where(mx > 0, c / torch.where(mx > 0, mx, torch.ones_like(mx)), c)
+            cam = torch.where(covered, c, torch.zeros_like(c))
+    return RecordingScore(starts=starts, logits=logits, prob=prob, finite=finite, prob_max=pmax, prob_mean=pmean,
+                          cam=cam, cover=cover)
+
+
+def score_wfdb_record(record_path, model, **kw):
+    """score_recording for a WFDB format-16 record of any length on disk (record_path without extension, as
+    ecg_hip.wfdb16.read_record takes it): the samples are uploaded once, as int16, to the device of the model."""
+    from .wfdb16 import read_record
+    rec = read_record(record_path)
+    dev = next(model.parameters()).device
+    return score_recording(model, torch.from_numpy(rec.d.astype("int16")).to(dev), torch.from_numpy(rec.gain).to(dev),
+                           torch.from_numpy(rec.baseline).to(dev), **kw)
