@@ -527,6 +527,24 @@ int ecg_zscore_rows(const float *x, float *out, float *stats, int rows, int T, e
 int ecg_wfdb16_windows(const int16_t *d, const double *gain, const int *baseline, float *out, float *stats,
                        int R, int Ttot, int leads, int T, int first, int hop, int W, int last_start,
                        ecg_stream_t stream);
+/* The same step for recordings sampled at ANOTHER RATE than the model's: a polyphase FIR resampler by up/down between the
+ * DAC conversion and the z-score.  With p[k] the physical sample as above (-32768 -> NaN) the resampled recording y has
+ * Tout = ceil(Ttot*up/down) samples (64-bit),
+ *     M = n*down + half (64-bit);  phi = M mod up;  k0 = M div up
+ *     acc = 0.0f;  for i = 0 .. ntap-1 ascending:  acc = acc + taps[phi][i] * p[clamp(k0 - i, 0, Ttot-1)]
+ *     y[n] = acc
+ * every product and every sum a separately rounded fp32 operation, all ntap terms added (zero taps included), the
+ * recording's ends edge-held by the clamp: y[n] depends on n and the recording only, never on the window that asks.
+ * Windows are then placed on y by the rule above with Tout where Ttot stood, and z-scored with the arithmetic above
+ * (the resampling launch writes the physical windows, ecg_zscore_rows normalises them in place).
+ * taps [up][ntap] fp32 on the device, caller-owned: taps[phi][i] = h[phi + i*up] of an FIR h of length 2*half+1 (0 past
+ * its end); ecg_hip/resample.py designs scipy.signal.resample_poly's default (Kaiser beta 5, half = 10*max(up, down)).
+ * out [R][W][leads][T]; stats [R*W*leads][2], or NULL to stop at the physical signal.  ECG_EINVAL before any launch
+ * unless up, down in [1,512], ntap in [1,256], half >= 0, ntap*up >= 2*half+1, leads in [1,16], the window rule holds
+ * against Tout, R*W <= 65535 (R*W*leads <= 65535 with stats). */
+int ecg_wfdb16_windows_resampled(const int16_t *d, const double *gain, const int *baseline, const float *taps,
+                                 float *out, float *stats, int R, int Ttot, int leads, int T, int first, int hop,
+                                 int W, int last_start, int up, int down, int ntap, int half, ecg_stream_t stream);
 /* Per-window time series back onto the recording's axis: v [R][W][K][T] (K series per window, windows placed by the
  * rule above) -> out [R][K][Ttot], the mean over the windows that cover a sample:
  *     acc = 0.0f;  for w ascending with start(w) <= t < start(w)+T:  acc = acc + v[r][w][k][t - start(w)]

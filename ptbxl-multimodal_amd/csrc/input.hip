@@ -19,6 +19,10 @@
 //   zscore_stats_kernel      one LANE per (window, lead) row walks its row twice (the sequential
 //                            sums are the semantics; 3072 rows at B=256 -> latency-, not HBM-bound)
 //   zscore_apply_kernel      elementwise, float4
+//
+// Recordings at another sampling rate than the model's: wfdb16_resample_kernel, a polyphase FIR between the DAC
+// conversion and the z-score, reading the same int16 stream in place (its arithmetic is stated above the kernel);
+// ecg_zscore_rows then normalises the windows it wrote.
 #include "common.h"
 
 // hipcc contracts a*b+c into an fma by default (-ffp-contract=fast) — and does so even through the
@@ -211,6 +215,83 @@ __global__ __launch_bounds__(256) void wfdb16_zscore_fused_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// Polyphase resampler: recordings sampled at another rate than the model's.  The resampled recording y has
+// Tout = ceil(Ttot*up/down) samples and the windows are cut out of y (WindowSrc::Ttot holds Tout here):
+//     M = n*down + half;  phi = M mod up;  k0 = M div up                           (64-bit)
+//     y[n] = sum over i = 0 .. ntap-1 ascending of  g[phi][i] * p[clamp(k0 - i, 0, Ttot-1)]
+// every product and sum a separately rounded fp32 op, all ntap terms added (the zero taps too), so y[n] depends on n
+// and the recording only and a numpy loop reproduces it bit for bit (tests/resample_ref.py).
+// One workgroup owns NT consecutive outputs of one window (NT a power of two, chosen by the host so that the tile
+// fits): it stages the source span floor((n0*down+half)/up) - ntap + 1 .. floor((n1*down+half)/up) as physical fp32
+// [lead][S] in LDS — clamped per sample, the double division once per staged sample — and each lane then runs the
+// ntap-term chain of one (lead, n) out of LDS; stores are coalesced along n.  Relative to the tile every index fits
+// 32 bits: rel = M - klo*up = phi0 + (ntap-1)*up + j*down.  TAPS_LDS: the table [up][ntap] is copied behind the tile
+// (small tables); otherwise it is read straight from global memory (L2-resident: at most 512*256 floats).
+// LDS banks (ds_read_b32: 32 banks per 32-lane half): consecutive lanes read down/up samples apart — conflict-free for
+// odd down (500 -> 100: 5) and for up >= down, 2-way for up = 1, down = 2 and 4-way for down = 4.
+// ---------------------------------------------------------------------------------------
+struct Resample {
+    int up, down, ntap, half;
+};
+
+template <bool TAPS_LDS>
+__global__ __launch_bounds__(256) void wfdb16_resample_kernel(
+    const int16_t *__restrict__ d, const double *__restrict__ gain, const int *__restrict__ baseline,
+    const float *__restrict__ taps, float *__restrict__ out, int T, int leads, int Tsrc, int logNT, int S,
+    Resample rs, WindowSrc ws) {
+    extern __shared__ __attribute__((aligned(16))) float span_lds[];      // [leads][S] (+ [up][ntap] behind)
+    __shared__ double sg[kMaxLeads];
+    __shared__ int sb[kMaxLeads];
+    const int NT = 1 << logNT;
+    const int b = blockIdx.y, t0 = blockIdx.x * NT, tid = threadIdx.x;
+    const int nt = min(NT, T - t0);
+    const int r = b / ws.W;
+    const long long n0 = window_start(ws, b - r * ws.W) + t0;
+    const long long A0 = n0 * rs.down + rs.half;
+    const long long k00 = A0 / rs.up;
+    const int phi0 = (int)(A0 - k00 * rs.up);
+    const long long klo = k00 - rs.ntap + 1;                              // may be negative: clamped below
+    const int rel0 = phi0 + (rs.ntap - 1) * rs.up;
+    const int span = (rel0 + (nt - 1) * rs.down) / rs.up + 1;             // <= S
+    const int16_t *rec = d + (size_t)r * Tsrc * leads;
+    if (tid < leads) {
+        sg[tid] = gain[(size_t)r * leads + tid];
+        sb[tid] = baseline[(size_t)r * leads + tid];
+    }
+    const float *g = taps;
+    if (TAPS_LDS) {
+        float *gl = span_lds + (size_t)leads * S;
+        for (int e = tid; e < rs.up * rs.ntap; e += 256) gl[e] = taps[e];
+        g = gl;
+    }
+    __syncthreads();
+    for (int s = tid; s < span; s += 256) {            // thread <-> source sample: `leads` consecutive int16
+        long long k = klo + s;
+        k = k < 0 ? 0 : (k > Tsrc - 1 ? Tsrc - 1 : k);
+        const int16_t *p = rec + (size_t)k * leads;
+        for (int l = 0; l < leads; ++l) {
+            const int v = p[l];
+            span_lds[(size_t)l * S + s] = (v == -32768) ? __builtin_nanf("") : (float)((double)(v - sb[l]) / sg[l]);
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < (leads << logNT); e += 256) {
+        const int l = e >> logNT, j = e & (NT - 1);
+        if (j >= nt) continue;
+        const int rel = rel0 + j * rs.down;
+        const int krel = rel / rs.up, phi = rel - krel * rs.up;           // krel in [ntap-1, span)
+        const float *row = span_lds + (size_t)l * S + krel;
+        const float *gp = g + (size_t)phi * rs.ntap;
+        float acc = 0.f;
+        for (int i = 0; i < rs.ntap; ++i) {
+            const float pr = gp[i] * row[-i];
+            acc = acc + pr;
+        }
+        out[((size_t)b * leads + l) * T + t0 + j] = acc;
+    }
+}
+
 // LANES active lanes per wave, one row each (fewer lanes per wave = more waves = more CUs busy and
 // fewer distinct cache lines per load instruction when there are few rows).
 template <int LANES>
@@ -389,6 +470,50 @@ ECG_API int ecg_wfdb16_windows(const int16_t *d, const double *gain, const int *
     if (rc) return rc;
     return wfdb16_windows_launch("wfdb16_windows", d, gain, baseline, out, stats, R, T, leads,
                                  WindowSrc{Ttot, W, first, hop, last_start}, stream);
+}
+
+ECG_API int ecg_wfdb16_windows_resampled(const int16_t *d, const double *gain, const int *baseline, const float *taps,
+                                         float *out, float *stats, int R, int Ttot, int leads, int T, int first, int hop,
+                                         int W, int last_start, int up, int down, int ntap, int half,
+                                         ecg_stream_t stream) {
+    const char *who = "wfdb16_windows_resampled";
+    ECG_REQUIRE(d && gain && baseline && taps && out, "%s: null pointer", who);
+    ECG_REQUIRE(up >= 1 && up <= 512 && down >= 1 && down <= 512, "%s: up=%d down=%d outside [1,512]", who, up, down);
+    ECG_REQUIRE(ntap >= 1 && ntap <= 256, "%s: ntap=%d outside [1,256]", who, ntap);
+    ECG_REQUIRE(half >= 0, "%s: half=%d must be >= 0", who, half);
+    ECG_REQUIRE((long long)ntap * up >= 2ll * half + 1, "%s: ntap*up=%d does not cover the filter length 2*half+1=%lld", who,
+                ntap * up, 2ll * half + 1);
+    ECG_REQUIRE(leads >= 1 && leads <= kMaxLeads, "%s: leads=%d outside [1,%d]", who, leads, kMaxLeads);
+    ECG_REQUIRE(R > 0 && Ttot > 0, "%s: R=%d Ttot=%d must be > 0", who, R, Ttot);
+    const long long Tout = ((long long)Ttot * up + down - 1) / down;      // the resampled recording's length
+    ECG_REQUIRE(Tout <= 0x7fffffffll, "%s: resampled length %lld exceeds int", who, Tout);
+    int rc = check_windows(who, R, (int)Tout, T, first, hop, W, last_start);
+    if (rc) return rc;
+    const long long NW = (long long)R * W;
+    ECG_REQUIRE(NW <= 65535, "%s: %lld windows exceed grid.y limit 65535", who, NW);
+    ECG_REQUIRE(!stats || NW * leads <= 65535, "%s: windows*leads=%lld exceeds 65535 rows for T=%d", who, NW * leads, T);
+    // The tile: the largest NT <= 256 whose source span (+ the table, when it is small enough to sit in LDS) fits in
+    // 64 KB together with the kernel's static 192 bytes.  NT = 1 always fits (S = ntap <= 256).
+    const bool taps_lds = up * ntap <= 2048;
+    const size_t tap_bytes = taps_lds ? (size_t)up * ntap * 4 : 0;
+    int logNT = 8, S = 0;
+    for (;; --logNT) {
+        S = (int)((((1ll << logNT) - 1) * down + up - 1) / up) + ntap;
+        if ((size_t)leads * S * 4 + tap_bytes <= 64u * 1024u - 256u || logNT == 0) break;
+    }
+    const size_t lds = (size_t)leads * S * 4 + tap_bytes;
+    const dim3 grid(cdiv(T, 1 << logNT), (int)NW);
+    const Resample rs{up, down, ntap, half};
+    const WindowSrc ws{Tout, W, first, hop, last_start};
+    if (taps_lds)
+        hipLaunchKernelGGL((wfdb16_resample_kernel<true>), grid, dim3(256), lds, as_stream(stream), d, gain, baseline, taps,
+                           out, T, leads, Ttot, logNT, S, rs, ws);
+    else
+        hipLaunchKernelGGL((wfdb16_resample_kernel<false>), grid, dim3(256), lds, as_stream(stream), d, gain, baseline, taps,
+                           out, T, leads, Ttot, logNT, S, rs, ws);
+    rc = check_launch("wfdb16_resample_kernel");
+    if (rc || !stats) return rc;
+    return ecg_zscore_rows(out, out, stats, (int)NW * leads, T, stream);   // the one copy of the statistics arithmetic
 }
 
 ECG_API int ecg_windows_overlap_mean(const float *v, float *out, float *cover, int R, int K, int T, int Ttot,

@@ -8,6 +8,7 @@ one-collective-per-step data-parallel wrapper.  CUDA(HIP) tensors always take th
 stock torch layers the modules inherit from, as the reference does on a GPU-less box.
 `ecg_hip.grad_cam` is batched Grad-CAM at the last Conv1d: a closed form on the GPU, the hook algorithm elsewhere.
 `ecg_hip.score_recording` scores a continuous recording of any length: sliding windows read in place, stitched CAMs.
+A recording at another sampling rate than the model's is resampled on the device (`ecg_hip.resample`, fs= / model_fs=).
 """
 from ._lib import EcgHipError, LIB_PATH, load  # noqa: F401
 

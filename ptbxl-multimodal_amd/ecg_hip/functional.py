@@ -916,6 +916,45 @@ def wfdb16_windows(d, gain, baseline, window, first, hop, W, last_start=-1, norm
     return (x, stats) if normalize and return_stats else x
 
 
+def wfdb16_windows_resampled(d, gain, baseline, window, first, hop, W, last_start, up, down, normalize=True,
+                             return_stats=False):
+    """wfdb16_windows for recordings sampled at another rate than the model's: d int16 [R, Ttot, leads] is resampled by
+    up/down on the device (ecg_hip.resample: scipy.signal.resample_poly's default filter, edge-held ends) between the
+    DAC conversion and the z-score, and the windows (first, hop, W, last_start — on the RESAMPLED axis of
+    resample.resampled_length(Ttot, up, down) samples) are cut out of the result.  -> fp32 [R, W, leads, window]
+    (stats [R*W*leads, 2] with return_stats).  A resampled sample depends on its index and the recording only, so
+    every window is a bitwise slice of the whole resampled recording.  The raw form, beside wfdb16_windows."""
+    from .resample import device_taps
+    if not (torch.is_tensor(d) and d.is_cuda):
+        raise L.EcgHipError("wfdb16_windows_resampled: a CPU tensor reached the HIP input step; d must be on the GPU")
+    if d.dtype != torch.int16 or gain.dtype != torch.float64 or baseline.dtype != torch.int32:
+        raise L.EcgHipError("wfdb16_windows_resampled: d must be int16, gain float64, baseline int32")
+    if d.dim() != 3:
+        raise L.EcgHipError("wfdb16_windows_resampled: d must be [R, Ttot, leads]")
+    d, gain, baseline = _contig(d), _contig(gain), _contig(baseline)
+    R, Ttot, leads = d.shape
+    if tuple(gain.shape) != (R, leads) or tuple(baseline.shape) != (R, leads):
+        raise L.EcgHipError("wfdb16_windows_resampled: gain/baseline must be [R, leads]")
+    up, down = int(up), int(down)
+    if not (1 <= up <= 512 and 1 <= down <= 512):
+        raise L.EcgHipError(f"wfdb16_windows_resampled: up={up} down={down} outside [1,512]")
+    taps, ntap, half = device_taps(up, down, d.device)
+    return _resampled_call(d, gain, baseline, taps, window, first, hop, W, last_start, up, down, ntap, half, normalize,
+                           return_stats)
+
+
+def _resampled_call(d, gain, baseline, taps, window, first, hop, W, last_start, up, down, ntap, half, normalize=True,
+                    return_stats=False):
+    """ecg_wfdb16_windows_resampled with a caller-made table taps fp32 [up, ntap] (the ABI's own argument list)."""
+    R, Ttot, leads = d.shape
+    x = torch.empty(R, max(int(W), 0), leads, max(int(window), 0), dtype=torch.float32, device=d.device)
+    stats = _empty(x, x.shape[0] * x.shape[1] * leads, 2) if normalize else None
+    _call("ecg_wfdb16_windows_resampled", L.ptr(d), L.ptr(gain), L.ptr(baseline), _f32(taps), _f32(x), _f32(stats), R,
+          Ttot, leads, int(window), int(first), int(hop), int(W), int(last_start), int(up), int(down), int(ntap), int(half),
+          _st())
+    return (x, stats) if normalize and return_stats else x
+
+
 def wfdb16_to_windows_sliding(d, gain, baseline, window, hop, tail="shift", normalize=True, return_stats=False):
     """wfdb16_to_windows for recordings longer than one window: d int16 [R, Ttot, leads] is cut into the windows of
     recording.window_plan(Ttot, window, hop, tail) without an overlapping copy ever existing.

@@ -8,6 +8,10 @@ of at most `batch_size`, and `ecg_windows_overlap_mean` averages the per-window 
 Window rule (shared with the C ABI): window w starts at sample first + w*hop; with tail="shift" a recording whose length
 is not first + k*hop + window gets one more window that ENDS with the recording (start Ttot - window), so that every
 sample is scored; tail="drop" leaves the remainder unscored.
+
+A recording sampled at another rate than the model's (`fs` != `model_fs`) is resampled on the device by
+`ecg_wfdb16_windows_resampled` (ecg_hip/resample.py) between the DAC conversion and the z-score; the window rule, the
+chunks and the stitched CAMs then live on the model-rate axis of resampled_length(Ttot, up, down) samples.
 """
 import torch
 
@@ -52,8 +56,10 @@ def plan_chunks(R, plan, batch_size):
 
 class RecordingScore:
     """starts (W start samples); logits, prob [R, W, C]; finite [R, W]; prob_max, prob_mean [R, C] over the finite windows
-    (NaN where a recording has none); with CAMs: cam [R, K, Ttot], cover [Ttot] (windows over each sample)."""
-    __slots__ = ("starts", "logits", "prob", "finite", "prob_max", "prob_mean", "cam", "cover")
+    (NaN where a recording has none); with CAMs: cam [R, K, Ttot], cover [Ttot] (windows over each sample).
+    fs: the sampling rate of the axis starts / cam / cover are on (the model's rate where the recording was resampled,
+    Ttot then being the resampled length; None when no rate was given); source_len: samples of the recording itself."""
+    __slots__ = ("starts", "logits", "prob", "finite", "prob_max", "prob_mean", "cam", "cover", "fs", "source_len")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -73,7 +79,7 @@ def _record_level(prob, finite):
 
 
 def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift", batch_size=256, x_demo=None,
-                    cam_classes=None, cam_normalize=None):
+                    cam_classes=None, cam_normalize=None, fs=None, model_fs=None):
     """Score recordings d int16 [Ttot, leads] or [R, Ttot, leads] (on the GPU, the .dat layout) with `model` in eval mode.
 
     gain float64 / baseline int32 [leads] or [R, leads]; window: samples per model input; hop: default window // 2;
@@ -87,6 +93,12 @@ def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift",
     `finite[r, w]` is False when a logit of the window is not finite or the window holds an invalid sample (-32768, a
     NaN lead): the fused eval blocks take max(., 0) after BatchNorm, which drops a NaN, so such a window has finite but
     meaningless logits and is kept out of prob_max / prob_mean by its input statistics.
+
+    fs / model_fs: the sampling rates of the recording and of the model's training data.  When both are given and differ,
+    the recording is resampled on the device by up/down = model_fs/fs (resample.rational_ratio; ValueError when the ratio
+    needs a term above 512): window, hop, starts, cam and cover are then on the MODEL-RATE axis of
+    resample.resampled_length(Ttot, up, down) samples, and model-axis sample t lies at source time t*down/up samples.
+    The CAMs are not mapped back to the source axis.  With either None, or both equal, nothing is resampled.
     -> RecordingScore."""
     if not (torch.is_tensor(d) and d.is_cuda):
         raise L.EcgHipError("score_recording: a CPU tensor reached the HIP input step; d must be on the GPU "
@@ -108,6 +120,14 @@ def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift",
     if x_demo is not None and x_demo.shape[0] != R:
         raise ValueError(f"x_demo has {x_demo.shape[0]} rows for {R} recordings")
     window = int(window)
+    source_len, ratio = Ttot, None
+    if fs is not None and model_fs is not None and fs != model_fs:
+        from .resample import rational_ratio, resampled_length
+        ratio = rational_ratio(fs, model_fs)
+        if ratio == (1, 1):         # equal within rational_ratio's 1e-9: nothing to resample
+            ratio = None
+        else:
+            Ttot = resampled_length(Ttot, *ratio)
     plan = window_plan(Ttot, window, window // 2 if hop is None else hop, tail)
     _, hop, W, _, starts = plan
     cams = None if cam_classes is None else [int(k) for k in cam_classes]
@@ -116,8 +136,12 @@ def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift",
     logits = v = None
     ok = torch.empty(R, W, dtype=torch.bool, device=dev)
     for r0, r1, w0, first, Wc, last in plan_chunks(R, plan, int(batch_size)):
-        x, stats = hipF.wfdb16_windows(d[r0:r1], gain[r0:r1], baseline[r0:r1], window, first, hop, Wc, last,
-                                       return_stats=True)
+        if ratio is None:
+            x, stats = hipF.wfdb16_windows(d[r0:r1], gain[r0:r1], baseline[r0:r1], window, first, hop, Wc, last,
+                                           return_stats=True)
+        else:
+            x, stats = hipF.wfdb16_windows_resampled(d[r0:r1], gain[r0:r1], baseline[r0:r1], window, first, hop, Wc, last,
+                                                     *ratio, return_stats=True)
         n = (r1 - r0) * Wc
         x = x.view(n, leads, window)
         xd = None if x_demo is None else x_demo[r0:r1].repeat_interleave(Wc, dim=0)
@@ -148,14 +172,16 @@ def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift",
             c = torch.where(mx > 0, c / torch.where(mx > 0, mx, torch.ones_like(mx)), c)
             cam = torch.where(covered, c, torch.zeros_like(c))
     return RecordingScore(starts=starts, logits=logits, prob=prob, finite=finite, prob_max=pmax, prob_mean=pmean,
-                          cam=cam, cover=cover)
+                          cam=cam, cover=cover, fs=fs if ratio is None else model_fs, source_len=source_len)
 
 
-def score_wfdb_record(record_path, model, **kw):
+def score_wfdb_record(record_path, model, model_fs=None, **kw):
     """score_recording for a WFDB format-16 record of any length on disk (record_path without extension, as
-    ecg_hip.wfdb16.read_record takes it): the samples are uploaded once, as int16, to the device of the model."""
+    ecg_hip.wfdb16.read_record takes it): the samples are uploaded once, as int16, to the device of the model.
+    model_fs: the rate the model was trained at; the record is resampled on the device when its header's rate differs.
+    None (default): the record is scored at its own rate, whatever the header says."""
     from .wfdb16 import read_record
     rec = read_record(record_path)
     dev = next(model.parameters()).device
     return score_recording(model, torch.from_numpy(rec.d.astype("int16")).to(dev), torch.from_numpy(rec.gain).to(dev),
-                           torch.from_numpy(rec.baseline).to(dev), **kw)
+                           torch.from_numpy(rec.baseline).to(dev), fs=rec.fs, model_fs=model_fs, **kw)

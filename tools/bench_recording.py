@@ -2,6 +2,7 @@
 score_recording end to end.
 
     python tools/bench_recording.py [--hours 1] [--rounds 7] [--iters 20] [--out profiles/recording_bench.json]
+                                    [--legs recording,resample] [--resample-out profiles/resample_bench.json]
 
 Workloads: one 12-lead recording of --hours at 500 Hz (window 5000) and at 100 Hz (window 1000), hop = window / 2.
   (a) sliding   ecg_wfdb16_windows on the recording in place
@@ -10,6 +11,14 @@ Workloads: one 12-lead recording of --hours at 500 Hz (window 5000) and at 100 H
   (c) score     score_recording in fp32 and under inference_precision("bf16"), without CAMs and with CAMs for all classes
 (a) and (b) alternate in one process, --rounds times; each round times --iters calls between device events.  The bytes
 are counted from the shapes; "frac_of_hbm" is bytes / time over the 6.3 TB/s the project uses as achievable bandwidth.
+
+Leg "resample": the same one-hour 12-lead recording at 500 Hz scored by the 12x1000 model at 100 Hz (hop = window / 2).
+  (d) resampled  ecg_wfdb16_windows_resampled on the recording in place
+  (e) stock      wfdb16_to_windows(normalize=False) on the whole recording, a strided torch.nn.functional.conv1d with the
+                 same taps (edge-padded), a torch index-gather of the windows, then ecg_zscore_rows
+alternating in one process like (a) and (b), together with the streaming plan spelled out (the resampling launch, then
+ecg_zscore_rows in place) against the plan the entry point picks; the resampling launch alone (normalize=False) is also rated against the bytes it must
+move, 2*down/up B in + 4 B out per output sample.  Written to --resample-out.
 Fails when no GPU is visible: no number here means anything on a CPU.
 """
 import argparse
@@ -45,6 +54,81 @@ def prime(fn, seconds=0.5):
         torch.cuda.synchronize()
 
 
+def resample_leg(a):
+    """500 Hz recording -> 12x1000 windows at 100 Hz: the resampled entry point against stock torch on the same GPU."""
+    from ecg_hip import functional as F
+    from ecg_hip.recording import window_plan
+    from ecg_hip.resample import device_taps, rational_ratio, resampled_length
+    fs, model_fs, window = 500, 100, 1000
+    hop = window // 2
+    up, down = rational_ratio(fs, model_fs)
+    Ttot = int(a.hours * 3600 * fs)
+    Tout = resampled_length(Ttot, up, down)
+    rng = np.random.default_rng(fs)
+    d = torch.from_numpy(rng.integers(-3000, 3000, size=(1, Ttot, LEADS)).astype(np.int16)).cuda()
+    gain = torch.full((1, LEADS), 1000.0, dtype=torch.float64).cuda()
+    base = torch.zeros(1, LEADS, dtype=torch.int32).cuda()
+    first, hop, W, last, starts = window_plan(Tout, window, hop)
+    taps, ntap, half = device_taps(up, down, d.device)
+    # stock form of the same filter: y[n] = sum_i g[phi][i] * p[k0 - i]; for up == 1 that is a correlation of the edge-padded
+    # signal with the reversed taps at stride `down` (this leg's ratio; a general up would need one conv per phase)
+    assert up == 1
+    w = taps[0].flip(0).reshape(1, 1, ntap).expand(LEADS, 1, ntap).contiguous()
+    lpad = ntap - 1 - half // up
+    rpad = max(0, ((Tout - 1) * down + half) // up - (Ttot - 1))
+    idx = torch.tensor(starts, device="cuda")[:, None] + torch.arange(window, device="cuda")[None, :]      # [W][T]
+
+    def resampled():
+        return F.wfdb16_windows_resampled(d, gain, base, window, first, hop, W, last, up, down)
+
+    def kernel_only():
+        return F.wfdb16_windows_resampled(d, gain, base, window, first, hop, W, last, up, down, normalize=False)
+
+    def streaming():                # the streaming plan spelled out: the resampling launch, then ecg_zscore_rows in place
+        p = kernel_only()
+        return F.zscore_per_lead(p, out=p)
+
+    def stock():
+        p = F.wfdb16_to_windows(d, gain, base, normalize=False)                          # [1][leads][Ttot]
+        p = torch.nn.functional.pad(p, (lpad, rpad), mode="replicate")
+        y = torch.nn.functional.conv1d(p, w, stride=down, groups=LEADS)[..., :Tout]      # [1][leads][Tout]
+        x = y[0][:, idx].permute(1, 0, 2).contiguous()                                   # [W][leads][T]
+        return F.zscore_per_lead(x, out=x)
+
+    # same filter, another summation order and fused multiply-adds: close, not bit-identical
+    diff = float((resampled()[0] - stock()).abs().max())
+    assert diff <= 1e-3, diff
+    assert torch.equal(resampled(), streaming())
+    prime(resampled), prime(stock), prime(kernel_only), prime(streaming)
+    ta, tb, tk, ts = [], [], [], []
+    for _ in range(a.rounds):
+        ta.append(timed(resampled, a.iters))
+        tb.append(timed(stock, a.iters))
+        tk.append(timed(kernel_only, a.iters))
+        ts.append(timed(streaming, a.iters))
+    n = W * window * LEADS                                                               # output samples
+    must = n * (2.0 * down / up + 4.0)
+    ma, mb, mk = float(np.median(ta)), float(np.median(tb)), float(np.median(tk))
+    line = {"metric": "resampled_input_step_ms", "value": round(ma, 4), "unit": "ms",
+            "config": {"workload": f"{a.hours:g} h, {LEADS} leads at {fs} Hz (Ttot {Ttot}) -> {model_fs} Hz (up/down {up}/{down}, "
+                                   f"{ntap} taps, Tout {Tout}), window {window}, hop {hop}, {W} windows, int16 -> z-scored fp32"},
+            "resampled_ms": [round(t, 4) for t in ta], "stock_ms": [round(t, 4) for t in tb],
+            "kernel_only_ms": [round(t, 4) for t in tk], "streaming_plan_ms": [round(t, 4) for t in ts],
+            "streaming_plan_median_ms": round(float(np.median(ts)), 4),
+            "streaming_over_resampled": round(float(np.median(ts)) / ma, 3),
+            "resampled_median_ms": round(ma, 4), "stock_median_ms": round(mb, 4), "kernel_only_median_ms": round(mk, 4),
+            "stock_spread_ms": round(max(tb) - min(tb), 4), "resampled_spread_ms": round(max(ta) - min(ta), 4),
+            "stock_over_resampled": round(mb / ma, 3), "max_abs_diff_resampled_vs_stock": diff,
+            "kernel_bytes_it_must_move": int(must), "kernel_GBps_of_those_bytes": round(must / (mk * 1e-3) / 1e9, 1),
+            "kernel_frac_of_hbm": round(must / (mk * 1e-3) / HBM_BYTES_PER_S, 4),
+            "kernel_fp32_madds_per_s": round(n * ntap / (mk * 1e-3), 1),
+            "windows_per_s": round(W / (ma * 1e-3), 1)}
+    print(json.dumps(line), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.resample_out)), exist_ok=True)
+    with open(a.resample_out, "w") as f:
+        json.dump([line], f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--hours", type=float, default=1.0)
@@ -52,6 +136,8 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "recording_bench.json"))
+    ap.add_argument("--legs", default="recording,resample")
+    ap.add_argument("--resample-out", default=os.path.join(ROOT, "profiles", "resample_bench.json"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_recording: no GPU visible")
@@ -61,6 +147,10 @@ def main():
     from src.models.ecg_cnn import ECGCNN
     from src.utils.seed import set_seed
     _lib.call("ecg_check_device")
+    if "resample" in a.legs.split(","):
+        resample_leg(a)
+    if "recording" not in a.legs.split(","):
+        return
     res = []
     for fs, window in ((500, 5000), (100, 1000)):
         Ttot, hop = int(a.hours * 3600 * fs), window // 2
