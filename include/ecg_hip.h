@@ -23,6 +23,21 @@
  *     backward on torch's autograd engine thread.
  *   - Conv1d support envelope: stride 1, dilation 1, groups 1, 1 <= K <= 31,
  *     0 <= pad < K (the reference uses K=15, pad=7 only: src/models/ecg_cnn.py:13).
+ *   - Non-finite values (NaN, +-Inf) are ordinary data (tests/test_gpu_values.py):
+ *     PROPAGATION  MaxPool1d(2) returns NaN when either element of the pair is NaN (otherwise the first element wins a
+ *       tie), ReLU clips only what compares <= 0 (a NaN passes, forward and as the mask of the backward, where the pool
+ *       routes the gradient to the NaN), BatchNorm, the eval epilogues, the tail, sigmoid and the loss give NaN / +-Inf
+ *       where the stock torch layers give them; train-mode statistics of a channel that holds a NaN are NaN (mean,
+ *       invstd, running statistics, every output of the channel).  Eval-mode backward has no batch term: a non-finite
+ *       y does not reach dy.
+ *     CONTAINMENT  no kernel that reduces over neither the batch nor the channel of a non-finite element lets it change
+ *       a bit of another sample; the per-row passes not a bit of another (sample, channel) row.  Inside the sample a
+ *       convolution's non-finite outputs cover the stock footprint (the K taps around the element, zero padding
+ *       included as a factor) and may exceed it by ONE time step on each side in the MFMA kernels — the fast-FIR form
+ *       combines the pair (2m, 2m+1) from three products and cancels x[2m] out of y[2m+1] only algebraically; the same
+ *       recombination turns an Inf into NaN (Inf - Inf).  The direct kernel and every non-conv kernel match the stock
+ *       set exactly.  Weight gradient: a non-finite x[., ci, .] reaches dw[:, ci, :] only, a non-finite
+ *       dy[., co, .] reaches dw[co, :, :] and db[co] only.
  */
 #ifndef ECG_HIP_H
 #define ECG_HIP_H
@@ -242,7 +257,7 @@ int ecg_bn_finalize(const float *stat_partials, int P, long long count,
 /* invstd[c] = 1/sqrt(var[c] + eps)  (eval mode: from running_var) */
 int ecg_bn_invstd(const float *var, float *invstd, int C, float eps, ecg_stream_t stream);
 
-/* p[n,c,j] = max(0, max(a[2j], a[2j+1])),  a = (y-mean)*(invstd*gamma)+beta,  Lp = L/2 */
+/* p[n,c,j] = relu(max(a[2j], a[2j+1])),  a = (y-mean)*(invstd*gamma)+beta,  Lp = L/2; NaN if either a is NaN */
 int ecg_bn_relu_pool_fwd(const float *y, const float *gamma, const float *beta,
                          const float *mean, const float *invstd, float *p,
                          int N, int C, int L, ecg_stream_t stream);
@@ -286,8 +301,10 @@ int ecg_bn_relu_pool_bwd_one_launch(const float *y, const float *dp, const float
 
 size_t ecg_bn_relu_pool_bwd_ws_floats(int N, int C, int L);
 /* Backward of the fused tail: dp [N][C][L/2] -> dy [N][C][L], dgamma[C], dbeta[C].
- * Arg-max and ReLU mask are recomputed from y (first element wins a tie, as max_pool1d).
- * train != 0: batch-statistics backward (native_batch_norm_backward);  train == 0: dy = da*gamma*invstd. */
+ * Arg-max and ReLU mask are recomputed from y (first element wins a tie, a NaN wins — the second of two —, and the
+ * gradient passes wherever the output does not compare <= 0: as max_pool1d and threshold_backward).
+ * train != 0: batch-statistics backward (native_batch_norm_backward);  train == 0: dy = da*gamma*invstd (y enters
+ * through the routing only: a non-finite y leaves dy finite). */
 int ecg_bn_relu_pool_bwd(const float *y, const float *dp, const float *gamma, const float *beta,
                          const float *mean, const float *invstd,
                          float *dy, float *dgamma, float *dbeta, float *ws,
@@ -432,6 +449,7 @@ int ecg_film_bwd(const float *z, const float *film, const float *dzc, float *dz,
                  int M, int F, ecg_stream_t stream);
 
 /* loss[0] = mean(max(x,0) - x*t + log1p(exp(-|x|)))  — src/training/loop.py:32, loop_demo.py:10,33
+ * (an infinite x takes ATen's form (1-t)*x + max(-x,0): +Inf for (+Inf, t=0), NaN for the other t in {0,1} cases)
  * dx (nullable) = (sigmoid(x) - t) / numel  (the gradient for d loss = 1).
  * running_sum (nullable, device double): running_sum[0] += loss * weight — the epoch-loss
  * bookkeeping of the loops (loop.py:36 weight = batch size, loop_demo.py:38 weight = 1). */

@@ -169,8 +169,7 @@ __global__ __launch_bounds__(kBlock) void bn_relu_pool_fwd_kernel(
         for (int u = 0; u < U; ++u) {
             if (!live[u]) continue;
             const float a0 = bn_apply1(y0[u], mu, sc, be), a1 = bn_apply1(y1[u], mu, sc, be);
-            const float m = a1 > a0 ? a1 : a0;
-            p[out[u]] = m > 0.f ? m : 0.f;
+            p[out[u]] = relu1(pool_max2(a0, a1));
         }
     }
 }
@@ -213,8 +212,7 @@ __global__ __launch_bounds__(kBlock) void bn_relu_pool_gap_fwd_kernel(
 #pragma unroll
             for (int r = 0; r < RB; ++r) {
                 const float a0 = bn_apply1(r0[r], mu, sc, be), a1 = bn_apply1(r1[r], mu, sc, be);
-                const float m = a1 > a0 ? a1 : a0;
-                a[r] += m > 0.f ? m : 0.f;
+                a[r] += relu1(pool_max2(a0, a1));
             }
         }
 #pragma unroll
@@ -241,8 +239,8 @@ __global__ __launch_bounds__(kBlock) void bn_apply_fwd_kernel(
 // da for the pair (2j, 2j+1): returns the arg-max slot am (0/1) and whether the gradient passes.
 __device__ __forceinline__ bool pool_route(float y0, float y1, float mu, float sc, float be, int &am) {
     float a0 = bn_apply1(y0, mu, sc, be), a1 = bn_apply1(y1, mu, sc, be);
-    am = a1 > a0 ? 1 : 0;          // first element wins a tie (max_pool1d keeps the first index)
-    return (am ? a1 : a0) > 0.f;   // ReLU backward: output > 0
+    am = pool_takes1(a0, a1) ? 1 : 0;      // first element wins a tie, a NaN wins (max_pool1d keeps the first index / the NaN)
+    return relu_passes(am ? a1 : a0);      // ReLU backward: everything but output <= 0 (a NaN passes its gradient)
 }
 
 // partials[c][s][2] = (sum da, sum da*xhat).  FUSED: da routed from dp through pool+ReLU;
@@ -401,8 +399,9 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_dx_kernel(
                 da0 = d0[u];
                 if (has1) da1 = d1[u];
             }
-            d[t] = gi * (da0 - k1 - (y0[u] - mu) * is * k2);
-            if (has1) d[t + 1] = gi * (da1 - k1 - (y1[u] - mu) * is * k2);
+            // eval mode has no batch terms: a non-finite y must not reach dy through 0 * xhat
+            d[t] = train ? gi * (da0 - k1 - (y0[u] - mu) * is * k2) : gi * da0;
+            if (has1) d[t + 1] = train ? gi * (da1 - k1 - (y1[u] - mu) * is * k2) : gi * da1;
             else if (t + 1 < ldy) d[t + 1] = 0.f;
         }
     }
@@ -606,9 +605,9 @@ __global__ __launch_bounds__(kResThreads) void bn_bwd_resident_kernel(
                 if (am) da1 = d[i]; else da0 = d[i];
             }
         }
-        const float o0 = gi * (da0 - k1 - (y0[i] - mu) * is * k2);
+        const float o0 = train ? gi * (da0 - k1 - (y0[i] - mu) * is * k2) : gi * da0;   // (eval: no 0 * xhat of a non-finite y)
         if (has1) {
-            const float o1 = gi * (da1 - k1 - (y1[i] - mu) * is * k2);
+            const float o1 = train ? gi * (da1 - k1 - (y1[i] - mu) * is * k2) : gi * da1;
             if (AL8 && (ldy & 1) == 0) *reinterpret_cast<float2 *>(dr + t) = make_float2(o0, o1);
             else { dr[t] = o0; dr[t + 1] = o1; }
         } else dr[t] = o0;
@@ -625,12 +624,12 @@ __global__ __launch_bounds__(kResThreads) void bn_bwd_resident_kernel(
 // ---------------------------------------------------------------------------------------
 __global__ void relu_fwd_kernel(const float *__restrict__ x, float *__restrict__ out, size_t n) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { float v = x[i]; out[i] = v > 0.f ? v : 0.f; }
+    if (i < n) { float v = x[i]; out[i] = relu1(v); }
 }
 __global__ void relu_bwd_kernel(const float *__restrict__ out, const float *__restrict__ dout,
                                 float *__restrict__ dx, size_t n) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dx[i] = out[i] > 0.f ? dout[i] : 0.f;
+    if (i < n) dx[i] = relu_passes(out[i]) ? dout[i] : 0.f;
 }
 __global__ void maxpool2_fwd_kernel(const float *__restrict__ x, float *__restrict__ p, int L,
                                     int Lp, size_t total) {
@@ -639,7 +638,7 @@ __global__ void maxpool2_fwd_kernel(const float *__restrict__ x, float *__restri
     size_t row = idx / Lp;
     int j = (int)(idx - row * Lp);
     const float *r = x + row * L + 2 * j;
-    p[idx] = r[1] > r[0] ? r[1] : r[0];
+    p[idx] = pool_max2(r[0], r[1]);
 }
 __global__ void maxpool2_bwd_kernel(const float *__restrict__ x, const float *__restrict__ dp,
                                     float *__restrict__ dx, int L, int Lh, size_t total) {
@@ -652,7 +651,7 @@ __global__ void maxpool2_bwd_kernel(const float *__restrict__ x, const float *__
     float *d = dx + row * L;
     if (t0 + 1 < L) {
         float v = dp[row * (size_t)(L >> 1) + j];
-        bool am = r[t0 + 1] > r[t0];
+        bool am = pool_takes1(r[t0], r[t0 + 1]);
         d[t0] = am ? 0.f : v;
         d[t0 + 1] = am ? v : 0.f;
     } else {

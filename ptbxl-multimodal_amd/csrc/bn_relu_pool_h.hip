@@ -78,8 +78,8 @@ __device__ __forceinline__ void bn_finalize_block_h(const BnFinH &f, int c, bool
 
 __device__ __forceinline__ bool pool_route_h(float y0, float y1, float mu, float sc, float be, int &am) {
     const float a0 = bn_apply1(y0, mu, sc, be), a1 = bn_apply1(y1, mu, sc, be);
-    am = a1 > a0 ? 1 : 0;          // first element wins a tie (max_pool1d keeps the first index)
-    return (am ? a1 : a0) > 0.f;   // ReLU backward: output > 0
+    am = pool_takes1(a0, a1) ? 1 : 0;      // first element wins a tie, a NaN wins (max_pool1d keeps the first index / the NaN)
+    return relu_passes(am ? a1 : a0);      // ReLU backward: everything but output <= 0 (a NaN passes its gradient)
 }
 
 // ---------------------------------------------------------------------------------------
@@ -124,8 +124,7 @@ __global__ __launch_bounds__(kBlockH) void bn_relu_pool_fwd_h_kernel(
             for (int i = 0; i < 8; ++i) {
                 const unsigned v = i < 4 ? lo[u][i] : hi[u][i - 4];
                 const float a0 = bn_apply1(bf_lo(v), mu, sc, be), a1 = bn_apply1(bf_hi(v), mu, sc, be);
-                float r = a1 > a0 ? a1 : a0;
-                r = r > 0.f ? r : 0.f;
+                const float r = relu1(pool_max2(a0, a1));
                 // pooled position q8 + i exists iff < Lp (then both its inputs are inside the row); the rest is the zero fill
                 m[i] = (q8[u] + i < Lp && (i < 4 ? vlo[u] : vhi[u])) ? r : 0.f;
             }
@@ -289,8 +288,9 @@ __global__ __launch_bounds__(kBlockH) void bn_bwd_dx_h_kernel(
                         if (am) da1 = d[u][i]; else da0 = d[u][i];
                     }
                 }
-                const float v0 = in0 ? gi * (da0 - k1 - (y0 - mu) * is * k2) : 0.f;
-                const float v1 = has1 ? gi * (da1 - k1 - (y1 - mu) * is * k2) : 0.f;
+                // eval mode has no batch terms: a non-finite y must not reach dy through 0 * xhat
+                const float v0 = !in0 ? 0.f : train ? gi * (da0 - k1 - (y0 - mu) * is * k2) : gi * da0;
+                const float v1 = !has1 ? 0.f : train ? gi * (da1 - k1 - (y1 - mu) * is * k2) : gi * da1;
                 o[i] = pack2h(v0, v1);
             }
             *reinterpret_cast<u32x4h *>(dy + out[u]) = o;

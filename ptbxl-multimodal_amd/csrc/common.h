@@ -66,4 +66,19 @@ __device__ __forceinline__ float bn_apply1(float y, float mean, float scale, flo
     return __fmaf_rn(y - mean, scale, beta);
 }
 
+// MaxPool1d(2) and ReLU on non-finite data exactly as the stock layers: the pool takes slot 1 when it is larger OR NaN
+// and otherwise slot 0 (so a NaN in either slot comes out, and the first slot wins a tie); ReLU clips only what compares
+// <= 0, so a NaN passes — forward and, as the mask of the backward, with its gradient.  On finite data these are the
+// plain compare forms bit for bit.
+__device__ __forceinline__ bool pool_takes1(float a0, float a1) { return a1 > a0 || a1 != a1; }
+__device__ __forceinline__ float pool_max2(float a0, float a1) { return pool_takes1(a0, a1) ? a1 : a0; }
+__device__ __forceinline__ bool relu_passes(float m) { return !(m <= 0.f); }
+__device__ __forceinline__ float relu1(float m) { return relu_passes(m) ? m : 0.f; }
+// relu(max(a0, a1)) of the eval epilogues, where only the value is needed: the three-operand max of the finite path (fmaxf
+// drops a NaN) and one unordered compare that puts the NaN back.  Same values as relu1(pool_max2(a0, a1)).
+__device__ __forceinline__ float pool_relu2(float a0, float a1) {
+    const float m = fmaxf(fmaxf(a0, a1), 0.f);
+    return __builtin_isunordered(a0, a1) ? __builtin_nanf("") : m;
+}
+
 }  // namespace ecg

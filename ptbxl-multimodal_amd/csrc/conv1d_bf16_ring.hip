@@ -322,7 +322,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 4 
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = __fmaf_rn(acc[i][j][4 * g4 + e], bsc[i], bsh[i]);
                     const int pp = (pt0 + 32 * j + 8 * g4 + 4 * half) >> 1;
-                    const float a = fmaxf(fmaxf(v[0], v[1]), 0.f), b = fmaxf(fmaxf(v[2], v[3]), 0.f);
+                    // A NaN comes out, as from the stock layers.  The non-finite footprint of the eval forms is bounded by the pooled image of
+                    // the conv output's footprint + 1, not by the smaller set behind torch's ReLU (a NaN is not clipped where torch's
+                    // -Inf is); DESIGN.md section 12
+                    const float a = pool_relu2(v[0], v[1]), b = pool_relu2(v[2], v[3]);
                     pv[2 * g4] = pp < Lp ? a : 0.f;
                     pv[2 * g4 + 1] = pp + 1 < Lp ? b : 0.f;
                 }

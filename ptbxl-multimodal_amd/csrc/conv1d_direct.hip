@@ -235,7 +235,9 @@ __global__ __launch_bounds__(kTT) void conv1d_wgrad_generic_kernel(
             for (int t = tl; t < Lo; t += kTT) {
                 if (k == K) { a += dyr[t]; continue; }
                 int sidx = t + k - pad;
-                if (sidx >= 0 && sidx < L) a += (double)dyr[t] * (double)xr[sidx];
+                // the zero padding is a factor, not a skipped term: a non-finite dy beside it gives NaN, as in torch (and in the
+                // MFMA kernels, which stage the zeros); a finite one adds an exact 0
+                a += (double)dyr[t] * (double)((sidx >= 0 && sidx < L) ? xr[sidx] : 0.f);
             }
         }
         a = wave_sum(a);

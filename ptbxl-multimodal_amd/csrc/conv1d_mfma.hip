@@ -355,7 +355,10 @@ __global__ __launch_bounds__(256, ECG_FFA_MINB) void conv1d_mfma_ffa_kernel(
         float s = 0.f, q = 0.f;
         if (EVALM) {
             const float mu = pick(p_mu, r), sc = pick(p_sc, r), be = pick(p_be, r);
-            const float mx = fmaxf(fmaxf(bn_apply1(v0, mu, sc, be), bn_apply1(v1, mu, sc, be)), 0.f);
+            // A NaN comes out, as from the stock layers.  Non-finite footprint inside the sample: the pooled image of the CONV output's
+            // footprint + 1 — wider than the set behind torch's ReLU for an Inf input (Inf - Inf in v1 is NaN, which the ReLU does not
+            // clip where it clips torch's -Inf); DESIGN.md section 12
+            const float mx = pool_relu2(bn_apply1(v0, mu, sc, be), bn_apply1(v1, mu, sc, be));
             if (GAP) {
                 s = row16_sum(okp ? mx : 0.f);
                 st_s += ((l31 & 15) == r) ? s : 0.f;

@@ -27,14 +27,18 @@ constexpr int kWaves = kThreads / kWave;
 constexpr int kMaxC = 256;
 constexpr int kMaxK = 8;
 
+// min / max that return NaN when either side is NaN, as torch's reductions do (fminf / fmaxf drop it)
+__device__ __forceinline__ float min_nan(float a, float b) { return (b < a || b != b) ? b : a; }
+__device__ __forceinline__ float max_nan(float a, float b) { return (b > a || b != b) ? b : a; }
+
 __device__ __forceinline__ float wave_min(float v) {
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off, 64));
+    for (int off = 32; off > 0; off >>= 1) v = min_nan(v, __shfl_xor(v, off, 64));
     return v;
 }
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    for (int off = 32; off > 0; off >>= 1) v = max_nan(v, __shfl_xor(v, off, 64));
     return v;
 }
 
@@ -49,7 +53,7 @@ __device__ __forceinline__ void block_minmax(float &mn, float &mx, float *red) {
     mn = red[0];
     mx = red[kWaves];
 #pragma unroll
-    for (int w = 1; w < kWaves; ++w) { mn = fminf(mn, red[w]); mx = fmaxf(mx, red[kWaves + w]); }
+    for (int w = 1; w < kWaves; ++w) { mn = min_nan(mn, red[w]); mx = max_nan(mx, red[kWaves + w]); }
 }
 
 // PyTorch's linear resampling (align_corners=False), every step rounded on its own as ATen's fp32 path does
@@ -105,9 +109,9 @@ __global__ __launch_bounds__(kThreads) void gradcam_kernel(
             float p = 0.0f;
             if (j < Lp) {
                 float z0 = __fmaf_rn(row[2 * j], sc, sh), z1 = __fmaf_rn(row[2 * j + 1], sc, sh);
-                p = fmaxf(fmaxf(z0, z1), 0.0f);
+                p = relu1(pool_max2(z0, z1));
             }
-            cnt += __popcll(__ballot(p > 0.0f));
+            cnt += __popcll(__ballot(relu_passes(p)));      // (ReLU backward passes at a NaN)
             gs += p;
         }
         gs = wave_sum(gs);
@@ -162,7 +166,7 @@ __global__ __launch_bounds__(kThreads) void gradcam_kernel(
                 if (t0 + s < Lo) {
                     float sum = part[k * TS + s];
                     for (int q = 1; q < CG; ++q) sum = __fadd_rn(sum, part[(q * KP + k) * TS + s]);
-                    rawn[(size_t)k * Lo + t0 + s] = fmaxf(sum, 0.0f);
+                    rawn[(size_t)k * Lo + t0 + s] = relu1(sum);
                 }
             }
             __syncthreads();
@@ -181,7 +185,7 @@ __global__ __launch_bounds__(kThreads) void gradcam_kernel(
         bool divide = false;
         if (norm == 1) {                              // GradCAM1D._normalize_cam: before resampling, divide only if max > 0
             float mn = INFINITY, mx = -INFINITY;
-            for (int t = tid; t < Lo; t += kThreads) { float v = r[t]; mn = fminf(mn, v); mx = fmaxf(mx, v); }
+            for (int t = tid; t < Lo; t += kThreads) { float v = r[t]; mn = min_nan(mn, v); mx = max_nan(mx, v); }
             block_minmax(mn, mx, red);
             sub = mn;
             div = __fsub_rn(mx, mn);
@@ -190,8 +194,8 @@ __global__ __launch_bounds__(kThreads) void gradcam_kernel(
             float mn = INFINITY, mx = -INFINITY;
             for (int j = tid; j < S; j += kThreads) {
                 float v = resampled<false>(r, j, same, ratio, Lo, 0.0f, 1.0f);
-                mn = fminf(mn, v);
-                mx = fmaxf(mx, v);
+                mn = min_nan(mn, v);
+                mx = max_nan(mx, v);
             }
             block_minmax(mn, mx, red);
             sub = mn;

@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) void gemm_small_kernel(
             if (m < M && k < K) {
                 size_t ia = (size_t)m * sam + (size_t)k * sak;
                 v = A[ia];
-                if (amask && !(amask[ia] > 0.f)) v = 0.f;
+                if (amask && amask[ia] <= 0.f) v = 0.f;          // (ReLU mask: a NaN passes its gradient, as torch)
             }
             As[ty][tx] = v;
             int kb = k0 + ty, n = n0 + tx;
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float *__restrict__ g
     for (int m = lane; m < M; m += 64) {
         size_t i = (size_t)m * Out + o;
         float v = g[i];
-        if (mask && !(mask[i] > 0.f)) v = 0.f;
+        if (mask && mask[i] <= 0.f) v = 0.f;
         a += v;
     }
     a = wave_sum(a);
@@ -114,6 +114,13 @@ __global__ void film_bwd_kernel(const float *__restrict__ z, const float *__rest
 // One workgroup of 1024 threads: at the model's sizes (B x C = 1280 logits) every element is loaded in the first trip — the
 // kernel is one dependent chain load -> exp / log1p -> reduce -> store, so its time is that chain's latency (5.8 us with 256
 // threads walking five trips; the sums are fixed-order per thread, then lanes by butterfly, then waves in order).
+// One element of the loss.  An infinite logit takes the form ATen evaluates, (1 - t) x + max(-x, 0): +inf against t = 0 is
+// +inf, the other three combinations with t in {0, 1} are NaN (0 * inf, inf - inf) — max(x, 0) - x t would swap two of them.
+// Finite logits keep the expression (and the bits) they always had; a NaN logit gives NaN through x * t.
+__device__ __forceinline__ float bce_term(float x, float t) {
+    if (fabsf(x) == INFINITY) return (1.0f - t) * x + fmaxf(-x, 0.f);
+    return fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
+}
 constexpr int kBceThreads = 1024;
 __global__ __launch_bounds__(kBceThreads) void bce_kernel(const float *__restrict__ x,
                                                           const float *__restrict__ t,
@@ -127,10 +134,10 @@ __global__ __launch_bounds__(kBceThreads) void bce_kernel(const float *__restric
         const int i1 = i0 + kBceThreads;
         const bool two = i1 < numel;
         const float x0 = x[i0], t0 = t[i0], x1 = two ? x[i1] : 0.f, t1 = two ? t[i1] : 0.f;      // both trips' loads in flight
-        a += (double)(fmaxf(x0, 0.f) - x0 * t0 + log1pf(expf(-fabsf(x0))));
+        a += (double)bce_term(x0, t0);
         if (dx) dx[i0] = (1.0f / (1.0f + expf(-x0)) - t0) * inv;
         if (two) {
-            a += (double)(fmaxf(x1, 0.f) - x1 * t1 + log1pf(expf(-fabsf(x1))));
+            a += (double)bce_term(x1, t1);
             if (dx) dx[i1] = (1.0f / (1.0f + expf(-x1)) - t1) * inv;
         }
     }

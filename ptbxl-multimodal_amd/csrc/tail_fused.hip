@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void tail_fwd_kernel(TailFwdArgs a) {
         for (int e = tid; e < a.H1 * kSB; e += 256) {
             int s = e / a.H1, j = e - s * a.H1;
             float acc = a.b0[j] + dot_col(xd_s, s, a.W0 + (size_t)j * a.D, 1, a.D);
-            acc = acc > 0.f ? acc : 0.f;
+            acc = relu1(acc);
             h1_s[j * kSB + s] = acc;
             if (m0 + s < a.M) a.h1[(size_t)(m0 + s) * a.H1 + j] = acc;
         }
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void tail_fwd_kernel(TailFwdArgs a) {
         for (int e = tid; e < a.H * kSB; e += 256) {
             int s = e / a.H, j = e - s * a.H;
             float acc = a.b2[j] + dot_col(h1_s, s, a.W2 + (size_t)j * a.H1, 1, a.H1);
-            acc = acc > 0.f ? acc : 0.f;
+            acc = relu1(acc);
             h2_s[j * kSB + s] = acc;
             if (m0 + s < a.M) a.h2[(size_t)(m0 + s) * a.H + j] = acc;
         }
@@ -216,7 +216,7 @@ __global__ __launch_bounds__(256) void tail_bwd_chain_kernel(TailBwdArgs a) {
             int s = e / a.H, i = e - s * a.H;
             float acc = dot_col(dfilm_s, s, a.Wf + i, (size_t)a.H, 2 * a.F);
             const bool live = m0 + s < a.M;
-            if (!(live && a.h2[(size_t)(m0 + s) * a.H + i] > 0.f)) acc = 0.f;
+            if (!(live && relu_passes(a.h2[(size_t)(m0 + s) * a.H + i]))) acc = 0.f;
             dh2_s[i * kSB + s] = acc;
             if (live) a.dh2m[(size_t)(m0 + s) * a.H + i] = acc;
         }
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(256) void tail_bwd_chain_kernel(TailBwdArgs a) {
             int s = e / a.H1, i = e - s * a.H1;
             float acc = dot_col(dh2_s, s, a.W2 + i, (size_t)a.H1, a.H);
             const bool live = m0 + s < a.M;
-            if (!(live && a.h1[(size_t)(m0 + s) * a.H1 + i] > 0.f)) acc = 0.f;
+            if (!(live && relu_passes(a.h1[(size_t)(m0 + s) * a.H1 + i]))) acc = 0.f;
             dh1_s[i * kSB + s] = acc;
             if (live) a.dh1m[(size_t)(m0 + s) * a.H1 + i] = acc;
         }

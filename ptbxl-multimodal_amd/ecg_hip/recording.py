@@ -91,8 +91,9 @@ def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift",
     where the maximum is > 0).  The CAM path keeps K x W x window floats per recording until the stitch.
 
     `finite[r, w]` is False when a logit of the window is not finite or the window holds an invalid sample (-32768, a
-    NaN lead): the fused eval blocks take max(., 0) after BatchNorm, which drops a NaN, so such a window has finite but
-    meaningless logits and is kept out of prob_max / prob_mean by its input statistics.
+    NaN lead).  The kernels hand a NaN on as the stock layers do (pool, ReLU and the eval epilogues included), so the
+    logits of such a window are NaN — in its own rows only, the other windows of the batch keep their bits — and it is
+    kept out of prob_max / prob_mean; the flag is still taken from the input statistics as well as from the logits.
 
     fs / model_fs: the sampling rates of the recording and of the model's training data.  When both are given and differ,
     the recording is resampled on the device by up/down = model_fs/fs (resample.rational_ratio; ValueError when the ratio

@@ -3,7 +3,7 @@ for `ecg_gradcam_fwd` and for the fixture tests/golden/g9_gradcam.npz.  Numpy on
 
 Behind the last Conv1d the model is eval BatchNorm -> ReLU -> MaxPool1d(2) -> mean -> linear map(s).  With A the conv
 output, z = A*scale + shift and U = d logit / d (pooled feature):
-    cnt[n,c]     = #{ j < Lp : max(z[2j], z[2j+1]) > 0 },  Lp = Lo // 2
+    cnt[n,c]     = #{ j < Lp : not max(z[2j], z[2j+1]) <= 0 },  Lp = Lo // 2     (the max of a pair with a NaN is NaN)
     alpha[n,k,c] = U[n,k,c] * scale[c] * cnt[n,c] / (Lp * Lo)
     raw[n,k,t]   = max(0, sum_c alpha[n,k,c] * A[n,c,t])
 """
@@ -29,7 +29,7 @@ def closed_form(A, scale, shift, U):
     N, C, Lo = A.shape
     Lp = Lo // 2
     zp = pair_max(A, scale, shift)
-    cnt = (zp > 0).sum(-1).astype(F64)
+    cnt = (~(zp <= 0)).sum(-1).astype(F64)          # (a NaN pair counts: torch's ReLU backward passes the gradient at a NaN)
     g = np.maximum(zp, 0).mean(-1)
     U = np.asarray(U, F64)
     if U.ndim == 2:

@@ -216,6 +216,7 @@ def test_invalid_windows_are_flagged_and_left_out(hip):
     want = torch.ones(2, 5, dtype=torch.bool)
     want[0, 2] = want[0, 3] = False
     assert torch.equal(s.finite.cpu(), want)
+    assert torch.isnan(s.logits[0, 2]).all()                 # the NaN lead comes out as NaN logits, as stock torch gives
     keep = s.prob[0][[0, 1, 4]]
     assert torch.equal(s.prob_max[0], keep.amax(0)) and torch.equal(s.prob_mean[0], keep.mean(0))
     assert torch.equal(s.prob_max[1], s.prob[1].amax(0)) and torch.equal(s.prob_mean[1], s.prob[1].mean(0))

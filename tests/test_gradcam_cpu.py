@@ -97,6 +97,49 @@ def test_float64_closed_form_matches_every_fixture_entry(name):
         assert zeros == 2 * ZERO_CAMS                # the same three (window, class) pairs at both lengths
 
 
+def test_closed_form_propagates_nan_like_torch_autograd():
+    """The restatement on an activation with a NaN against stock torch autograd through eval BatchNorm (folded) -> ReLU ->
+    MaxPool1d(2) -> mean -> linear: the pooled feature is NaN, the pair with the NaN counts (ReLU backward passes the
+    gradient there, the pool routes to the NaN), alpha stays finite, raw is NaN at that time step only, and the
+    normalised rows are NaN throughout.  NaN in the first slot, the second, both, and in the unpooled last sample."""
+    rng = np.random.default_rng(1)
+    N, C, Lo, K = 2, 8, 11, 3
+    scale = rng.uniform(0.5, 1.5, C) * rng.choice([-1.0, 1.0], C)
+    shift = rng.uniform(-0.5, 0.5, C)
+    U = rng.standard_normal((K, C))
+    for spots in ([4], [5], [4, 5], [10]):
+        A = rng.standard_normal((N, C, Lo))
+        A[1, 3, spots] = np.nan
+        ref = GR.closed_form(A, scale, shift, U)
+        At = torch.from_numpy(A).requires_grad_(True)
+        z = At * torch.from_numpy(scale)[None, :, None] + torch.from_numpy(shift)[None, :, None]
+        g = torch.nn.functional.max_pool1d(torch.relu(z), 2).mean(-1)
+        assert np.array_equal(np.isnan(g.detach().numpy()), np.isnan(ref["g"]))
+        np.testing.assert_allclose(np.nan_to_num(g.detach().numpy()), np.nan_to_num(ref["g"]), atol=1e-12)
+        for k in range(K):
+            grad, = torch.autograd.grad((g * torch.from_numpy(U[k])[None, :]).sum(), At, retain_graph=True)
+            alpha = grad.mean(-1).numpy()                               # GradCAM1D's channel weights
+            assert np.isfinite(alpha).all()
+            np.testing.assert_allclose(alpha, ref["alpha"][:, k], atol=1e-12)
+            raw = torch.relu((grad.mean(-1, keepdim=True) * At.detach()).sum(1)).numpy()
+            assert np.array_equal(np.isnan(raw), np.isnan(ref["raw"][:, k]))
+            np.testing.assert_allclose(np.nan_to_num(raw), np.nan_to_num(ref["raw"][:, k]), atol=1e-12)
+            for norm in (1, 2):
+                cam = torch.from_numpy(raw)
+                if norm == 1:
+                    cam = cam - cam.min(-1, keepdim=True).values
+                    mx = cam.max(-1, keepdim=True).values
+                    cam = torch.where(mx > 0, cam / mx, cam)
+                    cam = torch.nn.functional.interpolate(cam[:, None], size=20, mode="linear", align_corners=False)[:, 0]
+                else:
+                    cam = torch.nn.functional.interpolate(cam[:, None], size=20, mode="linear", align_corners=False)[:, 0]
+                    cam = cam - cam.min(-1, keepdim=True).values
+                    cam = cam / (cam.max(-1, keepdim=True).values + 1e-8)
+                want = GR.finish(ref["raw"][:, k], 20, norm)
+                assert np.array_equal(np.isnan(cam.numpy()), np.isnan(want)), (spots, k, norm)
+                assert np.isnan(want[1]).all() and np.isfinite(want[0]).all()
+
+
 def test_resampling_rule_is_torchs():
     rng = np.random.default_rng(3)
     for Lo, S in [(2, 5), (63, 777), (125, 1000), (625, 5000), (1250, 1000), (7, 7)]:
