@@ -563,6 +563,22 @@ int ecg_wfdb16_windows(const int16_t *d, const double *gain, const int *baseline
 int ecg_wfdb16_windows_resampled(const int16_t *d, const double *gain, const int *baseline, const float *taps,
                                  float *out, float *stats, int R, int Ttot, int leads, int T, int first, int hop,
                                  int W, int last_start, int up, int down, int ntap, int half, ecg_stream_t stream);
+/* Zero-phase FIR conditioning (baseline-wander high-pass, mains notch: ecg_hip/filter.py) between the DAC / resample step
+ * and the z-score.  x [R][leads][Ttot] is the physical fp32 recording, lead-major — what ecg_wfdb16_windows /
+ * ecg_wfdb16_windows_resampled write with T = the whole recording, W = 1, stats = NULL; only 4-byte alignment is assumed.
+ * c [half+1] fp32 on the device, caller-owned, the one-sided taps of a symmetric FIR h of length 2*half+1:
+ * c[i] = h[half+i] = h[half-i].  The filtered recording y has Ttot samples,
+ *     acc = c[0]*x[n];  for i = 1 .. half ascending:  acc = acc + c[i] * (x[clamp(n-i, 0, Ttot-1)] + x[clamp(n+i, 0, Ttot-1)])
+ *     y[n] = acc
+ * every add and every multiply a separately rounded fp32 operation, all `half` terms added (zero taps included), the
+ * symmetric pair added first, the recording's ends edge-held by the clamp: y[n] depends on n and the recording only,
+ * never on the window that asks.  A NaN sample makes y NaN for every n within `half` samples of it on that lead (more
+ * where the clamp repeats it): a long filter widens what an invalid sample poisons.
+ * Windows are placed on y by the rule above: out [R][W][leads][T]; stats [R*W*leads][2] -> the windows are z-scored in
+ * place by ecg_zscore_rows, or NULL to stop at the filtered physical windows.  ECG_EINVAL before any launch unless
+ * half in [0,4096], leads in [1,16], the window rule holds against Ttot, R*W <= 65535 (R*W*leads <= 65535 with stats). */
+int ecg_fir_windows(const float *x, const float *c, float *out, float *stats, int R, int Ttot, int leads, int T,
+                    int first, int hop, int W, int last_start, int half, ecg_stream_t stream);
 /* Per-window time series back onto the recording's axis: v [R][W][K][T] (K series per window, windows placed by the
  * rule above) -> out [R][K][Ttot], the mean over the windows that cover a sample:
  *     acc = 0.0f;  for w ascending with start(w) <= t < start(w)+T:  acc = acc + v[r][w][k][t - start(w)]

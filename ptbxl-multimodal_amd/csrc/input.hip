@@ -24,6 +24,7 @@
 // conversion and the z-score, reading the same int16 stream in place (its arithmetic is stated above the kernel);
 // ecg_zscore_rows then normalises the windows it wrote.
 #include "common.h"
+#include "windows.h"        // WindowSrc, window_start, check_windows, kMaxLeads
 
 // hipcc contracts a*b+c into an fma by default (-ffp-contract=fast) — and does so even through the
 // __fmul_rn/__fadd_rn wrappers, whose bodies are compiled under the header's own state: one rounding
@@ -35,20 +36,6 @@ namespace ecg {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kTT = 256;        // time samples per transpose tile
-constexpr int kMaxLeads = 16;
-
-// Where the windows of a launch lie in their recordings d [R][Ttot][leads]: window b = r*W + w of the
-// grid starts at sample first + w*hop of recording r — or at last_start when that is >= 0 and w is the
-// last window (the "shifted tail" that ends with the recording).  Pre-cut windows [B][T][leads] are the
-// case Ttot == T, W == 1.  A start is any sample index: the source is only ever read as int16.
-struct WindowSrc {
-    long long Ttot;
-    int W, first, hop, last_start;
-};
-
-__device__ __forceinline__ long long window_start(const WindowSrc &s, int w) {
-    return (s.last_start >= 0 && w == s.W - 1) ? (long long)s.last_start : s.first + (long long)w * s.hop;
-}
 
 // -> recording index r (gain / baseline row); src = first sample of the window
 __device__ __forceinline__ int window_source(const WindowSrc &s, int b, int leads, const int16_t *d,
@@ -398,21 +385,6 @@ ECG_API int ecg_zscore_rows(const float *x, float *out, float *stats, int rows, 
     hipLaunchKernelGGL(zscore_apply_kernel, dim3(cdiv(vec ? T4 : T, 256), rows), dim3(256), 0, st, x, stats,
                        out, T, T4);
     return check_launch("zscore_apply_kernel");
-}
-
-// The window rule on the host: every start inside [0, Ttot - T], checked before any launch.
-static int check_windows(const char *who, int R, int Ttot, int T, int first, int hop, int W, int last_start) {
-    ECG_REQUIRE(R > 0 && T > 0, "%s: R=%d T=%d must be > 0", who, R, T);
-    ECG_REQUIRE(hop >= 1 && W >= 1, "%s: hop=%d W=%d must be >= 1", who, hop, W);
-    ECG_REQUIRE(T <= Ttot, "%s: window T=%d longer than the recording Ttot=%d", who, T, Ttot);
-    ECG_REQUIRE(last_start >= -1 && last_start <= Ttot - T, "%s: last_start=%d outside [-1, Ttot-T=%d]", who,
-                last_start, Ttot - T);
-    const int wreg = last_start >= 0 ? W - 1 : W;       // windows on the first + w*hop lattice
-    ECG_REQUIRE(first >= 0, "%s: first=%d must be >= 0", who, first);
-    ECG_REQUIRE(wreg == 0 || first + (long long)(wreg - 1) * hop <= Ttot - T,
-                "%s: window %d starts at %lld, past Ttot-T=%d", who, wreg - 1, first + (long long)(wreg - 1) * hop,
-                Ttot - T);
-    return ECG_OK;
 }
 
 // One plan for pre-cut windows and for windows read in place out of recordings: the fused int16 -> z-scored

@@ -9,6 +9,7 @@ stock torch layers the modules inherit from, as the reference does on a GPU-less
 `ecg_hip.grad_cam` is batched Grad-CAM at the last Conv1d: a closed form on the GPU, the hook algorithm elsewhere.
 `ecg_hip.score_recording` scores a continuous recording of any length: sliding windows read in place, stitched CAMs.
 A recording at another sampling rate than the model's is resampled on the device (`ecg_hip.resample`, fs= / model_fs=).
+A raw recording is conditioned there too: a zero-phase baseline-wander high-pass and mains notch (`ecg_hip.filter`, filter=).
 """
 from ._lib import EcgHipError, LIB_PATH, load  # noqa: F401
 

@@ -955,6 +955,43 @@ def _resampled_call(d, gain, baseline, taps, window, first, hop, W, last_start, 
     return (x, stats) if normalize and return_stats else x
 
 
+def fir_windows(x, taps, window, first, hop, W, last_start=-1, normalize=True, return_stats=False):
+    """Zero-phase FIR conditioning of physical recordings x fp32 [R, leads, Ttot] (what wfdb16_windows /
+    wfdb16_windows_resampled give for window = the whole recording, W = 1, normalize=False), then the windows of the
+    window rule cut out of the filtered recording and z-scored: -> fp32 [R, W, leads, window] (stats [R*W*leads, 2] with
+    return_stats; normalize=False stops at the filtered physical windows).  taps: the full symmetric filter
+    [2*half + 1] (ecg_hip.filter designs them) or what filter.one_sided returns; half <= 4096.  A filtered sample depends
+    on its index and the recording only (ends edge-held), so every window is a bitwise slice of fir_filter's output; a NaN
+    sample poisons every output within `half` samples of it on its lead."""
+    from .filter import device_one_sided
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise L.EcgHipError("fir_windows: a CPU tensor reached the HIP input step; x must be on the GPU")
+    if x.dtype != torch.float32:
+        raise L.EcgHipError(f"fir_windows: x must be float32 (the physical recording), got {x.dtype}")
+    if x.dim() != 3:
+        raise L.EcgHipError("fir_windows: x must be [R, leads, Ttot]")
+    c, half = device_one_sided(taps, x.device)
+    return _fir_call(_contig(x), c, window, first, hop, W, last_start, half, normalize, return_stats)
+
+
+def _fir_call(x, c, window, first, hop, W, last_start, half, normalize=True, return_stats=False):
+    """ecg_fir_windows with caller-made one-sided taps c fp32 [half+1] on the device (the ABI's own argument list)."""
+    R, leads, Ttot = x.shape
+    out = torch.empty(R, max(int(W), 0), leads, max(int(window), 0), dtype=torch.float32, device=x.device)
+    stats = _empty(out, out.shape[0] * out.shape[1] * leads, 2) if normalize else None
+    _call("ecg_fir_windows", _f32(x), _f32(c), _f32(out), _f32(stats), R, Ttot, leads, int(window), int(first), int(hop),
+          int(W), int(last_start), int(half), _st())
+    return (out, stats) if normalize and return_stats else out
+
+
+def fir_filter(x, taps):
+    """The whole filtered recording, fp32 [R, leads, Ttot] for x [R, leads, Ttot]: fir_windows with one window that is
+    the recording, not z-scored — the signal a CAM of a filtered score_recording is plotted over."""
+    if torch.is_tensor(x) and x.dim() == 3:
+        return fir_windows(x, taps, x.shape[2], 0, 1, 1, -1, normalize=False)[:, 0]
+    return fir_windows(x, taps, 0, 0, 1, 1)        # raises fir_windows' own error for this x
+
+
 def wfdb16_to_windows_sliding(d, gain, baseline, window, hop, tail="shift", normalize=True, return_stats=False):
     """wfdb16_to_windows for recordings longer than one window: d int16 [R, Ttot, leads] is cut into the windows of
     recording.window_plan(Ttot, window, hop, tail) without an overlapping copy ever existing.

@@ -12,6 +12,10 @@ sample is scored; tail="drop" leaves the remainder unscored.
 A recording sampled at another rate than the model's (`fs` != `model_fs`) is resampled on the device by
 `ecg_wfdb16_windows_resampled` (ecg_hip/resample.py) between the DAC conversion and the z-score; the window rule, the
 chunks and the stitched CAMs then live on the model-rate axis of resampled_length(Ttot, up, down) samples.
+
+A raw ambulatory recording carries baseline wander and mains hum that the per-window z-score cannot remove (drift of a
+few mV dominates the std).  `filter=` conditions it on the device: the physical (or resampled) recording is written once
+as fp32 and `ecg_fir_windows` (ecg_hip/filter.py) cuts the windows out of its zero-phase filtered form.
 """
 import torch
 
@@ -79,7 +83,7 @@ def _record_level(prob, finite):
 
 
 def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift", batch_size=256, x_demo=None,
-                    cam_classes=None, cam_normalize=None, fs=None, model_fs=None):
+                    cam_classes=None, cam_normalize=None, fs=None, model_fs=None, filter=None):
     """Score recordings d int16 [Ttot, leads] or [R, Ttot, leads] (on the GPU, the .dat layout) with `model` in eval mode.
 
     gain float64 / baseline int32 [leads] or [R, leads]; window: samples per model input; hop: default window // 2;
@@ -100,6 +104,16 @@ def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift",
     needs a term above 512): window, hop, starts, cam and cover are then on the MODEL-RATE axis of
     resample.resampled_length(Ttot, up, down) samples, and model-axis sample t lies at source time t*down/up samples.
     The CAMs are not mapped back to the source axis.  With either None, or both equal, nothing is resampled.
+
+    filter: an ecg_hip.filter.FilterSpec (FilterSpec() is a 0.5 Hz baseline-wander high-pass; notch=50 adds a mains
+    notch), or symmetric FIR taps (full, or filter.one_sided's) taken as designed for the axis the windows live on.  A
+    spec is designed at that axis' rate — model_fs where the recording is resampled, otherwise fs — and raises ValueError
+    when that rate was not given.  The physical (or resampled) fp32 recording of the recordings in flight is then
+    written once per recording group of plan_chunks and every chunk comes from functional.fir_windows: zero phase, ends
+    edge-held, a filtered sample independent of the window that asks (functional.fir_filter gives the whole conditioned
+    signal).  An invalid sample poisons every filtered sample within `half` taps of it on its lead — 363 samples at
+    100 Hz, 1813 at 500 Hz for the default high-pass — so a long filter widens the set of windows flagged not finite.
+    None (default): no filter, no further launch, today's bits.
     -> RecordingScore."""
     if not (torch.is_tensor(d) and d.is_cuda):
         raise L.EcgHipError("score_recording: a CPU tensor reached the HIP input step; d must be on the GPU "
@@ -131,13 +145,26 @@ def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift",
             Ttot = resampled_length(Ttot, *ratio)
     plan = window_plan(Ttot, window, window // 2 if hop is None else hop, tail)
     _, hop, W, _, starts = plan
+    taps = None
+    if filter is not None:
+        from .filter import FilterSpec, one_sided
+        axis_fs = fs if ratio is None else model_fs
+        taps = one_sided(filter.taps(axis_fs) if isinstance(filter, FilterSpec) else filter)
+    phys, phys_of = None, None      # the fp32 recordings [r1-r0, leads, Ttot] of the group in flight (filter only)
     cams = None if cam_classes is None else [int(k) for k in cam_classes]
     d = hipF._contig(d)
 
     logits = v = None
     ok = torch.empty(R, W, dtype=torch.bool, device=dev)
     for r0, r1, w0, first, Wc, last in plan_chunks(R, plan, int(batch_size)):
-        if ratio is None:
+        if taps is not None:
+            if phys_of != (r0, r1):
+                whole = (d[r0:r1], gain[r0:r1], baseline[r0:r1], Ttot, 0, 1, 1, -1)
+                phys = (hipF.wfdb16_windows(*whole, normalize=False) if ratio is None else
+                        hipF.wfdb16_windows_resampled(*whole, *ratio, normalize=False))[:, 0]
+                phys_of = (r0, r1)
+            x, stats = hipF.fir_windows(phys, taps, window, first, hop, Wc, last, return_stats=True)
+        elif ratio is None:
             x, stats = hipF.wfdb16_windows(d[r0:r1], gain[r0:r1], baseline[r0:r1], window, first, hop, Wc, last,
                                            return_stats=True)
         else:
@@ -180,7 +207,8 @@ def score_wfdb_record(record_path, model, model_fs=None, **kw):
     """score_recording for a WFDB format-16 record of any length on disk (record_path without extension, as
     ecg_hip.wfdb16.read_record takes it): the samples are uploaded once, as int16, to the device of the model.
     model_fs: the rate the model was trained at; the record is resampled on the device when its header's rate differs.
-    None (default): the record is scored at its own rate, whatever the header says."""
+    None (default): the record is scored at its own rate, whatever the header says.  filter= (score_recording) is passed
+    through: a FilterSpec is designed at model_fs when the record is resampled, otherwise at the header's rate."""
     from .wfdb16 import read_record
     rec = read_record(record_path)
     dev = next(model.parameters()).device

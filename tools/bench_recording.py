@@ -2,7 +2,7 @@
 score_recording end to end.
 
     python tools/bench_recording.py [--hours 1] [--rounds 7] [--iters 20] [--out profiles/recording_bench.json]
-                                    [--legs recording,resample] [--resample-out profiles/resample_bench.json]
+                                    [--legs recording,resample,filter] [--resample-out profiles/resample_bench.json]
 
 Workloads: one 12-lead recording of --hours at 500 Hz (window 5000) and at 100 Hz (window 1000), hop = window / 2.
   (a) sliding   ecg_wfdb16_windows on the recording in place
@@ -19,6 +19,16 @@ Leg "resample": the same one-hour 12-lead recording at 500 Hz scored by the 12x1
 alternating in one process like (a) and (b), together with the streaming plan spelled out (the resampling launch, then
 ecg_zscore_rows in place) against the plan the entry point picks; the resampling launch alone (normalize=False) is also rated against the bytes it must
 move, 2*down/up B in + 4 B out per output sample.  Written to --resample-out.
+
+Leg "filter" (not in the default --legs): the zero-phase FIR conditioning step, ecg_fir_windows.
+  (f) fir_windows on --batch windows of 12x1000 with the default 100 Hz high-pass (half 363), and of 12x5000 with the
+      500 Hz high-pass + 50 Hz notch (half 2720): int16 -> physical fp32 (wfdb16_to_windows(normalize=False)) -> fir_windows
+  (g) score_recording(filter=...) on the one-hour recording at both rates, fp32, no CAMs
+each against (a) the unfiltered path on the same plan (wfdb16_to_windows / score_recording without filter: what the
+feature adds) and (b) what a user would otherwise run on the device: torch.nn.functional.conv1d with the same taps over
+the replicate-padded fp32 recording, then cutting and zscore_per_lead.  The three alternate in one process, --rounds
+times; the calls per round are cut down where one call is long, so that a round stays near a third of a second.
+Written into --out under "filter" (the other entries of that file are kept).
 Fails when no GPU is visible: no number here means anything on a CPU.
 """
 import argparse
@@ -129,6 +139,134 @@ def resample_leg(a):
         json.dump([line], f, indent=1)
 
 
+def _rounds(fns, a):
+    """{name: [ms per call, ...]}: the functions alternate, a.rounds times; calls per round from one timed call each."""
+    iters = {}
+    for k, fn in fns.items():
+        prime(fn, 0.3)
+        iters[k] = max(1, min(a.iters, int(300.0 / max(timed(fn, 1), 1e-3))))
+    ms = {k: [] for k in fns}
+    for _ in range(a.rounds):
+        for k, fn in fns.items():
+            ms[k].append(timed(fn, iters[k]))
+    return ms, iters
+
+
+def _report(metric, workload, ms, iters, extra):
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    line = {"metric": metric, "value": round(med["filtered"], 4), "unit": "ms", "config": {"workload": workload},
+            **{f"{k}_ms": [round(t, 4) for t in v] for k, v in ms.items()},
+            **{f"{k}_median_ms": round(m, 4) for k, m in med.items()},
+            **{f"{k}_spread_ms": round(max(v) - min(v), 4) for k, v in ms.items()},
+            "calls_per_round": iters,
+            "filtered_over_unfiltered": round(med["filtered"] / med["unfiltered"], 3),
+            "added_ms": round(med["filtered"] - med["unfiltered"], 4), **extra}
+    if "stock" in med:
+        line["stock_over_filtered"] = round(med["stock"] / med["filtered"], 3)
+    print(json.dumps(line), flush=True)
+    return line
+
+
+def filter_leg(a):
+    """ecg_fir_windows and score_recording(filter=) against the unfiltered path and against stock torch conv1d."""
+    from ecg_hip import functional as F
+    from ecg_hip.filter import FilterSpec, one_sided
+    from ecg_hip.recording import plan_chunks, score_recording, window_plan
+    from src.models.ecg_cnn import ECGCNN
+    from src.utils.seed import set_seed
+    conv1d, pad = torch.nn.functional.conv1d, torch.nn.functional.pad
+    res = []
+    for fs, window, spec in ((100, 1000, FilterSpec()), (500, 5000, FilterSpec(notch=50))):
+        h = spec.taps(fs)
+        c = one_sided(h)
+        half = len(c) - 1
+        w = torch.from_numpy(h.astype(np.float32)).cuda().reshape(1, 1, -1).expand(LEADS, 1, -1).contiguous()
+        rng = np.random.default_rng(fs + 1)
+        # (f) a batch of pre-cut windows
+        B = a.batch
+        d = torch.from_numpy(rng.integers(-3000, 3000, size=(B, window, LEADS)).astype(np.int16)).cuda()
+        gain = torch.full((B, LEADS), 1000.0, dtype=torch.float64).cuda()
+        base = torch.zeros(B, LEADS, dtype=torch.int32).cuda()
+
+        def filtered():
+            return F.fir_windows(F.wfdb16_to_windows(d, gain, base, normalize=False), c, window, 0, 1, 1)[:, 0]
+
+        def kernel_only(p=F.wfdb16_to_windows(d, gain, base, normalize=False)):
+            return F.fir_windows(p, c, window, 0, 1, 1, normalize=False)
+
+        def unfiltered():
+            return F.wfdb16_to_windows(d, gain, base)
+
+        def stock():
+            p = pad(F.wfdb16_to_windows(d, gain, base, normalize=False), (half, half), mode="replicate")
+            y = conv1d(p, w, groups=LEADS)
+            return F.zscore_per_lead(y, out=y)
+
+        print(f"filter leg: {fs} Hz, half {half}: windows", file=sys.stderr, flush=True)
+        # same filter, another summation order and fused multiply-adds: close, not bit-identical
+        diff = float((filtered() - stock()).abs().max())
+        assert diff <= 1e-3, diff
+        ms, iters = _rounds({"filtered": filtered, "unfiltered": unfiltered, "stock": stock, "kernel_only": kernel_only}, a)
+        n = B * window * LEADS
+        mk = float(np.median(ms["kernel_only"]))
+        res.append(_report("fir_windows_ms", f"{B} windows of {LEADS}x{window} at {fs} Hz, {spec!r} (half {half}), "
+                           "int16 -> physical -> filtered -> z-scored fp32", ms, iters,
+                           {"max_abs_diff_filtered_vs_stock": diff, "half": half,
+                            "kernel_fp32_ops_per_s": round(n * (3.0 * half + 1) / (mk * 1e-3), 1),
+                            "kernel_tap_pairs_per_s": round(n * float(half) / (mk * 1e-3), 1)}))
+        # (g) the one-hour recording
+        Ttot, hop = int(a.hours * 3600 * fs), window // 2
+        d1 = torch.from_numpy(rng.integers(-3000, 3000, size=(1, Ttot, LEADS)).astype(np.int16)).cuda()
+        g1, b1 = gain[:1].contiguous(), base[:1].contiguous()
+        plan = window_plan(Ttot, window, hop)
+        W, starts = plan[2], torch.tensor(plan[4], device="cuda")
+        set_seed(42)
+        model = ECGCNN(num_labels=5).cuda().eval()
+
+        def score(flt):
+            return score_recording(model, d1, g1, b1, window=window, hop=hop, batch_size=a.batch, fs=fs, filter=flt).logits
+
+        def stock_score():
+            p = pad(F.wfdb16_to_windows(d1, g1, b1, normalize=False), (half, half), mode="replicate")
+            y = conv1d(p, w, groups=LEADS)[0]                                           # [leads][Ttot]
+            out = []
+            for _, _, w0, _, Wc, _ in plan_chunks(1, plan, a.batch):
+                idx = starts[w0:w0 + Wc, None] + torch.arange(window, device="cuda")[None, :]
+                x = y[:, idx].permute(1, 0, 2).contiguous()
+                with torch.no_grad():
+                    out.append(model(F.zscore_per_lead(x, out=x)))
+            return torch.cat(out)
+
+        print(f"filter leg: {fs} Hz, half {half}: score_recording", file=sys.stderr, flush=True)
+        fns = {"filtered": lambda: score(c), "unfiltered": lambda: score(None)}
+        extra = {"windows": W, "half": half}
+        try:
+            extra["max_abs_logit_diff_filtered_vs_stock"] = float((score(c)[0] - stock_score()).abs().max())
+            fns["stock"] = stock_score
+        except RuntimeError as e:           # stock torch may have no plan for a filter this long on a signal this long
+            extra["stock_error"] = str(e).splitlines()[0][:200]
+        ms, iters = _rounds(fns, a)
+        extra["windows_per_s"] = round(W / (float(np.median(ms["filtered"])) * 1e-3), 1)
+        res.append(_report("score_recording_filtered_ms", f"ECGCNN(5) score_recording, {a.hours:g} h at {fs} Hz, window "
+                           f"{window}, hop {hop}, {W} windows in chunks of {a.batch}, fp32, no CAMs, {spec!r}", ms, iters,
+                           extra))
+    return res
+
+
+def _write(path, lines=None, filt=None):
+    """profiles/recording_bench.json: the recording leg's lines, then {"filter": [...]}; a leg replaces its own part."""
+    old = []
+    if os.path.exists(path):
+        with open(path) as f:
+            old = json.load(f)
+    old_filt = [e for e in old if isinstance(e, dict) and "filter" in e]
+    old_lines = [e for e in old if not (isinstance(e, dict) and "filter" in e)]
+    out = (old_lines if lines is None else lines) + (old_filt if filt is None else [{"filter": filt}])
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--hours", type=float, default=1.0)
@@ -149,6 +287,8 @@ def main():
     _lib.call("ecg_check_device")
     if "resample" in a.legs.split(","):
         resample_leg(a)
+    if "filter" in a.legs.split(","):
+        _write(a.out, filt=filter_leg(a))
     if "recording" not in a.legs.split(","):
         return
     res = []
@@ -218,9 +358,7 @@ def main():
                             "orchestration_cost": round((a.batch / eval_ms) / (W / ms), 3)}
                     print(json.dumps(line), flush=True)
                     res.append(line)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
+    _write(a.out, lines=res)
 
 
 if __name__ == "__main__":
