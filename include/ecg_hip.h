@@ -579,6 +579,22 @@ int ecg_wfdb16_windows_resampled(const int16_t *d, const double *gain, const int
  * half in [0,4096], leads in [1,16], the window rule holds against Ttot, R*W <= 65535 (R*W*leads <= 65535 with stats). */
 int ecg_fir_windows(const float *x, const float *c, float *out, float *stats, int R, int Ttot, int leads, int T,
                     int first, int hop, int W, int last_start, int half, ecg_stream_t stream);
+/* The step before all of the above: the BYTES of one WFDB .dat file -> the int16 stream d [Ttot][leads_out] the entry points
+ * above read.  raw / nbytes: device bytes of the file from its first sample byte (the caller has dropped the header's byte
+ * offset; raw may sit at ANY byte address).  fmt: 16 (little-endian int16), 61 (big-endian int16), 160 (little-endian
+ * uint16 - 32768), 80 (byte - 128) or 212 (pair p of samples 2p, 2p+1 in bytes b0 b1 b2 at 3p: b0 | (b1 & 0x0F) << 8 and
+ * b2 | (b1 & 0xF0) << 4, sign-extended from 12 bits).  frame: signals interleaved in this file = samples per time frame.
+ * slot, skew, col: HOST arrays of ncols <= 16 ints (copied into the launch arguments); for 0 <= t < Ttot and each j
+ *     out[t*leads_out + col[j]] = stored sample number (t + skew[j])*frame + slot[j]        (64-bit indices)
+ * The format's invalid code (-2048 for 212, -128 for 80, -32768 otherwise) becomes -32768, which the kernels above turn
+ * into NaN, and so does a sample whose bytes are not wholly inside nbytes (the tail a skew reaches past; a 212 file with
+ * an odd sample count ends after b1 of its last pair and that sample is valid).  No byte outside [raw, raw + nbytes) is
+ * loaded.  One call per file: the calls of a multi-file record write disjoint columns of the same out, and a call that
+ * covers only some of the leads_out columns leaves the others untouched.  Integer arithmetic only.
+ * ECG_EINVAL before any launch: null pointers, another fmt, frame < 1, ncols or leads_out outside [1,16], Ttot < 1,
+ * nbytes < 0, slot outside [0,frame), skew < 0, col outside [0,leads_out) or repeated, (Ttot + skew)*frame > 2^60. */
+int ecg_wfdb_decode16(const uint8_t *raw, long long nbytes, int fmt, int frame, const int *slot, const int *skew,
+                      const int *col, int ncols, int16_t *out, int Ttot, int leads_out, ecg_stream_t stream);
 /* Per-window time series back onto the recording's axis: v [R][W][K][T] (K series per window, windows placed by the
  * rule above) -> out [R][K][Ttot], the mean over the windows that cover a sample:
  *     acc = 0.0f;  for w ascending with start(w) <= t < start(w)+T:  acc = acc + v[r][w][k][t - start(w)]

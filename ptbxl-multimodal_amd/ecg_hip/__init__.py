@@ -10,6 +10,7 @@ stock torch layers the modules inherit from, as the reference does on a GPU-less
 `ecg_hip.score_recording` scores a continuous recording of any length: sliding windows read in place, stitched CAMs.
 A recording at another sampling rate than the model's is resampled on the device (`ecg_hip.resample`, fs= / model_fs=).
 A raw recording is conditioned there too: a zero-phase baseline-wander high-pass and mains notch (`ecg_hip.filter`, filter=).
+WFDB records in formats 16, 61, 80, 160 and 212, with skews, offsets and several files, are decoded on the device (`ecg_hip.wfdbraw`).
 """
 from ._lib import EcgHipError, LIB_PATH, load  # noqa: F401
 

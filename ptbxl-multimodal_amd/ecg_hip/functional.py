@@ -1005,6 +1005,43 @@ def wfdb16_to_windows_sliding(d, gain, baseline, window, hop, tail="shift", norm
     return (*out, plan) if isinstance(out, tuple) else (out, plan)
 
 
+def wfdb_decode16(files, layout, n_samp, columns=None):
+    """The packed bytes of a WFDB record's .dat files -> the int16 stream [n_samp, len(columns)] the input step reads
+    (time-major, as a format-16 file stores it), decoded on the device by ecg_wfdb_decode16: one launch per file.
+
+    files: uint8 CUDA tensors, one per .dat file, holding the file's bytes as they are.  layout: one entry per signal of
+    the record (wfdbraw.RawSignal, or anything with these attributes): file (index into files), fmt (16, 61, 80, 160 or
+    212), frame (signals interleaved in that file), slot (position inside a frame), skew (frames the signal is stored
+    late) and offset (bytes before the file's first sample; honoured by slicing, never by copying).  columns: indices
+    into layout, in output order (default: every signal).  The format's invalid code, and every sample a skew or a short
+    file puts past the end of the bytes, comes out as -32768 — what the window kernels turn into NaN."""
+    layout = list(layout)
+    columns = list(range(len(layout))) if columns is None else [int(c) for c in columns]
+    n_samp, L_out = int(n_samp), len(columns)
+    if not 1 <= L_out <= 16:
+        raise L.EcgHipError(f"wfdb_decode16: {L_out} output columns outside [1,16]")
+    for f in files:
+        if not (torch.is_tensor(f) and f.is_cuda):
+            raise L.EcgHipError("wfdb_decode16: a CPU tensor reached the HIP input step; the file bytes must be on the GPU")
+        if f.dtype != torch.uint8 or f.dim() != 1:
+            raise L.EcgHipError("wfdb_decode16: files must be one-dimensional uint8 tensors (the .dat bytes as they are)")
+    by_file = {}
+    for j, c in enumerate(columns):
+        if not 0 <= c < len(layout):
+            raise L.EcgHipError(f"wfdb_decode16: column {c} outside the record's {len(layout)} signals")
+        by_file.setdefault(int(layout[c].file), []).append((j, layout[c]))
+    out = torch.empty(max(n_samp, 0), L_out, dtype=torch.int16, device=files[0].device if files else None)
+    for fi, sel in by_file.items():
+        s0 = sel[0][1]
+        if any((s.fmt, s.frame, s.offset) != (s0.fmt, s0.frame, s0.offset) for _, s in sel):
+            raise L.EcgHipError(f"wfdb_decode16: the signals of file {fi} disagree on format, frame size or byte offset")
+        raw = _contig(files[fi])[int(s0.offset):]           # a view: the kernel takes any byte address
+        _call("ecg_wfdb_decode16", raw.data_ptr(), raw.numel(),
+              int(s0.fmt), int(s0.frame), L.int_table([s.slot for _, s in sel]), L.int_table([s.skew for _, s in sel]),
+              L.int_table([j for j, _ in sel]), len(sel), L.ptr(out), n_samp, L_out, _st())
+    return out
+
+
 def overlap_mean(v, plan, Ttot, return_cover=False):
     """Per-window time series v fp32 [R, W, K, T] (windows placed by `plan`, a window_plan result) -> [R, K, Ttot]: at
     every sample the mean of the windows that cover it, added in ascending window order by the one lane that owns the

@@ -1,7 +1,8 @@
-"""Scoring a continuous recording: any WFDB format-16 signal longer than one training window (a rhythm strip, a Holter
-export) -> per-window logits, record-level probabilities and Grad-CAMs on the recording's own time axis.
+"""Scoring a continuous recording: any WFDB signal longer than one training window (a rhythm strip, a Holter export)
+-> per-window logits, record-level probabilities and Grad-CAMs on the recording's own time axis.
 
-The recording stays on the device as the int16 samples of its .dat file.  `ecg_wfdb16_windows` cuts the z-scored windows
+The recording stays on the device as the int16 samples of a format-16 .dat file (records stored otherwise — format 212,
+skews, several files — are decoded to that form on the device, ecg_hip.wfdbraw).  `ecg_wfdb16_windows` cuts the z-scored windows
 straight out of it (no overlapping copy), the windows go through the model's eval forward (or `ecg_hip.grad_cam`) in chunks
 of at most `batch_size`, and `ecg_windows_overlap_mean` averages the per-window CAMs where windows overlap.
 
@@ -203,14 +204,31 @@ def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift",
                           cam=cam, cover=cover, fs=fs if ratio is None else model_fs, source_len=source_len)
 
 
-def score_wfdb_record(record_path, model, model_fs=None, **kw):
-    """score_recording for a WFDB format-16 record of any length on disk (record_path without extension, as
-    ecg_hip.wfdb16.read_record takes it): the samples are uploaded once, as int16, to the device of the model.
+def score_wfdb_record(record_path, model, model_fs=None, leads=None, **kw):
+    """score_recording for a WFDB record of any length on disk (record_path without extension), on the device of the model.
     model_fs: the rate the model was trained at; the record is resampled on the device when its header's rate differs.
     None (default): the record is scored at its own rate, whatever the header says.  filter= (score_recording) is passed
-    through: a FilterSpec is designed at model_fs when the record is resampled, otherwise at the header's rate."""
-    from .wfdb16 import read_record
-    rec = read_record(record_path)
+    through: a FilterSpec is designed at model_fs when the record is resampled, otherwise at the header's rate.
+
+    leads: the signals to score, in the model's lead order — names matched against the header's descriptions (e.g.
+    wfdbraw.PTBXL_LEADS for a 15-signal PTB Diagnostic record) or signal indices; None: every signal, in header order.
+    A plain format-16 record (one .dat file, no skew, no byte offset) with leads=None is read by ecg_hip.wfdb16 and
+    uploaded as int16.  Every other record — formats 61, 80, 160 and 212, skews, byte offsets, several files, a lead
+    selection — goes through ecg_hip.wfdbraw: the files' bytes are uploaded as they are and ecg_wfdb_decode16 writes the
+    int16 stream on the device (the header checksums are verified there)."""
+    from .wfdb16 import parse_header, read_record
     dev = next(model.parameters()).device
-    return score_recording(model, torch.from_numpy(rec.d.astype("int16")).to(dev), torch.from_numpy(rec.gain).to(dev),
-                           torch.from_numpy(rec.baseline).to(dev), fs=rec.fs, model_fs=model_fs, **kw)
+    with open(record_path + ".hea", "r") as f:
+        sigs = parse_header(f.read())["signals"]
+    plain = leads is None and len({s["file"] for s in sigs}) == 1 and all(
+        s["fmt"] == 16 and s["spf"] == 1 and s["skew"] == 0 and s["offset"] == 0 for s in sigs)
+    if plain:
+        rec = read_record(record_path)
+        d, gain, baseline, fs = torch.from_numpy(rec.d.astype("int16")).to(dev), rec.gain, rec.baseline, rec.fs
+    else:
+        from .wfdbraw import read_raw_record, to_device
+        rec = read_raw_record(record_path)
+        d, gain, baseline = to_device(rec, dev, leads)
+        fs = rec.fs
+    return score_recording(model, d, torch.from_numpy(gain).to(dev), torch.from_numpy(baseline).to(dev), fs=fs,
+                           model_fs=model_fs, **kw)

@@ -2,7 +2,7 @@
 score_recording end to end.
 
     python tools/bench_recording.py [--hours 1] [--rounds 7] [--iters 20] [--out profiles/recording_bench.json]
-                                    [--legs recording,resample,filter] [--resample-out profiles/resample_bench.json]
+                                    [--legs recording,resample,filter,decode] [--resample-out profiles/resample_bench.json]
 
 Workloads: one 12-lead recording of --hours at 500 Hz (window 5000) and at 100 Hz (window 1000), hop = window / 2.
   (a) sliding   ecg_wfdb16_windows on the recording in place
@@ -29,6 +29,18 @@ feature adds) and (b) what a user would otherwise run on the device: torch.nn.fu
 the replicate-padded fp32 recording, then cutting and zscore_per_lead.  The three alternate in one process, --rounds
 times; the calls per round are cut down where one call is long, so that a round stays near a third of a second.
 Written into --out under "filter" (the other entries of that file are kept).
+
+Leg "decode" (not in the default --legs): the step before all of them, ecg_wfdb_decode16 — the bytes of a .dat file -> the
+int16 stream.  The one-hour 12-lead 500 Hz recording stored as format 212, and 12 of the 15 signals (by name, reordered) of a
+one-hour format-16 file at 1000 Hz.
+  (h) kernel   functional.wfdb_decode16 on the uploaded bytes
+  (i) torch    the same decode in torch tensor ops on the device (view(-1, 3), shifts and masks, stack; a column gather for
+               the format-16 file): the stock alternative, several passes over widened temporaries
+  (j) numpy    the decode on the host and an upload of the int16 result
+alternating in one process like the others.  The kernel is also rated against the bytes it must move (1.5 B in + 2 B out
+per sample for 212; 2 B + 2 B per selected sample for the selection), and its share of score_wfdb_record end to end (header,
+file read, upload, decode, checksum, scoring; host clock around a synchronise) is reported.  Written into --out under
+"decode".
 Fails when no GPU is visible: no number here means anything on a CPU.
 """
 import argparse
@@ -253,15 +265,115 @@ def filter_leg(a):
     return res
 
 
-def _write(path, lines=None, filt=None):
-    """profiles/recording_bench.json: the recording leg's lines, then {"filter": [...]}; a leg replaces its own part."""
+def decode_leg(a):
+    """ecg_wfdb_decode16 against the same decode in torch ops on the device and in numpy on the host."""
+    import tempfile
+    from ecg_hip import functional as F
+    from ecg_hip import wfdbraw
+    from ecg_hip.recording import score_wfdb_record
+    from src.models.ecg_cnn import ECGCNN
+    from src.utils.seed import set_seed
+    res = []
+    a = argparse.Namespace(**{**vars(a), "iters": max(a.iters, 2000)})     # a call is tens of microseconds: _rounds caps a round at 0.3 s
+    tmp = tempfile.mkdtemp(prefix="bench_decode_")
+    rng = np.random.default_rng(212)
+    names = list(wfdbraw.PTBXL_LEADS) + ["vx", "vy", "vz"]
+    order = rng.permutation(15)
+    for fmt, fs, n_sig, window in ((212, 500, LEADS, 5000), (16, 1000, 15, 5000)):
+        Ttot = int(a.hours * 3600 * fs)
+        lim = 2047 if fmt == 212 else 3000
+        d = rng.integers(-lim, lim, size=(Ttot, n_sig)).astype(np.int16)
+        path = os.path.join(tmp, f"rec{fmt}")
+        sig_names = list(wfdbraw.PTBXL_LEADS) if n_sig == LEADS else [names[i] for i in order]
+        wfdbraw.write_raw_record(path, d, fs, np.full(n_sig, 1000.0), np.zeros(n_sig, np.int32), fmt=fmt, sig_names=sig_names)
+        rec = wfdbraw.read_raw_record(path)
+        leads = None if n_sig == LEADS else wfdbraw.PTBXL_LEADS
+        cols = list(range(n_sig)) if leads is None else wfdbraw.select_leads(rec, leads)
+        raw_host = rec.files[0]
+        raw = torch.from_numpy(raw_host).cuda()
+        idx = torch.tensor(cols, device="cuda")
+
+        def kernel():
+            return F.wfdb_decode16([raw], rec.signals, Ttot, cols)
+
+        def decode_ops(b, xp):                      # the same statements for torch (device) and numpy (host)
+            if fmt == 16:
+                return b.view(xp.int16).reshape(Ttot, n_sig)
+            b = b[:3 * (Ttot * n_sig // 2)].reshape(-1, 3).astype(np.int32) if xp is np else \
+                b[:3 * (Ttot * n_sig // 2)].view(-1, 3).to(torch.int32)
+            even = b[:, 0] | ((b[:, 1] & 0x0F) << 8)
+            odd = b[:, 2] | ((b[:, 1] & 0xF0) << 4)
+            v = xp.stack([even, odd], 1).reshape(-1)
+            v = (v ^ 0x800) - 0x800
+            v = xp.where(v == -2048, -32768, v)
+            return (v.astype(np.int16) if xp is np else v.to(torch.int16)).reshape(Ttot, n_sig)
+
+        def stock():
+            v = decode_ops(raw, torch)
+            return v if leads is None else v.index_select(1, idx)
+
+        def host_numpy():
+            v = decode_ops(raw_host, np)
+            return torch.from_numpy(np.ascontiguousarray(v if leads is None else v[:, cols])).cuda()
+
+        want = d if leads is None else d[:, cols]
+        assert Ttot * n_sig % 2 == 0
+        for fn in (kernel, stock, host_numpy):
+            assert np.array_equal(fn().cpu().numpy(), want), fn.__name__
+        print(f"decode leg: format {fmt}, {Ttot} x {n_sig}", file=sys.stderr, flush=True)
+        ms, iters = _rounds({"kernel": kernel, "torch": stock, "numpy": host_numpy}, a)
+        med = {k: float(np.median(v)) for k, v in ms.items()}
+        n_out = Ttot * len(cols)
+        must = n_out * (3.5 if fmt == 212 else 4.0)
+        # end to end: header, file read, upload, decode, checksum, scoring
+        set_seed(42)
+        model = ECGCNN(num_labels=5).cuda().eval()
+
+        def e2e():
+            t0 = time.perf_counter()
+            score_wfdb_record(path, model, leads=leads, window=window, batch_size=a.batch)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+
+        e2e()
+        e2e_ms = [e2e() for _ in range(max(3, a.rounds // 2))]
+        line = {"metric": "wfdb_decode16_ms", "value": round(med["kernel"], 4), "unit": "ms",
+                "config": {"workload": f"{a.hours:g} h at {fs} Hz, format {fmt}, {n_sig} signals in the file, {len(cols)} decoded"
+                                       f"{'' if leads is None else ' (picked by name, reordered)'}: {raw_host.size} bytes -> "
+                                       f"int16 [{Ttot}][{len(cols)}]"},
+                **{f"{k}_ms": [round(t, 4) for t in v] for k, v in ms.items()},
+                **{f"{k}_median_ms": round(m, 4) for k, m in med.items()},
+                **{f"{k}_spread_ms": round(max(v) - min(v), 4) for k, v in ms.items()},
+                "calls_per_round": iters, "torch_over_kernel": round(med["torch"] / med["kernel"], 3),
+                "numpy_over_kernel": round(med["numpy"] / med["kernel"], 3),
+                "kernel_bytes_it_must_move": int(must), "kernel_GBps_of_those_bytes": round(must / (med["kernel"] * 1e-3) / 1e9, 1),
+                "kernel_frac_of_hbm": round(must / (med["kernel"] * 1e-3) / HBM_BYTES_PER_S, 4),
+                "score_wfdb_record_ms": [round(t, 2) for t in e2e_ms],
+                "score_wfdb_record_median_ms": round(float(np.median(e2e_ms)), 2),
+                "kernel_share_of_score_wfdb_record": round(med["kernel"] / float(np.median(e2e_ms)), 5)}
+        print(json.dumps(line), flush=True)
+        res.append(line)
+        for ext in (".hea", ".dat"):
+            os.remove(path + ext)
+    os.rmdir(tmp)
+    return res
+
+
+_SECTIONS = ("filter", "decode")
+
+
+def _write(path, lines=None, **sections):
+    """profiles/recording_bench.json: the recording leg's lines, then {"filter": [...]} and {"decode": [...]}; a leg
+    replaces its own part."""
     old = []
     if os.path.exists(path):
         with open(path) as f:
             old = json.load(f)
-    old_filt = [e for e in old if isinstance(e, dict) and "filter" in e]
-    old_lines = [e for e in old if not (isinstance(e, dict) and "filter" in e)]
-    out = (old_lines if lines is None else lines) + (old_filt if filt is None else [{"filter": filt}])
+    kept = {k: e for e in old if isinstance(e, dict) for k in _SECTIONS if k in e}
+    old_lines = [e for e in old if not (isinstance(e, dict) and any(k in e for k in _SECTIONS))]
+    for k, v in sections.items():
+        kept[k] = {k: v}
+    out = (old_lines if lines is None else lines) + [kept[k] for k in _SECTIONS if k in kept]
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as f:
         json.dump(out, f, indent=1)
@@ -288,7 +400,9 @@ def main():
     if "resample" in a.legs.split(","):
         resample_leg(a)
     if "filter" in a.legs.split(","):
-        _write(a.out, filt=filter_leg(a))
+        _write(a.out, filter=filter_leg(a))
+    if "decode" in a.legs.split(","):
+        _write(a.out, decode=decode_leg(a))
     if "recording" not in a.legs.split(","):
         return
     res = []
