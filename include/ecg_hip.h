@@ -595,6 +595,50 @@ int ecg_fir_windows(const float *x, const float *c, float *out, float *stats, in
  * nbytes < 0, slot outside [0,frame), skew < 0, col outside [0,leads_out) or repeated, (Ttot + skew)*frame > 2^60. */
 int ecg_wfdb_decode16(const uint8_t *raw, long long nbytes, int fmt, int frame, const int *slot, const int *skew,
                       const int *col, int ncols, int16_t *out, int Ttot, int leads_out, ecg_stream_t stream);
+/* Signal-quality indices of the same int16 stream, read in place: one launch writes, for every (recording, window, lead),
+ * ECG_QUALITY_FIELDS exact integers.  d [R][Ttot][leads] as above; q [R][W][leads][ECG_QUALITY_FIELDS] int64, caller-owned.
+ * Windows are stated on the MODEL's axis by the rule above (T, first, hop, W, last_start) and mapped onto the source
+ * stream by up/down: window w with model-axis start s_w covers the source samples [a_w, a_w + Tq),
+ *     a_w = min(floor(s_w*down/up), Ttot - Tq)   (64-bit),     Tq = min(Ttot, ceil(T*down/up))  (supplied by the host)
+ * up == down == 1 is the plain rule (Tq == T, a_w == s_w).  With v[i] the raw int16 at source sample a_w + i of the lead,
+ * 0 <= i < Tq, and a sample VALID iff v[i] != -32768, the fields are
+ *     ECG_Q_N_INVALID  count of invalid samples
+ *     ECG_Q_VMIN       min over valid samples (32767 if none)
+ *     ECG_Q_VMAX       max over valid samples (-32768 if none)
+ *     ECG_Q_SUM        sum of v over valid samples
+ *     ECG_Q_SUMSQ      sum of v*v over valid samples
+ *     ECG_Q_FLAT_RUN   longest run of consecutive samples with identical raw value (invalid samples compare equal to each
+ *                      other), clipped to the window; >= 1
+ *     ECG_Q_N_RAIL     count of valid samples with v <= rail_lo or v >= rail_hi
+ *     ECG_Q_N_PAIRS    count of i < Tq-1 with v[i], v[i+1] both valid
+ *     ECG_Q_SUM_STEP   sum of |v[i+1] - v[i]| over those pairs
+ *     ECG_Q_MAX_STEP   max of the same (0 if no pair)
+ * rail_lo, rail_hi: [R][leads] int32 on the device, both given or both NULL (NULL: -32767 and 32767).  Every field depends
+ * on the samples inside the window only: row (r, w) equals the row of a W = 1, Ttot = Tq call on a copy of its slice.
+ * Integer arithmetic only, no atomics: one right answer.  All sums fit int64 for any Tq < 2^31.  Windows are indexed from
+ * a 1-D grid with a grid-stride loop: no R*W <= 65535 limit, R and W are bounded by int alone.  No byte outside the
+ * windows is loaded.  ecg_wfdb16_quality_tile: source samples per LDS tile of the kernel (longer windows loop); tests.
+ * ECG_EINVAL before any launch: leads outside [1,16], up or down outside [1,512], Tq outside [1,Ttot] or not the value
+ * above, a window rule check_windows refuses on the model axis of ceil(Ttot*up/down) samples, one of rail_lo / rail_hi
+ * NULL and the other not, d or q NULL. */
+enum {
+    ECG_Q_N_INVALID = 0,
+    ECG_Q_VMIN = 1,
+    ECG_Q_VMAX = 2,
+    ECG_Q_SUM = 3,
+    ECG_Q_SUMSQ = 4,
+    ECG_Q_FLAT_RUN = 5,
+    ECG_Q_N_RAIL = 6,
+    ECG_Q_N_PAIRS = 7,
+    ECG_Q_SUM_STEP = 8,
+    ECG_Q_MAX_STEP = 9,
+    ECG_QUALITY_FIELDS = 10
+};
+#define ECG_QUALITY_TILE 1024
+int ecg_wfdb16_quality_tile(void);
+int ecg_wfdb16_quality(const int16_t *d, const int *rail_lo, const int *rail_hi, long long *q,
+                       int R, int Ttot, int leads, int T, int first, int hop, int W, int last_start,
+                       int up, int down, int Tq, ecg_stream_t stream);
 /* Per-window time series back onto the recording's axis: v [R][W][K][T] (K series per window, windows placed by the
  * rule above) -> out [R][K][Ttot], the mean over the windows that cover a sample:
  *     acc = 0.0f;  for w ascending with start(w) <= t < start(w)+T:  acc = acc + v[r][w][k][t - start(w)]

@@ -11,6 +11,7 @@ stock torch layers the modules inherit from, as the reference does on a GPU-less
 A recording at another sampling rate than the model's is resampled on the device (`ecg_hip.resample`, fs= / model_fs=).
 A raw recording is conditioned there too: a zero-phase baseline-wander high-pass and mains notch (`ecg_hip.filter`, filter=).
 WFDB records in formats 16, 61, 80, 160 and 212, with skews, offsets and several files, are decoded on the device (`ecg_hip.wfdbraw`).
+Windows spoiled by flat lines, rails or artefacts are kept out of the record-level numbers (`ecg_hip.quality`, quality=).
 """
 from ._lib import EcgHipError, LIB_PATH, load  # noqa: F401
 

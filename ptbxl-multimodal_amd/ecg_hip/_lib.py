@@ -104,6 +104,8 @@ SIGNATURES = {
     "ecg_wfdb16_windows_resampled": (_i, [_vp] * 6 + [_i] * 12 + [_vp]),
     "ecg_fir_windows": (_i, [_vp] * 4 + [_i] * 9 + [_vp]),
     "ecg_wfdb_decode16": (_i, [_vp, _ll, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
+    "ecg_wfdb16_quality_tile": (_i, []),
+    "ecg_wfdb16_quality": (_i, [_vp] * 4 + [_i] * 11 + [_vp]),
     "ecg_windows_overlap_mean": (_i, [_vp] * 3 + [_i] * 8 + [_vp]),
     "ecg_host_gather_rows": (_i, [_vp, _sz, _vp, _i, _vp]),
 }

@@ -1042,6 +1042,32 @@ def wfdb_decode16(files, layout, n_samp, columns=None):
     return out
 
 
+def wfdb16_quality(d, window, first, hop, W, last_start=-1, up=1, down=1, rails=None):
+    """Signal-quality indices of the windows of d int16 [R, Ttot, leads], read in place by ONE launch of
+    ecg_wfdb16_quality: -> int64 [R, W, leads, 10], the fields of ecg_hip.quality.FIELDS (exact integers).
+    window, first, hop, W, last_start state the windows on the MODEL's axis, as for wfdb16_windows /
+    wfdb16_windows_resampled; up/down maps that axis onto the source stream: window w with start s_w covers the source
+    samples [a_w, a_w + Tq), a_w = min(s_w*down // up, Ttot - Tq), Tq = quality.source_span(window, Ttot, up, down).
+    rails: (lo, hi) int32 [leads] or [R, leads] (quality.rails_from_header), None: -32767 and 32767."""
+    from .quality import source_span
+    if not (torch.is_tensor(d) and d.is_cuda):
+        raise L.EcgHipError("wfdb16_quality: a CPU tensor reached the HIP input step; d must be on the GPU")
+    if d.dtype != torch.int16:
+        raise L.EcgHipError(f"wfdb16_quality: d must be int16 (the raw stream), got {d.dtype}")
+    if d.dim() != 3:
+        raise L.EcgHipError("wfdb16_quality: d must be [R, Ttot, leads]")
+    d = _contig(d)
+    R, Ttot, leads = d.shape
+    lo = hi = None
+    if rails is not None:
+        lo, hi = (_contig(torch.as_tensor(t, dtype=torch.int32).to(d.device).reshape(-1, leads).expand(R, leads))
+                  for t in rails)
+    q = torch.empty(R, max(int(W), 0), leads, 10, dtype=torch.int64, device=d.device)
+    _call("ecg_wfdb16_quality", L.ptr(d), L.ptr(lo), L.ptr(hi), L.ptr(q), R, Ttot, leads, int(window), int(first), int(hop),
+          int(W), int(last_start), int(up), int(down), source_span(window, Ttot, up, down), _st())
+    return q
+
+
 def overlap_mean(v, plan, Ttot, return_cover=False):
     """Per-window time series v fp32 [R, W, K, T] (windows placed by `plan`, a window_plan result) -> [R, K, Ttot]: at
     every sample the mean of the windows that cover it, added in ascending window order by the one lane that owns the

@@ -17,6 +17,10 @@ chunks and the stitched CAMs then live on the model-rate axis of resampled_lengt
 A raw ambulatory recording carries baseline wander and mains hum that the per-window z-score cannot remove (drift of a
 few mV dominates the std).  `filter=` conditions it on the device: the physical (or resampled) recording is written once
 as fp32 and `ecg_fir_windows` (ecg_hip/filter.py) cuts the windows out of its zero-phase filtered form.
+
+A finite window is not a trustworthy one: a flat line, an amplifier on its rail or a motion artefact z-scores into a
+confident number.  `quality=` (ecg_hip/quality.py) takes ten exact integer indices per (recording, window, lead) from the
+raw int16 stream in one launch of `ecg_wfdb16_quality` and keeps the windows it judges unusable out of prob_max / prob_mean.
 """
 import torch
 
@@ -63,8 +67,11 @@ class RecordingScore:
     """starts (W start samples); logits, prob [R, W, C]; finite [R, W]; prob_max, prob_mean [R, C] over the finite windows
     (NaN where a recording has none); with CAMs: cam [R, K, Ttot], cover [Ttot] (windows over each sample).
     fs: the sampling rate of the axis starts / cam / cover are on (the model's rate where the recording was resampled,
-    Ttot then being the resampled length; None when no rate was given); source_len: samples of the recording itself."""
-    __slots__ = ("starts", "logits", "prob", "finite", "prob_max", "prob_mean", "cam", "cover", "fs", "source_len")
+    Ttot then being the resampled length; None when no rate was given); source_len: samples of the recording itself.
+    With quality=: quality int64 [R, W, leads, 10] (quality.FIELDS, on the source axis), lead_ok [R, W, leads] and
+    usable [R, W]; prob_max / prob_mean are then over the windows that are finite AND usable.  None otherwise."""
+    __slots__ = ("starts", "logits", "prob", "finite", "prob_max", "prob_mean", "cam", "cover", "fs", "source_len",
+                 "quality", "lead_ok", "usable")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -84,7 +91,7 @@ def _record_level(prob, finite):
 
 
 def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift", batch_size=256, x_demo=None,
-                    cam_classes=None, cam_normalize=None, fs=None, model_fs=None, filter=None):
+                    cam_classes=None, cam_normalize=None, fs=None, model_fs=None, filter=None, quality=None, rails=None):
     """Score recordings d int16 [Ttot, leads] or [R, Ttot, leads] (on the GPU, the .dat layout) with `model` in eval mode.
 
     gain float64 / baseline int32 [leads] or [R, leads]; window: samples per model input; hop: default window // 2;
@@ -115,6 +122,16 @@ def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift",
     signal).  An invalid sample poisons every filtered sample within `half` taps of it on its lead — 363 samples at
     100 Hz, 1813 at 500 Hz for the default high-pass — so a long filter widens the set of windows flagged not finite.
     None (default): no filter, no further launch, today's bits.
+
+    quality: an ecg_hip.quality.QualitySpec, or True for QualitySpec() (its defaults are policy, not measurements).  ONE
+    launch of functional.wfdb16_quality for the whole call takes the indices of every window of the plan from the RAW
+    int16 stream — before resampling and before filter=, which would hide the defects it looks for; on a resampled
+    recording the model-axis windows are mapped onto the source samples they cover by up/down.  rails: (lo, hi) int32
+    [leads] or [R, leads], the ADC rails of the stream (quality.rails_from_header; None: -32767 and 32767).  The spec is
+    judged at the SOURCE rate fs (ValueError when flat_s is set and fs is None).  The score gains quality, lead_ok and
+    usable, and prob_max / prob_mean are taken over finite & usable (NaN where a recording has no such window).  logits,
+    prob, finite and the CAMs are untouched: unusable windows are still scored and still stitched.
+    None (default): no launch is added and every output keeps today's bits.
     -> RecordingScore."""
     if not (torch.is_tensor(d) and d.is_cuda):
         raise L.EcgHipError("score_recording: a CPU tensor reached the HIP input step; d must be on the GPU "
@@ -154,6 +171,15 @@ def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift",
     phys, phys_of = None, None      # the fp32 recordings [r1-r0, leads, Ttot] of the group in flight (filter only)
     cams = None if cam_classes is None else [int(k) for k in cam_classes]
     d = hipF._contig(d)
+    qtab = lead_ok = usable = None
+    if quality is not None and quality is not False:
+        from .quality import QualitySpec, source_span
+        spec = QualitySpec() if quality is True else quality
+        if not isinstance(spec, QualitySpec):
+            raise ValueError(f"quality={quality!r}: a QualitySpec, True or None")
+        up, down = ratio or (1, 1)
+        qtab = hipF.wfdb16_quality(d, window, plan[0], hop, W, plan[3], up, down, rails)
+        lead_ok, usable = spec.judge(qtab, gain, fs, source_span(window, source_len, up, down))
 
     logits = v = None
     ok = torch.empty(R, W, dtype=torch.bool, device=dev)
@@ -189,7 +215,7 @@ def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift",
         ok[r0:r1, w0:w0 + Wc] = torch.isfinite(stats).view(r1 - r0, Wc, -1).all(-1)
     finite = ok & torch.isfinite(logits).all(-1)
     prob = hipF.sigmoid(logits)
-    pmax, pmean = _record_level(prob, finite)
+    pmax, pmean = _record_level(prob, finite if usable is None else finite & usable)
     cam = cover = None
     if cams is not None:
         cam, cover = hipF.overlap_mean(v, plan, Ttot, return_cover=True)
@@ -201,7 +227,8 @@ def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift",
             c = torch.where(mx > 0, c / torch.where(mx > 0, mx, torch.ones_like(mx)), c)
             cam = torch.where(covered, c, torch.zeros_like(c))
     return RecordingScore(starts=starts, logits=logits, prob=prob, finite=finite, prob_max=pmax, prob_mean=pmean,
-                          cam=cam, cover=cover, fs=fs if ratio is None else model_fs, source_len=source_len)
+                          cam=cam, cover=cover, fs=fs if ratio is None else model_fs, source_len=source_len,
+                          quality=qtab, lead_ok=lead_ok, usable=usable)
 
 
 def score_wfdb_record(record_path, model, model_fs=None, leads=None, **kw):
@@ -209,6 +236,8 @@ def score_wfdb_record(record_path, model, model_fs=None, leads=None, **kw):
     model_fs: the rate the model was trained at; the record is resampled on the device when its header's rate differs.
     None (default): the record is scored at its own rate, whatever the header says.  filter= (score_recording) is passed
     through: a FilterSpec is designed at model_fs when the record is resampled, otherwise at the header's rate.
+    quality= is passed through too, with the ADC rails of the selected leads (quality.rails_from_header: adc_res and
+    adc_zero of the header, or the storage format's range) unless the caller gives rails= itself.
 
     leads: the signals to score, in the model's lead order — names matched against the header's descriptions (e.g.
     wfdbraw.PTBXL_LEADS for a 15-signal PTB Diagnostic record) or signal indices; None: every signal, in header order.
@@ -222,13 +251,19 @@ def score_wfdb_record(record_path, model, model_fs=None, leads=None, **kw):
         sigs = parse_header(f.read())["signals"]
     plain = leads is None and len({s["file"] for s in sigs}) == 1 and all(
         s["fmt"] == 16 and s["spf"] == 1 and s["skew"] == 0 and s["offset"] == 0 for s in sigs)
+    cols = range(len(sigs))
     if plain:
         rec = read_record(record_path)
         d, gain, baseline, fs = torch.from_numpy(rec.d.astype("int16")).to(dev), rec.gain, rec.baseline, rec.fs
     else:
-        from .wfdbraw import read_raw_record, to_device
+        from .wfdbraw import read_raw_record, select_leads, to_device
         rec = read_raw_record(record_path)
         d, gain, baseline = to_device(rec, dev, leads)
         fs = rec.fs
+        if leads is not None:
+            cols = select_leads(rec, leads)
+    if kw.get("quality") is not None and "rails" not in kw:
+        from .quality import rails_from_header
+        kw["rails"] = rails_from_header([sigs[c] for c in cols])
     return score_recording(model, d, torch.from_numpy(gain).to(dev), torch.from_numpy(baseline).to(dev), fs=fs,
                            model_fs=model_fs, **kw)

@@ -61,8 +61,8 @@ def checksum16(d):
 
 
 def parse_header(text):
-    """-> dict(name, n_sig, fs, n_samp, signals=[dict(file, fmt, gain, baseline, units, adc_zero,
-    init_value, checksum, description)])"""
+    """-> dict(name, n_sig, fs, n_samp, signals=[dict(file, fmt, gain, baseline, units, adc_res, adc_zero,
+    init_value, checksum, description)]); adc_res is 0 when the header does not give it."""
     lines = [ln.strip() for ln in text.splitlines()]
     lines = [ln for ln in lines if ln and not ln.startswith("#")]
     if not lines:
@@ -93,7 +93,7 @@ def parse_header(text):
             file=g["file"], fmt=int(g["fmt"]), spf=int(g["spf"] or 1), skew=int(g["skew"] or 0),
             offset=int(g["off"] or 0), gain=gain,
             baseline=int(g["base"]) if g["base"] is not None else zero,
-            units=g["units"] or "mV", adc_zero=zero,
+            units=g["units"] or "mV", adc_res=int(g["res"]) if g["res"] is not None else 0, adc_zero=zero,
             init_value=int(g["init"]) if g["init"] is not None else None,
             checksum=int(g["csum"]) if g["csum"] is not None else None,
             description=(g["desc"] or "").strip()))

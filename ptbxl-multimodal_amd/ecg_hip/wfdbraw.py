@@ -219,12 +219,13 @@ def encode_samples(v, fmt):
 
 
 def write_raw_record(record_path, d, fs, gain, baseline, fmt=212, skew=None, offset=0, files=None, units=None,
-                     sig_names=None):
+                     sig_names=None, adc_res=16):
     """Write d integer [n_samp, n_sig] (the values as they DECODE; -32768 marks an invalid sample and is stored as the
     format's invalid code) as <record_path>.hea and its .dat files.
 
     fmt, offset: one value, or one per FILE.  files: for every signal the index of its file (default: all in file 0);
-    file k is <name>.dat for one file, else <name>_k.dat.  skew: frames per signal (default 0).  Every file holds
+    file k is <name>.dat for one file, else <name>_k.dat.  skew: frames per signal (default 0).
+    adc_res: the ADC resolution in bits the signal lines announce (one value).  Every file holds
     n_samp frames: signal sample t is stored in frame t + skew, the first `skew` frames of that slot hold the invalid
     code and the last `skew` samples are NOT stored — they read back as invalid, and the header checksum counts them as
     the invalid code, like the samples that are stored as such.  `offset` bytes of 0xA5 precede the samples."""
@@ -252,7 +253,7 @@ def write_raw_record(record_path, d, fs, gain, baseline, fmt=212, skew=None, off
             stored[skew[i]:skew[i] + keep, slot] = v[:keep]
             as_read = np.concatenate([v[:keep], np.full(n_samp - keep, code, np.int64)])
             spec = f"{fmts[k]}" + (f":{skew[i]}" if skew[i] else "") + (f"+{offsets[k]}" if offsets[k] else "")
-            lines[i] = (f"{fnames[k]} {spec} {float(gain[i])!r}({int(baseline[i])})/{units[i]} 16 0 "
+            lines[i] = (f"{fnames[k]} {spec} {float(gain[i])!r}({int(baseline[i])})/{units[i]} {int(adc_res)} 0 "
                         f"{int(as_read[0])} {fold16(as_read.sum())} 0 {sig_names[i]}\n")
         body = encode_samples(stored.reshape(-1), fmts[k])
         np.concatenate([np.full(offsets[k], 0xA5, np.uint8), body]).tofile(os.path.join(folder, fnames[k]))

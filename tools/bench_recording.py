@@ -2,7 +2,8 @@
 score_recording end to end.
 
     python tools/bench_recording.py [--hours 1] [--rounds 7] [--iters 20] [--out profiles/recording_bench.json]
-                                    [--legs recording,resample,filter,decode] [--resample-out profiles/resample_bench.json]
+                                    [--legs recording,resample,filter,decode,quality]
+                                    [--resample-out profiles/resample_bench.json]
 
 Workloads: one 12-lead recording of --hours at 500 Hz (window 5000) and at 100 Hz (window 1000), hop = window / 2.
   (a) sliding   ecg_wfdb16_windows on the recording in place
@@ -41,6 +42,15 @@ alternating in one process like the others.  The kernel is also rated against th
 per sample for 212; 2 B + 2 B per selected sample for the selection), and its share of score_wfdb_record end to end (header,
 file read, upload, decode, checksum, scoring; host clock around a synchronise) is reported.  Written into --out under
 "decode".
+
+Leg "quality" (not in the default --legs): the signal-quality stage, ecg_wfdb16_quality, on the one-hour 12-lead recording at
+100 Hz (window 1000, hop 500) and at 500 Hz (window 5000, hop 2500).
+  (k) kernel   functional.wfdb16_quality on the recording in place: one launch, rated against the R*W*Tq*leads*2 bytes it
+               must read
+  (l) torch    the same table in torch tensor ops on the device: unfold plus masked reductions, run lengths through a
+               cummax of the positions where the value changes (checked equal to the kernel's table)
+  (m) score    score_recording with quality=True against the same call without it (fp32, no CAMs): what the gate adds
+alternating in one process like the others.  Written into --out under "quality".
 Fails when no GPU is visible: no number here means anything on a CPU.
 """
 import argparse
@@ -359,12 +369,90 @@ def decode_leg(a):
     return res
 
 
-_SECTIONS = ("filter", "decode")
+def quality_table_torch(d, window, hop, lo=-32767, hi=32767):
+    """The table of ecg_wfdb16_quality for one recording d int16 [Ttot, leads] in torch tensor ops (regular windows only)."""
+    v16 = d.unfold(0, window, hop)                                      # [W][leads][T], a view
+    v = v16.to(torch.int32)
+    valid = v16 != -32768
+    zero = torch.zeros((), dtype=torch.int32, device=d.device)
+    vv = torch.where(valid, v, zero)
+    t = torch.arange(window, device=d.device, dtype=torch.int32)
+    change = torch.ones_like(valid)
+    change[..., 1:] = v16[..., 1:] != v16[..., :-1]
+    run_start = torch.where(change, t, zero).cummax(-1).values          # where the run a sample belongs to began
+    pair = valid[..., 1:] & valid[..., :-1]
+    step = torch.where(pair, (v[..., 1:] - v[..., :-1]).abs(), zero)
+    i64 = torch.int64
+    return torch.stack([(~valid).sum(-1), torch.where(valid, v, zero + 32767).amin(-1).to(i64),
+                        torch.where(valid, v, zero - 32768).amax(-1).to(i64), vv.sum(-1, dtype=i64),
+                        (vv.to(i64) * vv).sum(-1), (t - run_start + 1).amax(-1).to(i64),
+                        (valid & ((v <= lo) | (v >= hi))).sum(-1), pair.sum(-1), step.sum(-1, dtype=i64),
+                        step.amax(-1).to(i64) if window > 1 else torch.zeros_like(pair.sum(-1))], -1)[None]
+
+
+def quality_leg(a):
+    """ecg_wfdb16_quality against the same table in torch ops, and what quality= adds to score_recording."""
+    from ecg_hip import functional as F
+    from ecg_hip.recording import score_recording, window_plan
+    from src.models.ecg_cnn import ECGCNN
+    from src.utils.seed import set_seed
+    res = []
+    for fs, window in ((100, 1000), (500, 5000)):
+        Ttot, hop = int(a.hours * 3600 * fs), window // 2
+        rng = np.random.default_rng(fs + 2)
+        h = rng.integers(-3000, 3000, size=(1, Ttot, LEADS)).astype(np.int16)
+        for _ in range(200):                            # flat stretches, rails and invalid samples, so that no field is trivial
+            t, c, n = int(rng.integers(0, Ttot - 400)), int(rng.integers(LEADS)), int(rng.integers(2, 400))
+            h[0, t:t + n, c] = rng.choice([0, 32767, -32767, -32768, int(rng.integers(-3000, 3000))])
+        d = torch.from_numpy(h).cuda()
+        gain = torch.full((1, LEADS), 1000.0, dtype=torch.float64).cuda()
+        base = torch.zeros(1, LEADS, dtype=torch.int32).cuda()
+        first, hop, W, last, _ = window_plan(Ttot, window, hop)
+        assert last == -1                               # the torch form below cuts regular windows only
+        set_seed(42)
+        model = ECGCNN(num_labels=5).cuda().eval()
+
+        def kernel():
+            return F.wfdb16_quality(d, window, first, hop, W, last)
+
+        def stock():
+            return quality_table_torch(d[0], window, hop)
+
+        def score(q):
+            return score_recording(model, d, gain, base, window=window, hop=hop, batch_size=a.batch, fs=fs, quality=q).prob_max
+
+        assert torch.equal(kernel(), stock())
+        print(f"quality leg: {fs} Hz, {W} windows of {LEADS}x{window}", file=sys.stderr, flush=True)
+        big = argparse.Namespace(**{**vars(a), "iters": max(a.iters, 2000)})       # a launch is microseconds
+        ms, iters = _rounds({"kernel": kernel, "torch": stock}, big)
+        ms2, iters2 = _rounds({"gated": lambda: score(True), "ungated": lambda: score(None)}, a)
+        ms.update(ms2), iters.update(iters2)
+        med = {k: float(np.median(v)) for k, v in ms.items()}
+        must = W * window * LEADS * 2
+        line = {"metric": "wfdb16_quality_ms", "value": round(med["kernel"], 4), "unit": "ms",
+                "config": {"workload": f"{a.hours:g} h, {LEADS} leads at {fs} Hz (Ttot {Ttot}), window {window}, hop {hop}, "
+                                       f"{W} windows: int16 in place -> int64 [1][{W}][{LEADS}][10]; score_recording: "
+                                       f"ECGCNN(5), chunks of {a.batch}, fp32, no CAMs"},
+                **{f"{k}_ms": [round(t, 4) for t in v] for k, v in ms.items()},
+                **{f"{k}_median_ms": round(m, 4) for k, m in med.items()},
+                **{f"{k}_spread_ms": round(max(v) - min(v), 4) for k, v in ms.items()},
+                "calls_per_round": iters, "torch_over_kernel": round(med["torch"] / med["kernel"], 3),
+                "kernel_bytes_it_must_read": int(must), "kernel_GBps_of_those_bytes": round(must / (med["kernel"] * 1e-3) / 1e9, 1),
+                "kernel_frac_of_hbm": round(must / (med["kernel"] * 1e-3) / HBM_BYTES_PER_S, 4),
+                "gated_over_ungated": round(med["gated"] / med["ungated"], 4),
+                "added_ms": round(med["gated"] - med["ungated"], 4),
+                "kernel_share_of_gated_score_recording": round(med["kernel"] / med["gated"], 5)}
+        print(json.dumps(line), flush=True)
+        res.append(line)
+    return res
+
+
+_SECTIONS = ("filter", "decode", "quality")
 
 
 def _write(path, lines=None, **sections):
-    """profiles/recording_bench.json: the recording leg's lines, then {"filter": [...]} and {"decode": [...]}; a leg
-    replaces its own part."""
+    """profiles/recording_bench.json: the recording leg's lines, then {"filter": [...]}, {"decode": [...]} and
+    {"quality": [...]}; a leg replaces its own part."""
     old = []
     if os.path.exists(path):
         with open(path) as f:
@@ -403,6 +491,8 @@ def main():
         _write(a.out, filter=filter_leg(a))
     if "decode" in a.legs.split(","):
         _write(a.out, decode=decode_leg(a))
+    if "quality" in a.legs.split(","):
+        _write(a.out, quality=quality_leg(a))
     if "recording" not in a.legs.split(","):
         return
     res = []
