@@ -110,13 +110,12 @@ ECG_API int ecg_fir_windows(const float *x, const float *c, float *out, float *s
     const char *who = "fir_windows";
     ECG_REQUIRE(x && c && out, "%s: null pointer", who);
     ECG_REQUIRE(half >= 0 && half <= kFirMaxHalf, "%s: half=%d outside [0,%d]", who, half, kFirMaxHalf);
-    ECG_REQUIRE(leads >= 1 && leads <= kMaxLeads, "%s: leads=%d outside [1,%d]", who, leads, kMaxLeads);
     ECG_REQUIRE(R > 0 && Ttot > 0, "%s: R=%d Ttot=%d must be > 0", who, R, Ttot);
     int rc = check_windows(who, R, Ttot, T, first, hop, W, last_start);
     if (rc) return rc;
     const long long NW = (long long)R * W;
-    ECG_REQUIRE(NW <= 65535, "%s: %lld windows exceed grid.y limit 65535", who, NW);
-    ECG_REQUIRE(!stats || NW * leads <= 65535, "%s: windows*leads=%lld exceeds 65535 rows for T=%d", who, NW * leads, T);
+    rc = check_grid(who, leads, NW, stats != nullptr, T);
+    if (rc) return rc;
     const int hpad = (half + 3) & ~3;
     const size_t lds = (size_t)(kFirNT + 2 * hpad) * sizeof(float);
     hipLaunchKernelGGL(fir_windows_kernel, dim3(cdiv(T, kFirNT), (int)NW, leads), dim3(kFirThreads), lds, as_stream(stream),

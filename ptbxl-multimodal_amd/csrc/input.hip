@@ -24,7 +24,7 @@
 // conversion and the z-score, reading the same int16 stream in place (its arithmetic is stated above the kernel);
 // ecg_zscore_rows then normalises the windows it wrote.
 #include "common.h"
-#include "windows.h"        // WindowSrc, window_start, check_windows, kMaxLeads
+#include "windows.h"        // WindowSrc, window_start, check_windows, check_grid, kMaxLeads
 
 // hipcc contracts a*b+c into an fma by default (-ffp-contract=fast) — and does so even through the
 // __fmul_rn/__fadd_rn wrappers, whose bodies are compiled under the header's own state: one rounding
@@ -45,6 +45,12 @@ __device__ __forceinline__ int window_source(const WindowSrc &s, int b, int lead
     return r;
 }
 
+// The DAC conversion of sample v of lead l (wfdb 4.3.0 Record.dac, then the float32 cast); base / g: the baselines and
+// gains of the leads, read for a valid sample only.  Format 16 reserves -32768 as "invalid sample": wfdb returns NaN.
+__device__ __forceinline__ float dac(int v, const int *base, const double *g, int l) {
+    return (v == -32768) ? __builtin_nanf("") : (float)((double)(v - base[l]) / g[l]);
+}
+
 __global__ __launch_bounds__(256) void wfdb16_physical_kernel(
     const int16_t *__restrict__ d, const double *__restrict__ gain, const int *__restrict__ baseline,
     float *__restrict__ out, int T, int leads, WindowSrc ws) {
@@ -62,9 +68,7 @@ __global__ __launch_bounds__(256) void wfdb16_physical_kernel(
             const int v = tile[tid * leads + l];
             const double g = gain[(size_t)r * leads + l];
             const int base = baseline[(size_t)r * leads + l];
-            // format 16 reserves -32768 as "invalid sample": wfdb returns NaN for it
-            const float p = (v == -32768) ? __builtin_nanf("") : (float)((double)(v - base) / g);
-            out[((size_t)b * leads + l) * T + t0 + tid] = p;
+            out[((size_t)b * leads + l) * T + t0 + tid] = dac(v, &base, &g, 0);
         }
     }
 }
@@ -170,7 +174,7 @@ __global__ __launch_bounds__(256) void wfdb16_zscore_fused_kernel(
         const int16_t *p = src + (size_t)t * leads;
         for (int l = 0; l < nl; ++l) {
             const int v = p[l];
-            phys[(size_t)l * Tpad + t] = (v == -32768) ? __builtin_nanf("") : (float)((double)(v - sb[l]) / sg[l]);
+            phys[(size_t)l * Tpad + t] = dac(v, sb, sg, l);
         }
     }
     __syncthreads();
@@ -259,7 +263,7 @@ __global__ __launch_bounds__(256) void wfdb16_resample_kernel(
         const int16_t *p = rec + (size_t)k * leads;
         for (int l = 0; l < leads; ++l) {
             const int v = p[l];
-            span_lds[(size_t)l * S + s] = (v == -32768) ? __builtin_nanf("") : (float)((double)(v - sb[l]) / sg[l]);
+            span_lds[(size_t)l * S + s] = dac(v, sb, sg, l);
         }
     }
     __syncthreads();
@@ -392,9 +396,7 @@ ECG_API int ecg_zscore_rows(const float *x, float *out, float *stats, int rows, 
 // at the physical signal.  NW = R*W windows.
 static int wfdb16_windows_launch(const char *who, const int16_t *d, const double *gain, const int *baseline, float *out,
                                  float *stats, int R, int T, int leads, const WindowSrc &ws, ecg_stream_t stream) {
-    ECG_REQUIRE(leads >= 1 && leads <= kMaxLeads, "%s: leads=%d outside [1,%d]", who, leads, kMaxLeads);
     const long long NW = (long long)R * ws.W;
-    ECG_REQUIRE(NW <= 65535, "%s: %lld windows exceed grid.y limit 65535", who, NW);
     int Tpad = (T + 3) / 4 * 4;
     Tpad += (4 - Tpad % 64 + 64) % 64;                 // row stride == 4 (mod 64 banks)
     const size_t row_bytes = (size_t)Tpad * 4;
@@ -404,11 +406,12 @@ static int wfdb16_windows_launch(const char *who, const int16_t *d, const double
     // need to overlap (12x5000: 220 us fused with 3 leads per workgroup vs 138 us streamed), so they
     // take the three streaming launches instead.
     const int G = (stats && row_bytes * leads + (size_t)leads * 8 <= 64u * 1024u) ? leads : 0;
+    int rc = check_grid(who, leads, NW, stats && G == 0, T);       // (the fused kernel takes its own statistics)
+    if (rc) return rc;
     if (G == 0) {
-        ECG_REQUIRE(!stats || NW * leads <= 65535, "%s: windows*leads=%lld exceeds 65535 rows for T=%d", who, NW * leads, T);
         hipLaunchKernelGGL(wfdb16_physical_kernel, dim3(cdiv(T, kTT), (int)NW), dim3(256), 0, as_stream(stream), d,
                            gain, baseline, out, T, leads, ws);
-        int rc = check_launch("wfdb16_physical_kernel");
+        rc = check_launch("wfdb16_physical_kernel");
         if (rc || !stats) return rc;
         return ecg_zscore_rows(out, out, stats, (int)NW * leads, T, stream);
     }
@@ -455,15 +458,14 @@ ECG_API int ecg_wfdb16_windows_resampled(const int16_t *d, const double *gain, c
     ECG_REQUIRE(half >= 0, "%s: half=%d must be >= 0", who, half);
     ECG_REQUIRE((long long)ntap * up >= 2ll * half + 1, "%s: ntap*up=%d does not cover the filter length 2*half+1=%lld", who,
                 ntap * up, 2ll * half + 1);
-    ECG_REQUIRE(leads >= 1 && leads <= kMaxLeads, "%s: leads=%d outside [1,%d]", who, leads, kMaxLeads);
     ECG_REQUIRE(R > 0 && Ttot > 0, "%s: R=%d Ttot=%d must be > 0", who, R, Ttot);
     const long long Tout = ((long long)Ttot * up + down - 1) / down;      // the resampled recording's length
     ECG_REQUIRE(Tout <= 0x7fffffffll, "%s: resampled length %lld exceeds int", who, Tout);
     int rc = check_windows(who, R, (int)Tout, T, first, hop, W, last_start);
     if (rc) return rc;
     const long long NW = (long long)R * W;
-    ECG_REQUIRE(NW <= 65535, "%s: %lld windows exceed grid.y limit 65535", who, NW);
-    ECG_REQUIRE(!stats || NW * leads <= 65535, "%s: windows*leads=%lld exceeds 65535 rows for T=%d", who, NW * leads, T);
+    rc = check_grid(who, leads, NW, stats != nullptr, T);
+    if (rc) return rc;
     // The tile: the largest NT <= 256 whose source span (+ the table, when it is small enough to sit in LDS) fits in
     // 64 KB together with the kernel's static 192 bytes.  NT = 1 always fits (S = ntap <= 256).
     const bool taps_lds = up * ntap <= 2048;

@@ -1,4 +1,4 @@
-// windows.h — the window rule of the input step, shared by input.hip and fir.hip.
+// windows.h — the window rule and the grid limits of the input step, shared by input.hip and fir.hip.
 #pragma once
 #include "common.h"
 
@@ -31,6 +31,15 @@ static int check_windows(const char *who, int R, int Ttot, int T, int first, int
     ECG_REQUIRE(wreg == 0 || first + (long long)(wreg - 1) * hop <= Ttot - T,
                 "%s: window %d starts at %lld, past Ttot-T=%d", who, wreg - 1, first + (long long)(wreg - 1) * hop,
                 Ttot - T);
+    return ECG_OK;
+}
+
+// The grid limits of a window launch: leads in range, one grid.y row per window (NW = R*W) and, when ecg_zscore_rows
+// takes the statistics of the result (`rows`), one per (window, lead).
+static int check_grid(const char *who, int leads, long long NW, bool rows, int T) {
+    ECG_REQUIRE(leads >= 1 && leads <= kMaxLeads, "%s: leads=%d outside [1,%d]", who, leads, kMaxLeads);
+    ECG_REQUIRE(NW <= 65535, "%s: %lld windows exceed grid.y limit 65535", who, NW);
+    ECG_REQUIRE(!rows || NW * leads <= 65535, "%s: windows*leads=%lld exceeds 65535 rows for T=%d", who, NW * leads, T);
     return ECG_OK;
 }
 

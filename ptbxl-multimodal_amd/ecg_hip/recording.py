@@ -90,6 +90,58 @@ def _record_level(prob, finite):
     return pmax, pmean
 
 
+def _chunk_windows(d, gain, baseline, window, hop, Ttot, ratio, taps):
+    """-> windows_of(chunk) = (x [r1-r0, Wc, leads, window], stats) for an entry of plan_chunks, walked in its order.
+    Without taps: ONE launch per chunk, wfdb16_windows — or wfdb16_windows_resampled by ratio = (up, down) — on the
+    chunk's recordings.  With taps: fir_windows per chunk out of `phys`, the fp32 physical (or resampled) recordings
+    [r1-r0, leads, Ttot] of the group in flight, which ONE whole-recording launch (W = 1, not normalised) writes when the
+    (r0, r1) group changes — once per group, not once per chunk.  Nothing else knows about phys."""
+    def cut(r0, r1, T, first, hop, W, last, normalize):       # -> (x, stats); x alone when not normalised
+        if ratio is None:
+            return hipF.wfdb16_windows(d[r0:r1], gain[r0:r1], baseline[r0:r1], T, first, hop, W, last, normalize, True)
+        return hipF.wfdb16_windows_resampled(d[r0:r1], gain[r0:r1], baseline[r0:r1], T, first, hop, W, last, *ratio,
+                                             normalize, True)
+
+    phys = phys_of = None
+
+    def windows_of(chunk):
+        nonlocal phys, phys_of
+        r0, r1, _, first, Wc, last = chunk
+        if taps is None:
+            return cut(r0, r1, window, first, hop, Wc, last, True)
+        if phys_of != (r0, r1):
+            phys, phys_of = cut(r0, r1, Ttot, 0, 1, 1, -1, False)[:, 0], (r0, r1)
+        return hipF.fir_windows(phys, taps, window, first, hop, Wc, last, return_stats=True)
+
+    return windows_of
+
+
+def _quality_gate(quality, d, gain, rails, window, plan, ratio, fs, source_len):
+    """-> (quality table, lead_ok, usable) of every window of the plan from ONE wfdb16_quality launch on the raw stream,
+    judged at the source rate fs; (None, None, None) and no launch without quality=."""
+    if quality is None or quality is False:
+        return None, None, None
+    from .quality import QualitySpec, source_span
+    spec = QualitySpec() if quality is True else quality
+    if not isinstance(spec, QualitySpec):
+        raise ValueError(f"quality={quality!r}: a QualitySpec, True or None")
+    up, down = ratio or (1, 1)
+    first, hop, W, last_start, _ = plan
+    qtab = hipF.wfdb16_quality(d, window, first, hop, W, last_start, up, down, rails)
+    return (qtab, *spec.judge(qtab, gain, fs, source_span(window, source_len, up, down)))
+
+
+def _normalize_per_record(cam, cover):
+    """cam_normalize="record": min-max of every (recording, class) row of cam [R, K, Ttot] over its covered samples
+    (cover > 0), divided only where the maximum is > 0; 0 where nothing covers."""
+    covered = (cover > 0)[None, None, :]
+    big = torch.finfo(cam.dtype).max
+    c = cam - torch.where(covered, cam, cam.new_full((), big)).amin(-1, keepdim=True)
+    mx = torch.where(covered, c, cam.new_full((), -big)).amax(-1, keepdim=True)
+    c = torch.where(mx > 0, c / torch.where(mx > 0, mx, torch.ones_like(mx)), c)
+    return torch.where(covered, c, torch.zeros_like(c))
+
+
 def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift", batch_size=256, x_demo=None,
                     cam_classes=None, cam_normalize=None, fs=None, model_fs=None, filter=None, quality=None, rails=None):
     """Score recordings d int16 [Ttot, leads] or [R, Ttot, leads] (on the GPU, the .dat layout) with `model` in eval mode.
@@ -168,35 +220,16 @@ def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift",
         from .filter import FilterSpec, one_sided
         axis_fs = fs if ratio is None else model_fs
         taps = one_sided(filter.taps(axis_fs) if isinstance(filter, FilterSpec) else filter)
-    phys, phys_of = None, None      # the fp32 recordings [r1-r0, leads, Ttot] of the group in flight (filter only)
     cams = None if cam_classes is None else [int(k) for k in cam_classes]
     d = hipF._contig(d)
-    qtab = lead_ok = usable = None
-    if quality is not None and quality is not False:
-        from .quality import QualitySpec, source_span
-        spec = QualitySpec() if quality is True else quality
-        if not isinstance(spec, QualitySpec):
-            raise ValueError(f"quality={quality!r}: a QualitySpec, True or None")
-        up, down = ratio or (1, 1)
-        qtab = hipF.wfdb16_quality(d, window, plan[0], hop, W, plan[3], up, down, rails)
-        lead_ok, usable = spec.judge(qtab, gain, fs, source_span(window, source_len, up, down))
+    qtab, lead_ok, usable = _quality_gate(quality, d, gain, rails, window, plan, ratio, fs, source_len)
+    windows_of = _chunk_windows(d, gain, baseline, window, hop, Ttot, ratio, taps)
 
     logits = v = None
     ok = torch.empty(R, W, dtype=torch.bool, device=dev)
-    for r0, r1, w0, first, Wc, last in plan_chunks(R, plan, int(batch_size)):
-        if taps is not None:
-            if phys_of != (r0, r1):
-                whole = (d[r0:r1], gain[r0:r1], baseline[r0:r1], Ttot, 0, 1, 1, -1)
-                phys = (hipF.wfdb16_windows(*whole, normalize=False) if ratio is None else
-                        hipF.wfdb16_windows_resampled(*whole, *ratio, normalize=False))[:, 0]
-                phys_of = (r0, r1)
-            x, stats = hipF.fir_windows(phys, taps, window, first, hop, Wc, last, return_stats=True)
-        elif ratio is None:
-            x, stats = hipF.wfdb16_windows(d[r0:r1], gain[r0:r1], baseline[r0:r1], window, first, hop, Wc, last,
-                                           return_stats=True)
-        else:
-            x, stats = hipF.wfdb16_windows_resampled(d[r0:r1], gain[r0:r1], baseline[r0:r1], window, first, hop, Wc, last,
-                                                     *ratio, return_stats=True)
+    for chunk in plan_chunks(R, plan, int(batch_size)):
+        r0, r1, w0, _, Wc, _ = chunk
+        x, stats = windows_of(chunk)
         n = (r1 - r0) * Wc
         x = x.view(n, leads, window)
         xd = None if x_demo is None else x_demo[r0:r1].repeat_interleave(Wc, dim=0)
@@ -220,12 +253,7 @@ def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift",
     if cams is not None:
         cam, cover = hipF.overlap_mean(v, plan, Ttot, return_cover=True)
         if cam_normalize == "record":
-            covered = (cover > 0)[None, None, :]
-            big = torch.finfo(cam.dtype).max
-            c = cam - torch.where(covered, cam, cam.new_full((), big)).amin(-1, keepdim=True)
-            mx = torch.where(covered, c, cam.new_full((), -big)).amax(-1, keepdim=True)
-            c = torch.where(mx > 0, c / torch.where(mx > 0, mx, torch.ones_like(mx)), c)
-            cam = torch.where(covered, c, torch.zeros_like(c))
+            cam = _normalize_per_record(cam, cover)
     return RecordingScore(starts=starts, logits=logits, prob=prob, finite=finite, prob_max=pmax, prob_mean=pmean,
                           cam=cam, cover=cover, fs=fs if ratio is None else model_fs, source_len=source_len,
                           quality=qtab, lead_ok=lead_ok, usable=usable)

@@ -12,48 +12,9 @@ import pytest
 import torch
 
 import fir_ref as fr
+from input_util import _model, _score, dev, guarded, hip, host, plan_on, unchanged  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 4097        # fp32 elements of 12345.0 on either side of the recordings
-
-
-@pytest.fixture(scope="module")
-def hip():
-    assert torch.cuda.is_available()
-    import ecg_hip
-    from ecg_hip import _lib, functional
-    ecg_hip.load()
-    _lib.call("ecg_check_device")
-    return functional
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def guarded(x):
-    """x [R, leads, Ttot] on the host -> (the same values on the device, contiguous, in the middle of a buffer of 12345.0;
-    the whole buffer)."""
-    big = torch.full((x.size + 2 * GUARD,), 12345.0, dtype=torch.from_numpy(x).dtype)
-    big[GUARD:GUARD + x.size] = torch.from_numpy(x.reshape(-1))
-    big = big.cuda()
-    return big[GUARD:GUARD + x.size].view(x.shape), big
-
-
-def plan_on(Ttot, T, hop, first):
-    """The window rule with a first start that need not be 0 and tail="shift": -> (first, hop, W, last_start, starts)."""
-    wreg = (Ttot - T - first) // hop + 1
-    starts = [first + w * hop for w in range(wreg)]
-    last = -1
-    if (Ttot - T - first) % hop != 0:
-        last = Ttot - T
-        starts.append(last)
-    return first, hop, len(starts), last, tuple(starts)
 
 
 # (half, leads, T, first).  half = 0: taps [1.0], the output is the unfiltered physical windows; 363 and 2720: the real
@@ -102,12 +63,6 @@ def case_data(case):
     dx, big = guarded(x)
     assert dx.data_ptr() % 8 == 4
     return dict(x=x, p=p, y=y, plan=plan, Ttot=Ttot, taps=taps, c=c, dx=dx, big=big)
-
-
-def unchanged(c):
-    big = host(c["big"])
-    return (np.array_equal(big[GUARD:-GUARD], c["x"].reshape(-1)) and (big[:GUARD] == 12345.0).all()
-            and (big[-GUARD:] == 12345.0).all())
 
 
 @pytest.mark.parametrize("case", CASES, ids=IDS)
@@ -161,19 +116,6 @@ def test_a_filtered_sample_does_not_depend_on_its_window(hip, case):
                                normalize=False))
     assert np.array_equal(two[0], two[1]) and np.array_equal(two[0], phys[0])
     assert unchanged(c)
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-def _model():
-    from src.models.ecg_cnn import ECGCNN
-    from src.utils.seed import set_seed
-    set_seed(42)
-    return ECGCNN(num_labels=5).cuda().eval()
-
-
-def _score(*a, **kw):
-    from ecg_hip.recording import score_recording
-    return score_recording(*a, **kw)
 
 
 def test_invalid_samples_poison_what_the_restatement_says(hip):

@@ -5,29 +5,12 @@ import numpy as np
 import pytest
 import torch
 
+from input_util import dev, hip, host  # noqa: F401
 from util import golden
 
 from oracle import input_oracle as io_ref
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hip():
-    assert torch.cuda.is_available()
-    import ecg_hip
-    from ecg_hip import _lib, functional
-    ecg_hip.load()
-    _lib.call("ecg_check_device")
-    return functional
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 def test_committed_reference_windows_bit_for_bit(hip):

@@ -12,43 +12,9 @@ import pytest
 import torch
 
 import quality_ref as qr
+from input_util import GUARD, _model, _score, dev, guarded, hip, host, plan_on, unchanged  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 4097        # int16 elements of the guard value on either side of the stream
-
-
-@pytest.fixture(scope="module")
-def hip():
-    assert torch.cuda.is_available()
-    import ecg_hip
-    from ecg_hip import _lib, functional
-    ecg_hip.load()
-    _lib.call("ecg_check_device")
-    return functional
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def guarded(d, value=12345):
-    """d int16 on the host -> (the same values on the device, contiguous, in the middle of a buffer of `value`; the buffer)."""
-    big = torch.full((d.size + 2 * GUARD,), value, dtype=torch.int16)
-    big[GUARD:GUARD + d.size] = torch.from_numpy(d.reshape(-1))
-    big = big.cuda()
-    return big[GUARD:GUARD + d.size].view(d.shape), big
-
-
-def plan_on(Ttot, T, hop, first):
-    """The window rule with a first start that need not be 0 and tail="shift": -> (first, hop, W, last_start)."""
-    wreg = (Ttot - T - first) // hop + 1
-    last = Ttot - T if (Ttot - T - first) % hop != 0 else -1
-    return first, hop, wreg + (last >= 0), last
 
 
 # (leads, T, first, hop, up, down), windows on the model's axis.  (1, 1, ...): no pair at all; (5, 37, 3, 20): window bases
@@ -94,7 +60,7 @@ def case_data(case):
     Tq0 = -(-T * down // up)
     Ttot = 2 * Tq0 + Tq0 // 2 + 6
     Tout = -(-Ttot * up // down)
-    first, hop, W, last = plan_on(Tout, T, hop, first)
+    first, hop, W, last = plan_on(Tout, T, hop, first)[:4]
     a, Tq = qr.source_starts(Ttot, T, first, hop, W, last, up, down)
     assert Tq == Tq0 and W >= 3
     rng = np.random.default_rng(leads * 10000 + T)
@@ -106,12 +72,6 @@ def case_data(case):
     return dict(d=d, dd=dd, big=big, Ttot=Ttot, Tq=Tq, a=a, plan=(first, hop, W, last), rails=rails,
                 want=qr.table(d, T, first, hop, W, last, up, down),
                 want_rails=qr.table(d, T, first, hop, W, last, up, down, rails))
-
-
-def unchanged(c, value=12345):
-    big = host(c["big"])
-    return (np.array_equal(big[GUARD:-GUARD], c["d"].reshape(-1)) and (big[:GUARD] == value).all()
-            and (big[-GUARD:] == value).all())
 
 
 def mismatch(got, want):
@@ -211,18 +171,6 @@ def test_bad_arguments_are_refused(hip):
 # ---------------------------------------------------------------------------------------------------------------------
 # end to end
 # ---------------------------------------------------------------------------------------------------------------------
-def _model():
-    from src.models.ecg_cnn import ECGCNN
-    from src.utils.seed import set_seed
-    set_seed(42)
-    return ECGCNN(num_labels=5).cuda().eval()
-
-
-def _score(*a, **kw):
-    from ecg_hip.recording import score_recording
-    return score_recording(*a, **kw)
-
-
 WINDOW = 256
 
 

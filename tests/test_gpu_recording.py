@@ -5,30 +5,13 @@ import numpy as np
 import pytest
 import torch
 
+from input_util import _model, dev, hip, host  # noqa: F401
 from util import golden
 
 from oracle import input_oracle as io_ref
 from test_recording_host import overlap_mean_ref
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def hip():
-    assert torch.cuda.is_available()
-    import ecg_hip
-    from ecg_hip import _lib, functional
-    ecg_hip.load()
-    _lib.call("ecg_check_device")
-    return functional
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 def recording(R, Ttot, leads, seed):
@@ -135,14 +118,6 @@ def test_overlap_mean_equals_the_numpy_definition(hip, case):
 # ---------------------------------------------------------------------------------------------------------------------
 # end to end
 # ---------------------------------------------------------------------------------------------------------------------
-def _model(name):
-    from src.models.ecg_cnn import ECGCNN
-    from src.models.ecg_multimodal import ECGMultimodal
-    from src.utils.seed import set_seed
-    set_seed(42)
-    return (ECGCNN(num_labels=5) if name == "cnn" else ECGMultimodal()).cuda().eval()
-
-
 @pytest.mark.parametrize("name", ["cnn", "multimodal"])
 def test_score_recording_equals_a_manual_loop(hip, name):
     import ecg_hip
@@ -203,6 +178,69 @@ def test_score_recording_equals_a_manual_loop(hip, name):
     s1 = score_recording(model, dd[0], dg[0], db[0], window=window, hop=hop, batch_size=16,
                          x_demo=None if xd is None else xd[:1])
     assert tuple(s1.logits.shape) == (1, W, 5) and torch.equal(s1.logits[0], s.logits[0])
+
+
+@pytest.mark.parametrize("R,batch", [(1, 2), (3, 16)])
+def test_score_recording_launches_what_the_plan_says(hip, monkeypatch, R, batch):
+    """The input-step launches of one score_recording call, in order, are what plan_chunks says: without filter= one
+    normalising ecg_wfdb16_windows[_resampled] per chunk; with filter= one whole-recording launch of it (W = 1, stats NULL)
+    per distinct (r0, r1) group and one ecg_fir_windows per chunk; ecg_wfdb16_quality once and first when quality is set;
+    ecg_windows_overlap_mean once and last when CAMs are asked for; nothing else of the input step.  The results of a launch
+    made once per chunk instead of once per group are bit-identical, so only the launch list can tell.
+    (1, 2): 6 windows in 3 chunks of one group; (3, 16): groups of two recordings, 2 chunks."""
+    import sys
+
+    from ecg_hip import _lib
+    from ecg_hip.recording import plan_chunks, score_recording, window_plan
+    model = _model("cnn")
+    window, taps = 200, np.array([0.25, 0.5, 0.25])
+    stats_at = {"ecg_wfdb16_windows": 4, "ecg_wfdb16_windows_resampled": 5, "ecg_fir_windows": 3}     # (W follows 7 later)
+    others = ("ecg_wfdb16_quality", "ecg_windows_overlap_mean", "ecg_wfdb16_physical", "ecg_wfdb16_zscore", "ecg_zscore_rows",
+              "ecg_wfdb_decode16")
+    seen, raw = [], _lib.call
+
+    def spy(name, *args):
+        if name in stats_at:
+            seen.append((name, args[stats_at[name]] is not None, args[stats_at[name] + 7]))
+        elif name in others:
+            seen.append((name, None, None))
+        raw(name, *args)
+
+    plan = window_plan(700, window, window // 2)
+    chunks = plan_chunks(R, plan, batch)
+    groups = {(c[0], c[1]) for c in chunks}
+    assert plan[2] == 6 and (len(chunks), len(groups)) == {1: (3, 1), 3: (2, 2)}[R]
+    rate = dict(fs=250, model_fs=100)
+    for kw in (dict(), rate, dict(filter=taps), dict(filter=taps, quality=True, cam_classes=[0, 1], **rate)):
+        Ttot = 1750 if "fs" in kw else 700          # 1750 samples at 250 Hz are 700 on the model's axis
+        d, gain, base = recording(R, Ttot, 12, 50 + R)
+        dd, dg, db = dev(d), dev(gain), dev(base)
+        del seen[:]
+        with monkeypatch.context() as m:            # every name the package's modules hold the ABI call under
+            for mod in [v for k, v in sys.modules.items() if k == "ecg_hip" or k.startswith("ecg_hip.")]:
+                for attr, val in list(vars(mod).items()):
+                    if val is raw:
+                        m.setattr(mod, attr, spy)
+            s = score_recording(model, dd, dg, db, window=window, batch_size=batch, **kw)
+        assert s.starts == plan[4]
+        cut = "ecg_wfdb16_windows_resampled" if "fs" in kw else "ecg_wfdb16_windows"
+        want, group = [("ecg_wfdb16_quality", None, None)] if kw.get("quality") else [], None
+        for r0, r1, _, _, Wc, _ in chunks:
+            if "filter" in kw:
+                if group != (r0, r1):
+                    want.append((cut, False, 1))
+                    group = (r0, r1)
+                want.append(("ecg_fir_windows", True, Wc))
+            else:
+                want.append((cut, True, Wc))
+        if "cam_classes" in kw:
+            want.append(("ecg_windows_overlap_mean", None, None))
+        assert seen == want, (kw.keys(), seen)
+        names = [n for n, _, _ in seen]
+        assert names.count(cut) == (len(groups) if "filter" in kw else len(chunks))
+        assert names.count("ecg_fir_windows") == (len(chunks) if "filter" in kw else 0)
+        assert names.count("ecg_wfdb16_quality") == (1 if kw.get("quality") else 0)
+        assert names.count("ecg_windows_overlap_mean") == (1 if "cam_classes" in kw else 0)
 
 
 def test_invalid_windows_are_flagged_and_left_out(hip):

@@ -12,46 +12,9 @@ import pytest
 import torch
 
 import resample_ref as rr
+from input_util import _model, _score, dev, guarded, hip, host, plan_on  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 4097        # int16 elements of 12345 on either side of the recordings
-
-
-@pytest.fixture(scope="module")
-def hip():
-    assert torch.cuda.is_available()
-    import ecg_hip
-    from ecg_hip import _lib, functional
-    ecg_hip.load()
-    _lib.call("ecg_check_device")
-    return functional
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def guarded(d):
-    """d int16 [R, Ttot, leads] on the host -> the same values on the device, contiguous, in the middle of a buffer of 12345."""
-    big = torch.full((d.size + 2 * GUARD,), 12345, dtype=torch.int16)
-    big[GUARD:GUARD + d.size] = torch.from_numpy(d.reshape(-1))
-    return big.cuda()[GUARD:GUARD + d.size].view(d.shape)
-
-
-def plan_on(Tout, T, hop, first):
-    """The window rule with a first start that need not be 0 and tail="shift": -> (first, hop, W, last_start, starts)."""
-    wreg = (Tout - T - first) // hop + 1
-    starts = [first + w * hop for w in range(wreg)]
-    last = -1
-    if (Tout - T - first) % hop != 0:
-        last = Tout - T
-        starts.append(last)
-    return first, hop, len(starts), last, tuple(starts)
 
 
 # ((up, down), leads, T, first).  T = 37: an odd tail, less than one tile; 256: whole tiles; 1000, 1500: more than one tile
@@ -81,7 +44,7 @@ def case_data(case):
     assert plan[3] == Tout - T and plan[4][0] == first      # the left edge in window 0, the right one in the shifted tail
     g, half = design_taps(up, down)
     y = [rr.resample(rr.physical(d[r], gain[r], base[r]), g, half, up, down) for r in range(R)]     # [Tout, leads] each
-    return dict(d=d, gain=gain, base=base, plan=plan, Tout=Tout, y=y, dd=guarded(d), dg=dev(gain), db=dev(base))
+    return dict(d=d, gain=gain, base=base, plan=plan, Tout=Tout, y=y, dd=guarded(d)[0], dg=dev(gain), db=dev(base))
 
 
 @pytest.mark.parametrize("case", CASES, ids=IDS)
@@ -131,7 +94,7 @@ def test_a_resampled_sample_does_not_depend_on_its_window(hip, case):
         assert np.array_equal(phys[:, w], whole[:, 0, :, s:s + T])
     # the same recording in both slots of a batch: the same bits
     twice = np.stack([c["d"][0], c["d"][0]])
-    two = host(hip.wfdb16_windows_resampled(guarded(twice), c["dg"][:1].repeat(2, 1), c["db"][:1].repeat(2, 1), T, first, hop,
+    two = host(hip.wfdb16_windows_resampled(guarded(twice)[0], c["dg"][:1].repeat(2, 1), c["db"][:1].repeat(2, 1), T, first, hop,
                                             W, last, up, down, normalize=False))
     assert np.array_equal(two[0], two[1]) and np.array_equal(two[0], phys[0])
 
@@ -153,12 +116,12 @@ def test_invalid_sample_poisons_what_the_restatement_says(hip, ratio):
     want = rr.windows(y, starts, T)
     bad = np.isnan(want)
     assert bad[:, 3].any() and not np.delete(bad, 3, axis=1).any()
-    phys = host(hip.wfdb16_windows_resampled(guarded(d), dev(gain), dev(base), T, first, hop, W, last, up, down,
+    phys = host(hip.wfdb16_windows_resampled(guarded(d)[0], dev(gain), dev(base), T, first, hop, W, last, up, down,
                                              normalize=False))[0]
     assert np.array_equal(np.isnan(phys), bad) and np.array_equal(phys, want, equal_nan=True)
     # score_recording: exactly the windows that hold one are flagged
     model = _model()
-    s = _score(model, guarded(d), dev(gain), dev(base), window=T, hop=hop, fs=down * 100, model_fs=up * 100)
+    s = _score(model, guarded(d)[0], dev(gain), dev(base), window=T, hop=hop, fs=down * 100, model_fs=up * 100)
     assert s.starts == starts
     assert np.array_equal(host(s.finite)[0], ~bad.any(axis=(1, 2)))
     assert not host(s.finite).all() and host(s.finite).any()
@@ -167,7 +130,7 @@ def test_invalid_sample_poisons_what_the_restatement_says(hip, ratio):
 def test_bad_arguments_are_refused(hip):
     from ecg_hip import EcgHipError
     from ecg_hip.resample import device_taps
-    d = guarded(np.zeros((1, 600, 12), np.int16))
+    d = guarded(np.zeros((1, 600, 12), np.int16))[0]
     gain, base = dev(np.full((1, 12), 1000.0)), dev(np.zeros((1, 12), np.int32))
     taps, ntap, half = device_taps(1, 5, d.device)           # Tout = 120
     assert (ntap, half) == (101, 50)
@@ -182,7 +145,7 @@ def test_bad_arguments_are_refused(hip):
                     (dict(last_start=71), "last_start"), (dict(window=121, W=1), "longer than")):
         with pytest.raises(EcgHipError, match=msg):
             call(**kw)
-    d17 = guarded(np.zeros((1, 600, 17), np.int16))
+    d17 = guarded(np.zeros((1, 600, 17), np.int16))[0]
     with pytest.raises(EcgHipError, match="leads=17"):
         call(dd=d17, g=dev(np.full((1, 17), 1000.0)), b=dev(np.zeros((1, 17), np.int32)))
     for kw in (dict(up=0, down=5), dict(up=1, down=513)):
@@ -195,18 +158,6 @@ def test_bad_arguments_are_refused(hip):
 # ---------------------------------------------------------------------------------------------------------------------
 # end to end
 # ---------------------------------------------------------------------------------------------------------------------
-def _model():
-    from src.models.ecg_cnn import ECGCNN
-    from src.utils.seed import set_seed
-    set_seed(42)
-    return ECGCNN(num_labels=5).cuda().eval()
-
-
-def _score(*a, **kw):
-    from ecg_hip.recording import score_recording
-    return score_recording(*a, **kw)
-
-
 def test_score_recording_at_another_rate(hip):
     import ecg_hip
     from ecg_hip.resample import design_taps, resampled_length
@@ -215,7 +166,7 @@ def test_score_recording_at_another_rate(hip):
     rng = np.random.default_rng(31)
     d = rng.integers(-3000, 3000, size=(1, Ttot, 12)).astype(np.int16)
     gain, base = np.full((1, 12), 1000.0), rng.integers(-9, 9, size=(1, 12)).astype(np.int32)
-    dd, dg, db = guarded(d), dev(gain), dev(base)
+    dd, dg, db = guarded(d)[0], dev(gain), dev(base)
     Tout = resampled_length(Ttot, 1, 5)
     assert Tout == 1201
     g, half = design_taps(1, 5)
@@ -242,7 +193,7 @@ def test_equal_or_missing_rates_never_reach_the_resampler(hip, monkeypatch):
     model = _model()
     rng = np.random.default_rng(32)
     d = rng.integers(-3000, 3000, size=(1, 700, 12)).astype(np.int16)
-    dd, dg, db = guarded(d), dev(np.full((1, 12), 1000.0)), dev(np.zeros((1, 12), np.int32))
+    dd, dg, db = guarded(d)[0], dev(np.full((1, 12), 1000.0)), dev(np.zeros((1, 12), np.int32))
     base = _score(model, dd, dg, db, window=200)
     assert base.fs is None and base.source_len == 700
 

@@ -11,30 +11,13 @@ import torch
 import wfdbraw_ref as ref
 from ecg_hip import wfdb16, wfdbraw
 from ecg_hip.wfdb16 import WfdbFormatError
+from input_util import _model, dev, hip, host  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 TILE = 512          # kDecTile of csrc/wfdb_decode.hip: frames per workgroup
 FORMATS = wfdbraw.FORMATS
 RANGE = {16: (-32767, 32767), 61: (-32767, 32767), 160: (-32767, 32767), 80: (-127, 127), 212: (-2047, 2047)}
-
-
-@pytest.fixture(scope="module")
-def hip():
-    assert torch.cuda.is_available()
-    import ecg_hip
-    from ecg_hip import _lib, functional
-    ecg_hip.load()
-    _lib.call("ecg_check_device")
-    return functional
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 def stored(fmt, n, seed):
@@ -231,13 +214,6 @@ def test_abi_refusals_launch_nothing(hip):
 
 
 # ---- end to end -----------------------------------------------------------------------------------------------------
-
-def _model():
-    from src.models.ecg_cnn import ECGCNN
-    from src.utils.seed import set_seed
-    set_seed(42)
-    return ECGCNN(num_labels=5).cuda().eval()
-
 
 @pytest.fixture(scope="module")
 def strip():
