@@ -10,14 +10,12 @@ import copy
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as TF
 
-from util import golden, sd_from_npz
+from util import bf16_eval_launch, bf16_eval_params, bf16_eval_reference, bf16_f64, golden, sd_from_npz, ulp_bf16
 from oracle import ref_models as R
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-EPS = 1e-5
 
 
 @pytest.fixture(scope="module")
@@ -29,62 +27,8 @@ def hip():
     return _lib
 
 
-def _bf16(a):
-    return torch.as_tensor(a).to(torch.bfloat16).double()
-
-
-def _ulp_bf16(v):
-    """One bf16 ulp at |v| (normal range)."""
-    e = torch.floor(torch.log2(v.abs().clamp_min(1e-30)))
-    return torch.pow(2.0, e - 7)
-
-
-def _params(Ci, Co, seed):
-    g = torch.Generator().manual_seed(seed)
-    w = torch.randn(Co, Ci, 15, generator=g) / np.sqrt(Ci * 15)
-    b = torch.randn(Co, generator=g) * 0.1
-    gamma = 1.0 + 0.2 * torch.randn(Co, generator=g)
-    beta = 0.1 * torch.randn(Co, generator=g)
-    rm = 0.2 * torch.randn(Co, generator=g)
-    rv = torch.rand(Co, generator=g) + 0.5
-    return w, b, gamma, beta, rm, rv
-
-
-def _reference(x, w, b, gamma, beta, rm, rv):
-    """float64 conv of bf16(x), bf16(w), eval BatchNorm, ReLU, MaxPool(2): [N][C][Lo/2]."""
-    y = TF.conv1d(_bf16(x), _bf16(w), b.double(), padding=7)
-    z = (y - rm.double()[:, None]) / torch.sqrt(rv.double()[:, None] + EPS) * gamma.double()[:, None] + beta.double()[:, None]
-    return TF.max_pool1d(torch.relu(z), 2)
-
-
-def _launch(hip, x, w, b, gamma, beta, rm, rv, out, x_bf16_rows=False):
-    """Run one bf16 eval block on the GPU.  out: 'bf16' | 'fp32' | 'gap'.  Returns the output (device)."""
-    from ecg_hip import functional as F
-    N, Ci, Lx = x.shape
-    Co = w.shape[0]
-    wd, bd, gd, bed, rmd, rvd = (t.to(DEV).float().contiguous() for t in (w, b, gamma, beta, rm, rv))
-    wb, _ = F.conv1d_pack_bf16(wd, need_bwd=False)
-    if x_bf16_rows:
-        ldx = (Lx + 7) & ~7
-        xd = torch.zeros(N, Ci, ldx, dtype=torch.bfloat16, device=DEV)
-        xd[:, :, :Lx] = x.to(DEV).to(torch.bfloat16)
-    else:
-        ldx, xd = 0, x.to(DEV).float().contiguous()
-    Lo = Lx
-    args = (hip.ptr(xd), 1 if x_bf16_rows else 0, ldx, hip.ptr(wb), hip.f32(bd), hip.f32(gd), hip.f32(bed), hip.f32(rmd),
-            hip.f32(rvd), EPS)
-    if out == "gap":
-        g = torch.empty(N, Co, device=DEV)
-        hip.call("ecg_conv1d_bn_relu_pool_gap_eval_fwd_bf16", *args, hip.f32(g), N, Ci, Co, Lx, 15, 7, hip.stream())
-        return g
-    if out == "bf16":
-        ldp = (Lo // 2 + 7) & ~7
-        p = torch.full((N, Co, ldp), float("nan"), dtype=torch.bfloat16, device=DEV)     # the pad must be written
-        hip.call("ecg_conv1d_bn_relu_pool_eval_fwd_bf16", *args, hip.ptr(p), 1, ldp, N, Ci, Co, Lx, 15, 7, hip.stream())
-        return p
-    p = torch.full((N, Co, Lo // 2), float("nan"), device=DEV)
-    hip.call("ecg_conv1d_bn_relu_pool_eval_fwd_bf16", *args, hip.ptr(p), 0, 0, N, Ci, Co, Lx, 15, 7, hip.stream())
-    return p
+# operands, float64 reference and launch of one bf16 eval block: shared with test_gpu_conv_padding.py (tests/util.py)
+_bf16, _ulp_bf16, _params, _reference, _launch = bf16_f64, ulp_bf16, bf16_eval_params, bf16_eval_reference, bf16_eval_launch
 
 
 # (C_in, C_out, L, x as bf16 rows, N): the four blocks at 12x1000 and 12x5000, batch sizes no tile divides, an odd Lo

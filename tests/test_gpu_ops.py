@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from util import check_put, golden
+from util import bf16_round as _bf16_round, bf16_rows as _bf16_rows, check_put, dev, golden, host
 
 pytestmark = pytest.mark.gpu
 
@@ -20,14 +20,6 @@ def hip():
     ecg_hip.load()
     _lib.call("ecg_check_device")
     return functional
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 def conv_all(hip, x, w, b, dy, pad=7):
@@ -858,18 +850,6 @@ def test_eval_fused_conv_bn_relu_pool_gap(hip, oracle, shape):
     with pytest.raises(L.EcgHipError, match="not covered"):
         L.call("ecg_conv1d_bn_relu_pool_gap_eval_fwd", L.f32(args[0]), L.f32(w_fwd), *map(L.f32, args[1:]), 1e-5, L.f32(g),
                N, Ci, Co, 1000, 15, 7, L.stream())
-
-
-def _bf16_round(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(torch.bfloat16).to(torch.float32).numpy()
-
-
-def _bf16_rows(a, ld, fill=0.0):
-    """fp32 host array [N][C][L] -> bf16 device tensor [N][C][ld], rows padded with `fill` past L."""
-    a = np.asarray(a)
-    t = torch.full((a.shape[0], a.shape[1], ld), fill, dtype=torch.bfloat16, device="cuda")
-    t[:, :, :a.shape[2]] = dev(np.ascontiguousarray(a)).to(torch.bfloat16)
-    return t
 
 
 # every tile configuration of the round-2 bf16 kernel (short rows): 32x256, 64x256 (rows > 160), 64x128, 128x256 (eight waves),

@@ -123,8 +123,10 @@ def bn_pool_ref(y, gamma, beta, mean, invstd, gap=False):
 # A. containment (and the non-finite sets of B) — convolutions
 # =====================================================================================================================
 # (N, Ci, Co, L, K, pad): the four block geometries at their smallest established sizes + the generic direct kernel
+# (the tests of the one-launch eval blocks take CONV[:4]: they hard-code 15/7);
+# last two: the MFMA kernels at K = 15 with the extreme paddings — output rows of 243 (from 257) and 144 (from 130)
 CONV = [(3, 12, 32, 300, 15, 7), (2, 32, 64, 257, 15, 7), (2, 64, 128, 130, 15, 7), (2, 128, 256, 70, 15, 7),
-        (2, 7, 12, 50, 3, 1)]
+        (2, 7, 12, 50, 3, 1), (2, 32, 64, 257, 15, 0), (2, 64, 128, 130, 15, 14)]
 
 
 @functools.lru_cache(maxsize=None)

@@ -73,8 +73,31 @@ RIDER_CASES = [
 @pytest.mark.parametrize("case", RIDER_CASES, ids=[c[0] for c in RIDER_CASES])
 def test_rider_matches_the_two_entry_points(hip, case):
     _, N, Ci, Co, L, padded = case
-    a, b, ldy = _both(hip, N, Ci, Co, L, padded=padded)
-    assert (ldy > L) == padded
+    K, pad = 15, 7
+    a, b, ldy = _both(hip, N, Ci, Co, L, K, pad, padded=padded)
+    Lo = L + 2 * pad - K + 1
+    assert (ldy > Lo) == padded
+    _assert_same(a, b)
+
+
+# (id, N, Ci, Co, Lo, padded dY rows): the output row is given, the input row follows from the padding
+RIDER_PAD_CASES = [
+    ("fast_fir_wgrad", 3, 128, 128, 70, True),
+    ("tile_64", 2, 32, 64, 257, True),
+    ("dense_rows_128", 3, 128, 128, 70, False),
+]
+
+
+@pytest.mark.parametrize("pad", [0, 8, 14])
+@pytest.mark.parametrize("case", RIDER_PAD_CASES, ids=[c[0] for c in RIDER_PAD_CASES])
+def test_rider_matches_the_two_entry_points_at_other_paddings(hip, case, pad):
+    """K = 15 with a padding other than 7: the input-gradient launch that carries the riders has padding 14 - pad and writes
+    dx rows of L = Lo + 14 - 2 pad, longer or shorter than the dY rows it reads."""
+    _, N, Ci, Co, Lo, padded = case
+    L = Lo + 14 - 2 * pad
+    a, b, ldy = _both(hip, N, Ci, Co, L, pad=pad, padded=padded, seed=4 + pad)
+    assert ldy >= Lo and (ldy > Lo) == padded
+    assert a[2].shape == (N, Ci, L)
     _assert_same(a, b)
 
 
