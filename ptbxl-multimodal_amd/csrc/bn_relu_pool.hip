@@ -5,13 +5,12 @@
 //
 // Replaces ATen native_batch_norm(_backward), threshold(_backward), max_pool2d_with_indices
 // (_backward) behind ConvBlock.net[1..3] (reference src/models/ecg_cnn.py:14-16).
-#include "common.h"
+#include "bn_common.h"
+#include "bf16_util.h"
 #include <atomic>
 #include <cstdlib>
 
 namespace ecg {
-
-constexpr int kBlock = 256;
 
 // the pooling pair (r[0], r[1]) as ONE 8-byte load when the pair is 8-byte aligned (even row length: every row of
 // the 12x1000 / 12x5000 models except the last block's), two 4-byte loads otherwise (AL8 is chosen per launch by the host)
@@ -31,34 +30,17 @@ template <bool AL8, bool YH>
 __device__ __forceinline__ void ld_pair_y(const float *y, size_t row, int ld, int t, float &a, float &b) {
     if (YH) {
         const unsigned v = *reinterpret_cast<const unsigned *>(reinterpret_cast<const unsigned short *>(y) + row * ld + t);
-        a = __uint_as_float(v << 16);
-        b = __uint_as_float(v & 0xFFFF0000u);
+        a = bf16_lo(v);
+        b = bf16_hi(v);
     } else ld_pair<AL8>(y + row * ld + t, a, b);
 }
 
 // ---------------------------------------------------------------------------------------
 // statistics
 // ---------------------------------------------------------------------------------------
-// Workgroups of the streaming passes: 2048 = 256 CUs x 8 resident 256-thread workgroups, i.e. exactly one round (every
-// workgroup pays the folded statistics combine once, none waits for a slot).  Measured per train step at B=256 12x1000:
-// 1024: +9 us, 1536: -3, 2048: -10, 2560: +6, 3072: +3, 4096: 0 (round 1's value), 8192: +42.
-constexpr int kStreamBlocks = 2048;
-// workgroups of the reduce passes per channel.  fp32 operands: 1024 in all (2048 measured the same at 12x1000, 512 slower).
-// bf16 operands (the bf16-storage backward, `wide`): 2048 — that pass is bound by the latency of its dependent load rounds
-// (6 bytes per position: the number of loads in flight per thread, the per-position instruction count and the walk order
-// were all varied without effect), and twice the workgroups took 4-11 us off every backward call of 12x5000 (config-5 step
-// 1.449 -> 1.415 ms); 4096 adds nothing.
-static int stat_splits(int N, int C, bool wide = false) {
-    int s = cdiv(wide ? 2048 : 1024, C);
-    if (s > N) s = N;
-    if (s < 1) s = 1;
-    return s;
-}
-
 // partials[c][s][2] = (sum y, sum y^2) over n in split s.  grid = (C, S)
 __global__ __launch_bounds__(kBlock) void bn_stat_partials_kernel(
     const float *__restrict__ y, float *__restrict__ partials, int N, int C, int L, int S) {
-    __shared__ float red[4][2];
     const int c = blockIdx.x, s = blockIdx.y, tl = threadIdx.x;
     const int n0 = (int)((long long)N * s / S), n1 = (int)((long long)N * (s + 1) / S);
     float a = 0.f, q = 0.f;
@@ -68,58 +50,8 @@ __global__ __launch_bounds__(kBlock) void bn_stat_partials_kernel(
         const float v = y[((size_t)(n0 + nl) * C + c) * L + t];
         a += v; q = __fmaf_rn(v, v, q);
     }
-    a = wave_sum(a); q = wave_sum(q);
-    if ((tl & 63) == 0) { red[tl >> 6][0] = a; red[tl >> 6][1] = q; }
-    __syncthreads();
-    if (tl < 2)
-        partials[((size_t)c * S + s) * 2 + tl] = red[0][tl] + red[1][tl] + red[2][tl] + red[3][tl];
-}
-
-// Double-precision, fixed-order combine of the P statistics partials of channel c by one 256-thread workgroup
-// (thread t sums partials t, t+256, ...; lanes by butterfly; waves 0..3 in order) -> batch mean / invstd, returned
-// to every thread.  `writer` (one workgroup per channel) also stores them and updates the running statistics
-// (momentum, unbiased variance) and, for channel 0, the batch counter.  Used by bn_finalize_kernel (its own launch)
-// and, FOLDED IN, by the BN+ReLU+pool forward kernels: every workgroup re-derives the numbers of its channel from
-// L2 instead of waiting for a 4.7 us launch per layer; same arithmetic, same bits.
-struct BnFin {
-    const float *partials; int P; double count; float *mean, *invstd, *running_mean, *running_var;
-    long long *nbt; float momentum, eps;
-};
-__device__ __forceinline__ void bn_finalize_block(const BnFin &f, int c, bool writer, float &mu_out, float &is_out) {
-    __shared__ double red[4][2];
-    __shared__ float res[2];
-    const int tl = threadIdx.x;
-    const float2 *pc = reinterpret_cast<const float2 *>(f.partials) + (size_t)c * f.P;
-    double a = 0.0, q = 0.0;
-    for (int p = tl; p < f.P; p += 256) {
-        const float2 v = pc[p];
-        a += (double)v.x;
-        q += (double)v.y;
-    }
-    a = wave_sum(a); q = wave_sum(q);
-    if ((tl & 63) == 0) { red[tl >> 6][0] = a; red[tl >> 6][1] = q; }
-    __syncthreads();
-    if (tl == 0) {
-        a = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
-        q = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
-        const double mu = a / f.count;
-        double var = q / f.count - mu * mu;
-        if (var < 0.0) var = 0.0;
-        const float mf = (float)mu, isf = (float)(1.0 / sqrt(var + (double)f.eps));
-        res[0] = mf; res[1] = isf;
-        if (writer) {
-            f.mean[c] = mf;
-            f.invstd[c] = isf;
-            if (f.running_mean) {
-                const double unb = f.count > 1.0 ? var * f.count / (f.count - 1.0) : var;
-                f.running_mean[c] = (float)((1.0 - f.momentum) * f.running_mean[c] + f.momentum * mu);
-                f.running_var[c] = (float)((1.0 - f.momentum) * f.running_var[c] + f.momentum * unb);
-            }
-            if (f.nbt && c == 0) *f.nbt += 1;
-        }
-    }
-    __syncthreads();
-    mu_out = res[0]; is_out = res[1];
+    const PairSums<float> &red = block_pair_reduce(a, q);
+    if (tl < 2) partials[((size_t)c * S + s) * 2 + tl] = block_pair_total(red, tl);
 }
 
 __global__ __launch_bounds__(256) void bn_finalize_kernel(BnFin f) {
@@ -236,13 +168,6 @@ __global__ __launch_bounds__(kBlock) void bn_apply_fwd_kernel(
 // ---------------------------------------------------------------------------------------
 // backward
 // ---------------------------------------------------------------------------------------
-// da for the pair (2j, 2j+1): returns the arg-max slot am (0/1) and whether the gradient passes.
-__device__ __forceinline__ bool pool_route(float y0, float y1, float mu, float sc, float be, int &am) {
-    float a0 = bn_apply1(y0, mu, sc, be), a1 = bn_apply1(y1, mu, sc, be);
-    am = pool_takes1(a0, a1) ? 1 : 0;      // first element wins a tie, a NaN wins (max_pool1d keeps the first index / the NaN)
-    return relu_passes(am ? a1 : a0);      // ReLU backward: everything but output <= 0 (a NaN passes its gradient)
-}
-
 // partials[c][s][2] = (sum da, sum da*xhat).  FUSED: da routed from dp through pool+ReLU;
 // otherwise da = dout (plain BatchNorm backward).  grid = (C, S).
 // bcast != 0 (FUSED only): dp[row][j] = g[row] * bcast for every j — the gradient of a global
@@ -253,7 +178,6 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_kernel(
     const float *__restrict__ beta, const float *__restrict__ mean,
     const float *__restrict__ invstd, float *__restrict__ partials, int N, int C, int L, int S,
     float bcast) {
-    __shared__ float red[4][2];
     const int c = blockIdx.x, s = blockIdx.y, tl = threadIdx.x;
     const int n0 = (int)((long long)N * s / S), n1 = (int)((long long)N * (s + 1) / S);
     const float mu = mean[c], is = invstd[c], sc = is * gamma[c], be = FUSED ? beta[c] : 0.f;
@@ -299,19 +223,14 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_kernel(
             }
         }
     }
-    a = wave_sum(a); q = wave_sum(q);
-    if ((tl & 63) == 0) { red[tl >> 6][0] = a; red[tl >> 6][1] = q; }
-    __syncthreads();
-    if (tl < 2)
-        partials[((size_t)c * S + s) * 2 + tl] = red[0][tl] + red[1][tl] + red[2][tl] + red[3][tl];
+    const PairSums<float> &red = block_pair_reduce(a, q);
+    if (tl < 2) partials[((size_t)c * S + s) * 2 + tl] = block_pair_total(red, tl);
 }
 
 // dy[t] = gamma*invstd * (da[t] - k1 - xhat[t]*k2), (k1, k2) = (dbeta, dgamma) / M in train mode, (0, 0) in eval mode.
 // grid = (C, S2): a block owns channel c and the samples of split s2 and walks their (sample, output pair) positions
 // flat, four iterations in flight (all loads unconditional, as in the reduce kernel above).
-// The combine of the S reduce partials is FOLDED in: every block re-derives (dbeta, dgamma) of its channel in double,
-// in a fixed order (thread t sums partials t, t+256, ...; lanes by butterfly; waves 0..3 in order) — S <= 1024/C + 1
-// numbers out of L2 — instead of a separate 4.9 us launch per layer; block s2 == 0 writes dbeta / dgamma.
+// The combine of the S reduce partials is FOLDED in (bn_grad_terms_block); block s2 == 0 writes dbeta / dgamma.
 // dy rows have stride ldy >= L; the pad [L, ldy) is written as zeros (Lh = ceil(ldy/2) pairs per row): the
 // weight-gradient kernel streams such rows by LDS-DMA and needs the zeros.
 template <bool FUSED, bool AL8>
@@ -321,31 +240,9 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_dx_kernel(
     const float *__restrict__ invstd, const float *__restrict__ partials, int S, double M,
     float *__restrict__ dgamma, float *__restrict__ dbeta, float *__restrict__ dy,
     int N, int C, int L, int ldy, int Lh, int S2, float bcast, int train) {
-    __shared__ double red[4][2];
-    __shared__ float kk[2];
     const int c = blockIdx.x, s2 = blockIdx.y, tl = threadIdx.x;
-    {
-        double a = 0.0, q = 0.0;
-        for (int p = tl; p < S; p += kBlock) {
-            a += (double)partials[((size_t)c * S + p) * 2];
-            q += (double)partials[((size_t)c * S + p) * 2 + 1];
-        }
-        a = wave_sum(a); q = wave_sum(q);
-        if ((tl & 63) == 0) { red[tl >> 6][0] = a; red[tl >> 6][1] = q; }
-        __syncthreads();
-        if (tl == 0) {
-            a = ((red[0][0] + red[1][0]) + red[2][0]) + red[3][0];
-            q = ((red[0][1] + red[1][1]) + red[2][1]) + red[3][1];
-            if (s2 == 0) {
-                if (dbeta) dbeta[c] = (float)a;
-                if (dgamma) dgamma[c] = (float)q;
-            }
-            kk[0] = train ? (float)(a / M) : 0.f;
-            kk[1] = train ? (float)(q / M) : 0.f;
-        }
-        __syncthreads();
-    }
-    const float k1 = kk[0], k2 = kk[1];
+    float k1, k2;
+    bn_grad_terms_block(partials, S, c, M, train, s2 == 0, dgamma, dbeta, k1, k2);
     const float mu = mean[c], is = invstd[c], ga = gamma[c], sc = is * ga, gi = ga * is;
     const float be = FUSED ? beta[c] : 0.f;
     const int n0 = (int)((long long)N * s2 / S2), n1 = (int)((long long)N * (s2 + 1) / S2);
@@ -707,14 +604,6 @@ ECG_API int ecg_bn_invstd(const float *var, float *invstd, int C, float eps, ecg
 }
 
 // ---- BN-apply + ReLU + MaxPool(2) forward, optionally with the statistics combine folded in (fin != NULL) ----------
-static int check_fin(const char *who, const BnFin &f, int C) {
-    ECG_REQUIRE(f.partials && f.mean && f.invstd, "%s: null pointer", who);
-    ECG_REQUIRE(f.P > 0 && C > 0 && f.count > 0, "%s: P=%d C=%d count=%g", who, f.P, C, f.count);
-    ECG_REQUIRE((f.running_mean == nullptr) == (f.running_var == nullptr),
-                "%s: running_mean/var must both be given or both NULL", who);
-    return ECG_OK;
-}
-
 static int pool_fwd_impl(const BnFin *fin, const float *y, const float *gamma, const float *beta, const float *mean,
                          const float *invstd, float *p, int N, int C, int L, hipStream_t st) {
     int rc = check_ncl("bn_relu_pool_fwd", N, C, L);
@@ -723,8 +612,7 @@ static int pool_fwd_impl(const BnFin *fin, const float *y, const float *gamma, c
     const int Lp = L / 2;
     if (Lp == 0 && !fin) return ECG_OK;   // MaxPool1d(2) of a length-1 row is empty
     ECG_REQUIRE(p || Lp == 0, "bn_relu_pool_fwd: null output");
-    int S2 = cdiv(kStreamBlocks, C);
-    if (S2 > N) S2 = N;
+    const int S2 = stream_splits(C, N);
     const bool al8 = pairs_aligned(y, L);
     const BnFin f = fin ? *fin : BnFin{};
 #define ECG_POOL(FIN, AL8) hipLaunchKernelGGL((bn_relu_pool_fwd_kernel<FIN, AL8>), dim3(C, S2), dim3(kBlock), 0, st, y, gamma, \
@@ -742,8 +630,7 @@ static int pool_gap_fwd_impl(const BnFin *fin, const float *y, const float *gamm
     if (rc) return rc;
     ECG_REQUIRE(y && gamma && beta && mean && invstd && g, "bn_relu_pool_gap_fwd: null pointer");
     ECG_REQUIRE(L >= 2, "bn_relu_pool_gap_fwd: L=%d leaves an empty pooled row", L);
-    int S2 = cdiv(kStreamBlocks, C);
-    if (S2 > cdiv(N, 4)) S2 = cdiv(N, 4);          // four rows (one per wave) in flight per workgroup
+    const int S2 = stream_splits(C, cdiv(N, 4));          // four rows (one per wave) in flight per workgroup
     if (yh)         // bf16 activation storage (train mode: always with the statistics combine)
         hipLaunchKernelGGL((bn_relu_pool_gap_fwd_kernel<true, true>), dim3(C, S2), dim3(kBlock), 0, st, y, gamma, beta,
                            mean, invstd, g, N, C, L, L / 2, S2, *fin, ldy);
@@ -803,7 +690,8 @@ ECG_API int ecg_bn_stats_relu_pool_gap_fwd_yh(const float *stat_partials, int P,
 
 ECG_API size_t ecg_bn_relu_pool_bwd_ws_floats(int N, int C, int L) {
     (void)L;
-    return (size_t)C * stat_splits(N, C, true) * 2 + (size_t)C * 2;      // (room for the bf16-storage pass's split count)
+    // the split count ecg_bn_relu_pool_bwd_h launches with (the fp32 passes' stat_splits(N, C) is never larger)
+    return (size_t)C * stat_splits(N, C, true) * 2 + (size_t)C * 2;
 }
 ECG_API size_t ecg_bn_bwd_ws_floats(int N, int C, int L) { return ecg_bn_relu_pool_bwd_ws_floats(N, C, L); }
 
@@ -856,8 +744,7 @@ static int bn_bwd_impl(const float *y, const float *g, const float *gamma, const
     if (rc) return rc;
     // dx pass with the combine of the reduce partials folded in (no finalize launch)
     const int Lh = (ldy + 1) / 2;
-    int S2 = cdiv(kStreamBlocks, C);            // one round of resident workgroups
-    if (S2 > N) S2 = N;
+    const int S2 = stream_splits(C, N);
     if (pairs_aligned(y, L) && L >= 2)
         hipLaunchKernelGGL((bn_bwd_dx_kernel<FUSED, true>), dim3(C, S2), dim3(kBlock), 0, st, y, g, gamma, beta, mean,
                            invstd, partials, S, (double)N * L, dgamma, dbeta, dy, N, C, L, ldy, Lh, S2, bcast, train);

@@ -275,8 +275,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 4 
         uint2 a, b;
         if constexpr (XF32) {
             auto pk = [](unsigned lo, unsigned hi) __attribute__((always_inline)) {
-                return (unsigned)__builtin_bit_cast(u16, (__bf16)__uint_as_float(lo)) |
-                       ((unsigned)__builtin_bit_cast(u16, (__bf16)__uint_as_float(hi)) << 16);
+                return pack2_bf16(__uint_as_float(lo), __uint_as_float(hi));
             };
             a = make_uint2(pk(xreg[j][0], xreg[j][2]) & keep, pk(xreg[j][4], xreg[j][6]) & keep);
             b = make_uint2(pk(xreg[j][1], xreg[j][3]) & keep1, pk(xreg[j][5], xreg[j][7]) & keep1);
@@ -335,8 +334,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 4 
 #pragma unroll
                     for (int g4 = 0; g4 < 4; ++g4)
                         *reinterpret_cast<unsigned *>(&lds[patch + l31 * EPROW + 8 * g4 + 4 * half]) =
-                            (unsigned)__builtin_bit_cast(u16, (__bf16)pv[2 * g4]) |
-                            ((unsigned)__builtin_bit_cast(u16, (__bf16)pv[2 * g4 + 1]) << 16);
+                            pack2_bf16(pv[2 * g4], pv[2 * g4 + 1]);
                     const uint4 o = *reinterpret_cast<const uint4 *>(&lds[patch + (lane >> 1) * EPROW + 16 * (lane & 1)]);
                     const int pos = (pt0 >> 1) + 16 * j + 8 * (lane & 1);     // ldyo % 8 == 0: 8 positions in or out
                     if (pos < ldyo) *reinterpret_cast<uint4 *>(y + ((size_t)n * Cout + ch + (lane >> 1)) * ldyo + pos) = o;

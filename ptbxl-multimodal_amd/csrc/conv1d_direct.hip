@@ -11,7 +11,7 @@
 // [K][C_in][C_out] form (ecg_conv1d_pack_weights): for a fixed (tap, ci) the C_out values a
 // workgroup needs are contiguous and wave-uniform, so they arrive through the scalar cache
 // (s_load_dwordx8/x16) and feed v_fma_f32 as SGPR operands — one LDS read of x feeds CO_T FMAs.
-#include "common.h"
+#include "bf16_util.h"
 #include "wgrad_reduce.h"
 #include <cstdlib>
 
@@ -406,10 +406,6 @@ constexpr int kPackCo = 16, kPackCi = 16, kPackKMax = 15;   // ~700 tiles of 15 
 struct PackProb { const float *w; float *w_fwd, *w_bwd; unsigned short *wb_fwd, *wb_bwd; int Co, Ci, K, block0, ci_tiles; };
 struct PackArgs { PackProb p[kMaxPack]; int count; };
 
-__device__ __forceinline__ unsigned pack_bf16_pair(float lo, float hi) {
-    return (unsigned)__builtin_bit_cast(unsigned short, (__bf16)lo) | ((unsigned)__builtin_bit_cast(unsigned short, (__bf16)hi) << 16);
-}
-
 // the bf16 operands of one staged tile (tile[co * ld + ci * K + k]), two channels per thread and store
 __device__ __forceinline__ void pack_tile_bf16(const PackProb &pr, const float *tile, int ld, int co0, int ci0, int nco,
                                                int nci, int tid) {
@@ -420,7 +416,7 @@ __device__ __forceinline__ void pack_tile_bf16(const PackProb &pr, const float *
             const int jp = e & 7, r = e >> 3, co = r % nco, k = r / nco;
             const float lo = 2 * jp < nci ? tile[co * ld + (2 * jp) * K + k] : 0.f;
             const float hi = 2 * jp + 1 < nci ? tile[co * ld + (2 * jp + 1) * K + k] : 0.f;
-            dst[((size_t)k * pr.Co + co) * 8 + jp] = pack_bf16_pair(lo, hi);
+            dst[((size_t)k * pr.Co + co) * 8 + jp] = pack2_bf16(lo, hi);
         }
     }
     if (pr.wb_bwd) {            // [co0 / 16][K-1-k][ci0 + ci][j = co]
@@ -429,7 +425,7 @@ __device__ __forceinline__ void pack_tile_bf16(const PackProb &pr, const float *
             const int jp = e & 7, r = e >> 3, ci = r % nci, k = r / nci;
             const float lo = 2 * jp < nco ? tile[(2 * jp) * ld + ci * K + (K - 1 - k)] : 0.f;
             const float hi = 2 * jp + 1 < nco ? tile[(2 * jp + 1) * ld + ci * K + (K - 1 - k)] : 0.f;
-            dst[((size_t)k * pr.Ci + ci) * 8 + jp] = pack_bf16_pair(lo, hi);
+            dst[((size_t)k * pr.Ci + ci) * 8 + jp] = pack2_bf16(lo, hi);
         }
     }
 }

@@ -49,11 +49,6 @@ __device__ __forceinline__ void wait_lgkm(int n) {
     }
 }
 
-__device__ __forceinline__ unsigned pack2_bf16(float lo, float hi) {
-    const u16 a = __builtin_bit_cast(u16, (__bf16)lo), b = __builtin_bit_cast(u16, (__bf16)hi);
-    return (unsigned)a | ((unsigned)b << 16);
-}
-
 // w [Co][Ci][K] fp32 -> wb_fwd [ceil(Ci/16)][K][Co][16] and wb_bwd [ceil(Co/16)][K][Ci][16]
 // (tap-flipped, roles of the channel axes swapped), zero-filled past the channel count.
 __global__ void pack_weights_bf16_kernel(const float *__restrict__ w, u16 *__restrict__ wb_fwd,

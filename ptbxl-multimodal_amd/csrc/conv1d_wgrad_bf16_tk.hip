@@ -45,11 +45,6 @@ constexpr int XCOPY_PAD[4] = {0, 32, 128, 160};   // the four shifted copies sta
                                                   // (channel, copy) windows of 8 banks that the 32 lanes of a half-wave
                                                   // read then overlap only between channel c and c + 2
 
-__device__ __forceinline__ unsigned pack2(float lo, float hi) {
-    const u16 a = __builtin_bit_cast(u16, (__bf16)lo), b = __builtin_bit_cast(u16, (__bf16)hi);
-    return (unsigned)a | ((unsigned)b << 16);
-}
-
 // WK > 1: the WK waves of a wave-tile group take every WK-th k-step of a stage and are summed through LDS at the end (the
 // 32-channel first layer: one 32 x 192 tile, MFMA work for two waves — the kernel is a stream of dY rows there).
 template <int M_T, int R_T, int WM, int WR, int WK, bool XF32>
@@ -182,10 +177,10 @@ __global__ __launch_bounds__(512) void conv1d_wgrad_bf16_tk_kernel(
 #pragma unroll
             for (int i = 0; i < 4; ++i) { v[i] = ok ? a[i] : 0.f; v[4 + i] = ok ? b[i] : 0.f; }
 #pragma unroll
-            for (int i = 0; i < 4; ++i) xE[j][i] = pack2(v[2 * i], v[2 * i + 1]);
+            for (int i = 0; i < 4; ++i) xE[j][i] = pack2_bf16(v[2 * i], v[2 * i + 1]);
             const bool okn = g0 + 8 >= 0 && g0 + 8 < L;
-            xN[j][0] = okn ? pack2(nx[0], nx[1]) : 0u;
-            xN[j][1] = okn ? pack2(nx[2], nx[3]) : 0u;
+            xN[j][0] = okn ? pack2_bf16(nx[0], nx[1]) : 0u;
+            xN[j][1] = okn ? pack2_bf16(nx[2], nx[3]) : 0u;
         } else {
             const u16 *xr = static_cast<const u16 *>(xin) + (size_t)xn * Cin * ldx + xrow[j];
             const int gc = min(max(g0, 0), ldx - 8);

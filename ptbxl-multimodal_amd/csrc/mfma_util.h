@@ -2,7 +2,7 @@
 // conv1d_mfma_bf16.hip, conv1d_bf16_ring.hip, conv1d_wgrad_bf16_tk.hip).  Nothing here keeps state: the per-file stamp
 // buffers stay in their translation units (the library is built without relocatable device code).
 #pragma once
-#include "common.h"
+#include "bf16_util.h"      // the bf16 pair of a packed dword: bf16_lo, bf16_hi, pack2_bf16
 
 namespace ecg {
 

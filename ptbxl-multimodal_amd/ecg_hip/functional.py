@@ -394,10 +394,8 @@ def bn_batch_stats(y, partials, P, running_mean, running_var, nbt, momentum, eps
         partials = _empty(y, C * P * 2)
         _call("ecg_bn_stat_partials", _f32(y), _f32(partials), N, C, Lo, _st())
     mean, invstd = _empty(y, C), _empty(y, C)
-    if nbt is not None and nbt.dtype != torch.int64:
-        raise L.EcgHipError("num_batches_tracked must be int64")
-    _call("ecg_bn_finalize", _f32(partials), P, N * Lo, _f32(mean), _f32(invstd),
-          _f32(running_mean), _f32(running_var), L.ptr(nbt), C, float(momentum), float(eps), _st())
+    rm, rv, cnt, mom = _running_args(running_mean, running_var, nbt, True, momentum)
+    _call("ecg_bn_finalize", _f32(partials), P, N * Lo, _f32(mean), _f32(invstd), rm, rv, cnt, C, mom, float(eps), _st())
     return mean, invstd
 
 
@@ -411,6 +409,15 @@ def _bn_momentum(momentum, nbt):
     if momentum is None:      # cumulative moving average: factor = 1/(count+1) (host read)
         return 1.0 / (int(nbt.item()) + 1) if nbt is not None else 0.0
     return float(momentum)
+
+
+def _running_args(running_mean, running_var, nbt, training, momentum):
+    """The running-statistics arguments of a batch-statistics call, as the entry points take them: (running_mean,
+    running_var, num_batches_tracked, momentum).  Outside training nothing is updated: the three pointers are NULL."""
+    rm, rv, cnt = (running_mean, running_var, nbt) if training else (None, None, None)
+    if cnt is not None and cnt.dtype != torch.int64:
+        raise L.EcgHipError("num_batches_tracked must be int64")
+    return _f32(rm), _f32(rv), L.ptr(cnt), _bn_momentum(momentum, nbt)
 
 
 # --------------------------------------------------------------------------------------
@@ -539,13 +546,10 @@ class ConvBlockFn(torch.autograd.Function):
         p = _empty(x, N, Co) if gap else _empty(x, N, Co, Lo // 2)
         if use_batch:
             # statistics combine + BN-apply + ReLU + pool in ONE launch (ecg_bn_finalize folded into the streaming pass)
-            rm, rv, cnt = (running_mean, running_var, nbt) if training else (None, None, None)
-            if cnt is not None and cnt.dtype != torch.int64:
-                raise L.EcgHipError("num_batches_tracked must be int64")
             mean, invstd = _empty(x, Co), _empty(x, Co)
-            _call("ecg_bn_stats_relu_pool_fwd", _f32(partials), P, N * Lo, _f32(rm), _f32(rv), L.ptr(cnt),
-                  _bn_momentum(momentum, nbt), float(eps), _f32(y), _f32(gamma), _f32(beta), _f32(mean), _f32(invstd),
-                  _f32(p), N, Co, Lo, 1 if gap else 0, _st())
+            _call("ecg_bn_stats_relu_pool_fwd", _f32(partials), P, N * Lo,
+                  *_running_args(running_mean, running_var, nbt, training, momentum), float(eps), _f32(y), _f32(gamma),
+                  _f32(beta), _f32(mean), _f32(invstd), _f32(p), N, Co, Lo, 1 if gap else 0, _st())
         else:
             mean, invstd = bn_eval_stats(running_mean, running_var, eps)
             # (last block: AdaptiveAvgPool1d(1) folded in, the pooled tensor never exists)
@@ -611,24 +615,20 @@ class ConvBlockFn(torch.autograd.Function):
         partials = _empty(x, Co * P * 2)
         _call("ecg_conv1d_fwd_bf16_yh", L.ptr(x), 1 if x_h else 0, ldx, L.ptr(w_fwd), _f32(b), L.ptr(y), ldyh,
               _f32(partials), N, Ci, Co, Lin, K, pad, _st())
-        rm, rv, cnt = (running_mean, running_var, nbt) if training else (None, None, None)
-        if cnt is not None and cnt.dtype != torch.int64:
-            raise L.EcgHipError("num_batches_tracked must be int64")
+        running = _running_args(running_mean, running_var, nbt, training, momentum)
         mean, invstd = _empty(x, Co), _empty(x, Co)
         ldp = 0
         if gap:
             p = _empty(x, N, Co)
-            _call("ecg_bn_stats_relu_pool_gap_fwd_yh", _f32(partials), P, N * Lo, _f32(rm), _f32(rv), L.ptr(cnt),
-                  _bn_momentum(momentum, nbt), float(eps), L.ptr(y), ldyh, _f32(gamma), _f32(beta), _f32(mean), _f32(invstd),
-                  _f32(p), N, Co, Lo, _st())
+            _call("ecg_bn_stats_relu_pool_gap_fwd_yh", _f32(partials), P, N * Lo, *running, float(eps), L.ptr(y), ldyh,
+                  _f32(gamma), _f32(beta), _f32(mean), _f32(invstd), _f32(p), N, Co, Lo, _st())
         else:
             # p as bf16 rows [N][Co][ldp], zero-filled past Lo/2: the next conv's forward reads half the bytes, and its input
             # gradient comes back as bf16 of the same shape
             ldp = (Lo // 2 + 7) & ~7
             p = torch.empty(N, Co, ldp, dtype=torch.bfloat16, device=x.device)
-            _call("ecg_bn_stats_relu_pool_fwd_h", _f32(partials), P, N * Lo, _f32(rm), _f32(rv), L.ptr(cnt),
-                  _bn_momentum(momentum, nbt), float(eps), L.ptr(y), ldyh, _f32(gamma), _f32(beta), _f32(mean),
-                  _f32(invstd), L.ptr(p), ldp, N, Co, Lo, _st())
+            _call("ecg_bn_stats_relu_pool_fwd_h", _f32(partials), P, N * Lo, *running, float(eps), L.ptr(y), ldyh,
+                  _f32(gamma), _f32(beta), _f32(mean), _f32(invstd), L.ptr(p), ldp, N, Co, Lo, _st())
             if not next_bf16:
                 # the consumer is not a mixed-precision block (a model that mixes geometries, a frozen BatchNorm downstream):
                 # hand it fp32 rows; its gradient comes back as fp32 rows (dp_kind 2 of the backward pass)

@@ -3,7 +3,9 @@
 revisions:  tools/isa_diff.py old.s new.s
 
 A kernel is the text from its `_Z...:` label to `.Lfunc_end`, without comments and empty lines, with the basic-block labels'
-function index (.LBB<n>_ -> .LBB_) and every mangled name replaced by a token.  Bodies are matched as a multiset, not by
+function index dropped and their numbers replaced by the order of first appearance (.LBB<n>_<m> -> .LBB_<k>: the same
+instructions in the same order are the same kernel, whatever numbers the compiler gave its blocks) and every mangled name
+replaced by a token.  Bodies are matched as a multiset, not by
 name (a removed template parameter changes the mangled name): per kernel `same` / `DIFF` (same name, other body) / `gone` /
 `new`, then the register and LDS / scratch sizes of each side.  Exit status 1 if anything is DIFF or new."""
 import re
@@ -19,8 +21,11 @@ def kernels(path):
         if m and name is None:
             name, body = m.group(1), []
         elif name is not None and line.startswith(".Lfunc_end"):
-            res = tuple(int(re.search(r"\.amdhsa_%s (\d+)" % k, "\n".join(body)).group(1)) for k in RES)
-            out.append((name, "\n".join(body), res))
+            text = "\n".join(body)
+            res = tuple(int(re.search(r"\.amdhsa_%s (\d+)" % k, text).group(1)) for k in RES)
+            order = {}                  # a block label's number is a name: the n-th label to appear in the text is block n
+            text = re.sub(r"\.LBB_\d+", lambda m: ".LBB_%d" % order.setdefault(m.group(0), len(order)), text)
+            out.append((name, text, res))
             name = None
         elif name is not None:
             line = re.sub(r"_Z\w+", "<sym>", re.sub(r"\.LBB\d+_", ".LBB_", line.split(";")[0])).strip()
