@@ -169,16 +169,18 @@ def _hook_pass(model, target_layer, x, x_demo, form, value, S, norm):
     if "A" not in store:
         raise ValueError("grad_cam: the target layer did not run in the model's forward")
     A = store["A"]
-    N = logits.shape[0]
+    N, n_labels = logits.shape
     if form == "pred":
         cols = logits.detach().argmax(1)[:, None]
     elif form == "tensor":
         if value.shape[0] != N:
             raise ValueError(f"class_idx has {value.shape[0]} entries for a batch of {N}")
-        cols = value.to(logits.device)[:, None]
-    else:
+        cols = value.to(logits.device)[:, None] % n_labels             # (negative indices as Python counts them;
+    else:                                                                 #  gather takes none, and faults on the device)
         ks = [value] if form == "int" else value
-        cols = torch.tensor(ks, dtype=torch.int64, device=logits.device)[None, :].expand(N, -1)
+        if any(k < -n_labels or k >= n_labels for k in ks):
+            raise IndexError(f"class_idx {ks} out of range for {n_labels} labels")
+        cols = torch.tensor([k % n_labels for k in ks], dtype=torch.int64, device=logits.device)[None, :].expand(N, -1)
     grads, raws = [], []
     for j in range(cols.shape[1]):
         score = logits.gather(1, cols[:, j:j + 1]).sum()

@@ -226,6 +226,13 @@ def test_grad_cam_on_cpu_tensors_is_the_hook_algorithm_and_leaves_no_hooks(name)
     for n in range(3):
         np.testing.assert_allclose(by_vec[n].numpy(), all_b[n, pred[n]].numpy(), atol=1e-6)
     np.testing.assert_allclose(by_int.numpy(), all_b[:, -1].numpy(), atol=1e-6)
+    # negative indices count from the end on the hook path as on the fused one; out of range raises on the host
+    assert torch.equal(grad_cam(model, x, xd, class_idx=-1, signal_length=T), by_int)
+    assert torch.equal(grad_cam(model, x, xd, class_idx=[-1, 0], signal_length=T), all_b[:, [-1, 0]])
+    assert torch.equal(grad_cam(model, x, xd, class_idx=pred - len(ks), signal_length=T), by_vec)
+    for bad in (len(ks), -len(ks) - 1):
+        with pytest.raises(IndexError):
+            grad_cam(model, x, xd, class_idx=bad)
     assert grad_cam(model, x, xd, class_idx=0).shape == (3, T // 8)
     assert grad_cam(model, x, xd, class_idx=0, normalize=None, signal_length=T).min() >= 0
     with pytest.raises(ValueError):

@@ -47,6 +47,24 @@ def paired(g, name, value):
     return sub(v), np.asarray(g[name + "__sub"], dtype=np.float64)
 
 
+def assert_grads_match_a_cpu_run(grads, ref32, ref64, tol_of, what=""):
+    """Parameter gradients against the reference model run on the CPU.  An fp32 run of the SAME network can take a ReLU /
+    max-pool decision differently from the exact (float64) forward pass when two candidates are within rounding of each
+    other; one such flip moves a dY element by one position and changes a channel's gradients by ~1/sqrt(terms) — 1e-4 ...
+    1e-2 at small batches, far above any rounding of the sums.  tools/wgrad_error.py itemises them
+    (profiles/r05_accuracy_attribution_b7_t999.txt): at B=7, T=999 exactly one decision differs from float64 — block 2,
+    (n, c, j) = (4, 34, 110), candidates 1.05e-7 apart under a live gradient of 1.8e-5 — and it is flipped by the CPU fp32
+    run and by the HIP path's UNFUSED leaves (a hooked model; round 4's table counted those and called them "HIP"), NOT by
+    the fused ConvBlock launches this test and the train step run: those take the float64 run's decisions (0 flips, gradients
+    5e-7 rel-RMS from float64 where the CPU fp32 run sits at 7e-3).  Both CPU runs are legitimate outcomes of the reference,
+    so every tensor must match AT LEAST ONE of them within the tolerance — a HIP-only flip still fails."""
+    for k, p32 in ref32.named_parameters():
+        g, g32, g64 = grads[k], p32.grad.numpy(), dict(ref64.named_parameters())[k].grad.numpy()
+        tol = tol_of(k, g32)
+        e32, e64 = np.abs(g - g32).max(), np.abs(g - g64.astype(np.float32)).max()
+        assert min(e32, e64) <= tol, f"{k} {what}: |hip - cpu fp32| = {e32:.3e}, |hip - cpu float64| = {e64:.3e}, tol {tol:.1e}"
+
+
 def dev(a):
     """Host array -> contiguous tensor on the GPU."""
     import torch
