@@ -639,6 +639,65 @@ int ecg_wfdb16_quality_tile(void);
 int ecg_wfdb16_quality(const int16_t *d, const int *rail_lo, const int *rail_hi, long long *q,
                        int R, int Ttot, int leads, int T, int first, int hop, int W, int last_start,
                        int up, int down, int Tq, ecg_stream_t stream);
+/* Beat detection on the same int16 stream, read in place, on the SOURCE axis: an integer detector in which every sample
+ * decides for itself from a bounded neighbourhood — one right answer.  Per recording r, v_l[n] the sample of lead l, a
+ * sample VALID iff it is not -32768, leads taking part: the bits of lead_mask below `leads`:
+ *     f[n] = sum over those leads of |v_l[n+s] - v_l[n-s]|  for s <= n < Ttot - s  (a lead's term is 0 when either sample
+ *            is invalid), 0 for the other n;                                              f < 2^20
+ *     g[n] = sum of f[j] over max(0, n-h) <= j <= min(Ttot-1, n+h);                        g < 2^29
+ *     M[b] = max of g over block b = n / blk (nblk = ceil(Ttot/blk) blocks, the last may be short);
+ *     med[b] = the LOWER median of M[b'] over b' in [b-2, b+2] within [0, nblk): of k values sorted ascending the one at
+ *            index (k-1)/2;          thr[b] = max(g_min[r], num*med[b] / den)  (64-bit, floor)
+ *     n is a beat iff  g[n] >= thr[n / blk],  g[n] > g[j] for every j in [max(0, n-ref), n)  and
+ *            g[n] >= g[j] for every j in (n, min(Ttot-1, n+ref)]:  strict on the left, weak on the right — the first of
+ *            equal maxima wins, and any two beats are more than ref samples apart.
+ * beats [R][cap] int32, cap = (Ttot + ref) / (ref + 1): the beats of recording r ascending, -1 from n_beats[r] on;
+ * n_beats [R] int32.  g_min [R] int64 on the device, every value >= 1 (the caller's word; it is not read on the host).
+ * Row r depends on recording r only.  No byte outside the stream is loaded.  Four launches on `stream`, no host
+ * synchronisation; the only atomics are integer maxima, whose arrival order shows in nothing.
+ * The library allocates nothing: `workspace` (16-byte aligned, ecg_wfdb16_beats_workspace_bytes(R, Ttot, blk) bytes, 0 for
+ * sizes the call would refuse) is the caller's and holds g as int32, the block maxima and the per-chunk beat lists and
+ * counts between the launches; its contents afterwards are unspecified.  ecg_wfdb16_beats_chunk: samples one workgroup
+ * decides per pass (tests put features on its multiples).
+ * ECG_EINVAL before any launch: R < 1, Ttot outside [1,2^30], leads outside [1,16], s outside [1,64], h outside [0,255],
+ * ref outside [1,1024], blk outside [16,2^20], not 1 <= num <= den <= 1024, no bit of lead_mask below `leads`, a NULL
+ * pointer, a workspace off 16 bytes — the integer limits first, so they can be asked with NULL pointers. */
+#define ECG_BEATS_CHUNK 1024
+int ecg_wfdb16_beats_chunk(void);
+size_t ecg_wfdb16_beats_workspace_bytes(int R, int Ttot, int blk);
+int ecg_wfdb16_beats(const int16_t *d, const long long *g_min, int *beats, int *n_beats, void *workspace,
+                     int R, int Ttot, int leads, int lead_mask, int s, int h, int ref, int blk, int num, int den,
+                     ecg_stream_t stream);
+/* Rhythm table of a beat list: out [R][W][ECG_RHYTHM_FIELDS] int64, one launch.  Windows are stated on the MODEL's axis
+ * (T, first, hop, W, last_start) and mapped onto the source axis by up/down and Tq exactly as for ecg_wfdb16_quality:
+ * window w covers the source samples [a_w, a_w + Tq).  With x_0 < ... < x_{k-1} the beats of recording r (the first
+ * n_beats[r] entries of beats [R][cap]) inside that span, rr_i = x_{i+1} - x_i and dr_i = rr_{i+1} - rr_i:
+ *     ECG_RH_N_BEATS      k
+ *     ECG_RH_FIRST_BEAT   x_0 as a recording sample index (-1 if k = 0)
+ *     ECG_RH_LAST_BEAT    x_{k-1} (-1 if k = 0)
+ *     ECG_RH_SUM_RR_SQ    sum of rr_i^2
+ *     ECG_RH_MIN_RR       min rr_i (2^31-1 if k < 2)
+ *     ECG_RH_MAX_RR       max rr_i (0 if k < 2)
+ *     ECG_RH_SUM_DRR_SQ   sum of dr_i^2
+ *     ECG_RH_N_DRR_OVER   count of |dr_i| > nn_delta
+ * (the sum of rr is last - first and their count max(k-1, 0): neither is stored).  Row (r, w) depends on the beats inside
+ * its span only; every sum fits int64 for Ttot <= 2^30.  Integer arithmetic, no atomics.
+ * ECG_EINVAL before any launch: up or down outside [1,512], Ttot outside [1,2^30], cap < 1, nn_delta < 0, Tq outside
+ * [1,Ttot] or not min(Ttot, ceil(T*down/up)), a window rule check_windows refuses on the model axis, a NULL pointer. */
+enum {
+    ECG_RH_N_BEATS = 0,
+    ECG_RH_FIRST_BEAT = 1,
+    ECG_RH_LAST_BEAT = 2,
+    ECG_RH_SUM_RR_SQ = 3,
+    ECG_RH_MIN_RR = 4,
+    ECG_RH_MAX_RR = 5,
+    ECG_RH_SUM_DRR_SQ = 6,
+    ECG_RH_N_DRR_OVER = 7,
+    ECG_RHYTHM_FIELDS = 8
+};
+int ecg_beats_rhythm(const int *beats, const int *n_beats, long long *out, int R, int Ttot, int cap,
+                     int T, int first, int hop, int W, int last_start, int up, int down, int Tq, int nn_delta,
+                     ecg_stream_t stream);
 /* Per-window time series back onto the recording's axis: v [R][W][K][T] (K series per window, windows placed by the
  * rule above) -> out [R][K][Ttot], the mean over the windows that cover a sample:
  *     acc = 0.0f;  for w ascending with start(w) <= t < start(w)+T:  acc = acc + v[r][w][k][t - start(w)]

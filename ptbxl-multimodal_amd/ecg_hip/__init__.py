@@ -12,6 +12,7 @@ A recording at another sampling rate than the model's is resampled on the device
 A raw recording is conditioned there too: a zero-phase baseline-wander high-pass and mains notch (`ecg_hip.filter`, filter=).
 WFDB records in formats 16, 61, 80, 160 and 212, with skews, offsets and several files, are decoded on the device (`ecg_hip.wfdbraw`).
 Windows spoiled by flat lines, rails or artefacts are kept out of the record-level numbers (`ecg_hip.quality`, quality=).
+Beat positions and per-window RR statistics come from an integer QRS detector on the device (`ecg_hip.beats`, beats=).
 """
 from ._lib import EcgHipError, LIB_PATH, load  # noqa: F401
 

@@ -106,6 +106,10 @@ SIGNATURES = {
     "ecg_wfdb_decode16": (_i, [_vp, _ll, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _vp]),
     "ecg_wfdb16_quality_tile": (_i, []),
     "ecg_wfdb16_quality": (_i, [_vp] * 4 + [_i] * 11 + [_vp]),
+    "ecg_wfdb16_beats_chunk": (_i, []),
+    "ecg_wfdb16_beats_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ecg_wfdb16_beats": (_i, [_vp] * 5 + [_i] * 10 + [_vp]),
+    "ecg_beats_rhythm": (_i, [_vp] * 3 + [_i] * 12 + [_vp]),
     "ecg_windows_overlap_mean": (_i, [_vp] * 3 + [_i] * 8 + [_vp]),
     "ecg_host_gather_rows": (_i, [_vp, _sz, _vp, _i, _vp]),
 }

@@ -864,6 +864,6 @@ def sigmoid(x):
 
 
 from .leaves import BatchNormFn, Conv1dFn, FilmFn, GapFn, LinearFn, MaxPool2Fn, ReLUFn  # noqa: E402,F401
-from .input_step import (_fir_call, _resampled_call, fir_filter, fir_windows, overlap_mean,  # noqa: E402,F401
-                         wfdb16_quality, wfdb16_to_windows, wfdb16_to_windows_sliding, wfdb16_windows,
+from .input_step import (_fir_call, _resampled_call, beats_rhythm, fir_filter, fir_windows, overlap_mean,  # noqa: E402,F401
+                         wfdb16_beats, wfdb16_quality, wfdb16_to_windows, wfdb16_to_windows_sliding, wfdb16_windows,
                          wfdb16_windows_resampled, wfdb_decode16, zscore_per_lead)

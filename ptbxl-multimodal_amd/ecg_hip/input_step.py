@@ -216,6 +216,49 @@ def wfdb16_quality(d, window, first, hop, W, last_start=-1, up=1, down=1, rails=
     return q
 
 
+def wfdb16_beats(d, s, h, ref, blk, num, den, g_min, lead_mask=None):
+    """The beats of d int16 [R, Ttot, leads], read in place by ecg_wfdb16_beats (four launches, no host synchronisation):
+    -> (beats int32 [R, cap], n_beats int32 [R]), cap = (Ttot + ref) // (ref + 1); row r holds the beat samples of
+    recording r ascending, -1 from n_beats[r] on.  s, h, ref, blk, num, den: the integers of the detector
+    (include/ecg_hip.h; beats.BeatSpec.params derives them from physical units); g_min: int64 [R] (or one value), every
+    entry >= 1; lead_mask: bit l = lead l takes part (None: every lead).  Allocates the outputs and the workspace."""
+    d, _, _ = _raw_stream("wfdb16_beats", d)
+    R, Ttot, leads = d.shape
+    ref = int(ref)
+    g_min = _contig(torch.as_tensor(g_min, dtype=torch.int64).to(d.device).reshape(-1).expand(R))
+    mask = (1 << leads) - 1 if lead_mask is None else int(lead_mask)
+    cap = (Ttot + ref) // (ref + 1) if ref >= 0 else 0
+    beats = torch.empty(R, max(cap, 0), dtype=torch.int32, device=d.device)
+    n_beats = torch.empty(R, dtype=torch.int32, device=d.device)
+    nbytes = int(L.query("ecg_wfdb16_beats_workspace_bytes", R, Ttot, int(blk)))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=d.device)
+    _call("ecg_wfdb16_beats", L.ptr(d), L.ptr(g_min), L.ptr(beats), L.ptr(n_beats), L.ptr(ws), R, Ttot, leads, mask, int(s),
+          int(h), ref, int(blk), int(num), int(den), _st())
+    return beats, n_beats
+
+
+def beats_rhythm(beats, n_beats, Ttot, window, first, hop, W, last_start=-1, up=1, down=1, nn_delta=0):
+    """The rhythm table of a beat list (wfdb16_beats) by ONE launch of ecg_beats_rhythm: -> int64 [R, W, 8], the fields of
+    ecg_hip.beats.FIELDS (exact integers).  Ttot: samples of the recordings the beats index (the source axis); window,
+    first, hop, W, last_start state the windows on the MODEL's axis and up/down maps them onto the source samples
+    [a_w, a_w + Tq) exactly as for wfdb16_quality; nn_delta: the |difference of successive RR| bound of n_drr_over, in
+    source samples."""
+    from .quality import source_span
+    for name, t in (("beats", beats), ("n_beats", n_beats)):
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise L.EcgHipError(f"beats_rhythm: a CPU tensor reached the HIP input step; {name} must be on the GPU")
+        if t.dtype != torch.int32:
+            raise L.EcgHipError(f"beats_rhythm: {name} must be int32, got {t.dtype}")
+    if beats.dim() != 2 or tuple(n_beats.shape) != (beats.shape[0],):
+        raise L.EcgHipError("beats_rhythm: beats must be [R, cap] and n_beats [R]")
+    R, cap = beats.shape
+    out = torch.empty(R, max(int(W), 0), 8, dtype=torch.int64, device=beats.device)
+    _call("ecg_beats_rhythm", L.ptr(_contig(beats)), L.ptr(_contig(n_beats)), L.ptr(out), R, int(Ttot), cap, int(window),
+          int(first), int(hop), int(W), int(last_start), int(up), int(down), source_span(window, Ttot, up, down),
+          int(nn_delta), _st())
+    return out
+
+
 def overlap_mean(v, plan, Ttot, return_cover=False):
     """Per-window time series v fp32 [R, W, K, T] (windows placed by `plan`, a window_plan result) -> [R, K, Ttot]: at
     every sample the mean of the windows that cover it, added in ascending window order by the one lane that owns the

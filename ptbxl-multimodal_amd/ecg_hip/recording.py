@@ -21,6 +21,9 @@ as fp32 and `ecg_fir_windows` (ecg_hip/filter.py) cuts the windows out of its ze
 A finite window is not a trustworthy one: a flat line, an amplifier on its rail or a motion artefact z-scores into a
 confident number.  `quality=` (ecg_hip/quality.py) takes ten exact integer indices per (recording, window, lead) from the
 raw int16 stream in one launch of `ecg_wfdb16_quality` and keeps the windows it judges unusable out of prob_max / prob_mean.
+
+A probability says nothing about where the beats are.  `beats=` (ecg_hip/beats.py) runs an integer QRS detector over the
+raw stream (`ecg_wfdb16_beats`) and `ecg_beats_rhythm` gives every window its beat count and RR statistics, on the device.
 """
 import torch
 
@@ -69,9 +72,11 @@ class RecordingScore:
     fs: the sampling rate of the axis starts / cam / cover are on (the model's rate where the recording was resampled,
     Ttot then being the resampled length; None when no rate was given); source_len: samples of the recording itself.
     With quality=: quality int64 [R, W, leads, 10] (quality.FIELDS, on the source axis), lead_ok [R, W, leads] and
-    usable [R, W]; prob_max / prob_mean are then over the windows that are finite AND usable.  None otherwise."""
+    usable [R, W]; prob_max / prob_mean are then over the windows that are finite AND usable.  None otherwise.
+    With beats=: beats int32 [R, cap] (beat samples on the SOURCE axis, ascending, -1 from n_beats[r] on), n_beats int32
+    [R], rhythm int64 [R, W, 8] (beats.FIELDS) and heart_rate float64 [R, W] in bpm (NaN under 2 beats).  None otherwise."""
     __slots__ = ("starts", "logits", "prob", "finite", "prob_max", "prob_mean", "cam", "cover", "fs", "source_len",
-                 "quality", "lead_ok", "usable")
+                 "quality", "lead_ok", "usable", "beats", "n_beats", "rhythm", "heart_rate")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -131,6 +136,25 @@ def _quality_gate(quality, d, gain, rails, window, plan, ratio, fs, source_len):
     return (qtab, *spec.judge(qtab, gain, fs, source_span(window, source_len, up, down)))
 
 
+def _beat_stage(beats, d, gain, window, plan, ratio, fs, source_len):
+    """-> (beats, n_beats, rhythm, heart_rate) from ONE wfdb16_beats call on the raw stream at the source rate fs and ONE
+    beats_rhythm launch on the call's plan and ratio; four Nones and no launch without beats=."""
+    if beats is None or beats is False:
+        return None, None, None, None
+    from .beats import BeatSpec, heart_rate
+    spec = BeatSpec() if beats is True else beats
+    if not isinstance(spec, BeatSpec):
+        raise ValueError(f"beats={beats!r}: a BeatSpec, True or None")
+    if fs is None:
+        raise ValueError("beats=: the detector's parameters are in seconds and need the sampling rate fs of the source stream")
+    p = spec.params(fs, gain)
+    up, down = ratio or (1, 1)
+    first, hop, W, last_start, _ = plan
+    b, n = hipF.wfdb16_beats(d, p["s"], p["h"], p["ref"], p["blk"], p["num"], p["den"], p["g_min"], p["lead_mask"])
+    rhythm = hipF.beats_rhythm(b, n, source_len, window, first, hop, W, last_start, up, down, p["nn_delta"])
+    return b, n, rhythm, heart_rate(rhythm, fs)        # summarize(rhythm, fs)["heart_rate"]
+
+
 def _normalize_per_record(cam, cover):
     """cam_normalize="record": min-max of every (recording, class) row of cam [R, K, Ttot] over its covered samples
     (cover > 0), divided only where the maximum is > 0; 0 where nothing covers."""
@@ -143,7 +167,8 @@ def _normalize_per_record(cam, cover):
 
 
 def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift", batch_size=256, x_demo=None,
-                    cam_classes=None, cam_normalize=None, fs=None, model_fs=None, filter=None, quality=None, rails=None):
+                    cam_classes=None, cam_normalize=None, fs=None, model_fs=None, filter=None, quality=None, rails=None,
+                    beats=None):
     """Score recordings d int16 [Ttot, leads] or [R, Ttot, leads] (on the GPU, the .dat layout) with `model` in eval mode.
 
     gain float64 / baseline int32 [leads] or [R, leads]; window: samples per model input; hop: default window // 2;
@@ -184,6 +209,13 @@ def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift",
     usable, and prob_max / prob_mean are taken over finite & usable (NaN where a recording has no such window).  logits,
     prob, finite and the CAMs are untouched: unusable windows are still scored and still stitched.
     None (default): no launch is added and every output keeps today's bits.
+
+    beats: an ecg_hip.beats.BeatSpec, or True for BeatSpec() (its defaults are policy, not measurements).  ONE
+    functional.wfdb16_beats call for the whole call detects the beats of every recording on the RAW int16 stream at the
+    SOURCE rate fs (ValueError when fs is None) — before resampling and before filter= — and ONE functional.beats_rhythm
+    launch takes the table of every window of the plan, mapped onto the source samples by up/down as for quality=.  The
+    score gains beats, n_beats (source-axis sample indices; they are not mapped onto the model-rate axis), rhythm and
+    heart_rate (beats.summarize).  Every other output is untouched.  None (default): nothing is launched.
     -> RecordingScore."""
     if not (torch.is_tensor(d) and d.is_cuda):
         raise L.EcgHipError("score_recording: a CPU tensor reached the HIP input step; d must be on the GPU "
@@ -223,6 +255,7 @@ def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift",
     cams = None if cam_classes is None else [int(k) for k in cam_classes]
     d = hipF._contig(d)
     qtab, lead_ok, usable = _quality_gate(quality, d, gain, rails, window, plan, ratio, fs, source_len)
+    beat_list, n_beats, rhythm, heart_rate = _beat_stage(beats, d, gain, window, plan, ratio, fs, source_len)
     windows_of = _chunk_windows(d, gain, baseline, window, hop, Ttot, ratio, taps)
 
     logits = v = None
@@ -256,7 +289,8 @@ def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift",
             cam = _normalize_per_record(cam, cover)
     return RecordingScore(starts=starts, logits=logits, prob=prob, finite=finite, prob_max=pmax, prob_mean=pmean,
                           cam=cam, cover=cover, fs=fs if ratio is None else model_fs, source_len=source_len,
-                          quality=qtab, lead_ok=lead_ok, usable=usable)
+                          quality=qtab, lead_ok=lead_ok, usable=usable, beats=beat_list, n_beats=n_beats, rhythm=rhythm,
+                          heart_rate=heart_rate)
 
 
 def score_wfdb_record(record_path, model, model_fs=None, leads=None, **kw):
@@ -265,7 +299,8 @@ def score_wfdb_record(record_path, model, model_fs=None, leads=None, **kw):
     None (default): the record is scored at its own rate, whatever the header says.  filter= (score_recording) is passed
     through: a FilterSpec is designed at model_fs when the record is resampled, otherwise at the header's rate.
     quality= is passed through too, with the ADC rails of the selected leads (quality.rails_from_header: adc_res and
-    adc_zero of the header, or the storage format's range) unless the caller gives rails= itself.
+    adc_zero of the header, or the storage format's range) unless the caller gives rails= itself.  beats= is passed
+    through as well and detects at the header's rate.
 
     leads: the signals to score, in the model's lead order — names matched against the header's descriptions (e.g.
     wfdbraw.PTBXL_LEADS for a 15-signal PTB Diagnostic record) or signal indices; None: every signal, in header order.

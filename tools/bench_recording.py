@@ -2,7 +2,7 @@
 score_recording end to end.
 
     python tools/bench_recording.py [--hours 1] [--rounds 7] [--iters 20] [--out profiles/recording_bench.json]
-                                    [--legs recording,resample,filter,decode,quality]
+                                    [--legs recording,resample,filter,decode,quality,beats]
                                     [--resample-out profiles/resample_bench.json]
 
 Workloads: one 12-lead recording of --hours at 500 Hz (window 5000) and at 100 Hz (window 1000), hop = window / 2.
@@ -51,6 +51,14 @@ Leg "quality" (not in the default --legs): the signal-quality stage, ecg_wfdb16_
                cummax of the positions where the value changes (checked equal to the kernel's table)
   (m) score    score_recording with quality=True against the same call without it (fp32, no CAMs): what the gate adds
 alternating in one process like the others.  Written into --out under "quality".
+
+Leg "beats" (not in the default --legs): beat detection and the rhythm table on the one-hour 12-lead recording at 100 Hz
+(window 1000, hop 500) and at 500 Hz (window 5000, hop 2500): R-like pulses every 0.7-0.9 s in noise, BeatSpec() defaults.
+  (n) kernel   functional.wfdb16_beats + functional.beats_rhythm (five launches); "detect" is wfdb16_beats alone
+  (o) torch    the same detector in torch tensor ops on the device: cumsum for g, max_pool1d for the windowed maxima,
+               nonzero for the list (checked equal to the kernel's list; no table)
+  (p) score    score_recording with beats=True against the same call without it (fp32, no CAMs): what the stage adds
+alternating in one process like the others.  Written into --out under "beats".
 Fails when no GPU is visible: no number here means anything on a CPU.
 """
 import argparse
@@ -447,12 +455,107 @@ def quality_leg(a):
     return res
 
 
-_SECTIONS = ("filter", "decode", "quality")
+def beats_torch(d, s, h, ref, blk, num, den, g_min):
+    """The beat list of ecg_wfdb16_beats for one recording d int16 [Ttot, leads] in torch tensor ops on d's device: cumsum
+    for g, a sort of five shifted copies for the block medians, max_pool1d (float64: g < 2^29 is exact) for the windowed
+    maxima, nonzero for the list."""
+    Ttot, i64 = d.shape[0], torch.int64
+    v, valid = d.to(torch.int32), d != -32768
+    f = torch.zeros(Ttot, dtype=i64, device=d.device)
+    if Ttot > 2 * s:
+        both = valid[2 * s:] & valid[:Ttot - 2 * s]
+        f[s:Ttot - s] = torch.where(both, (v[2 * s:] - v[:Ttot - 2 * s]).abs(), torch.zeros_like(v[2 * s:])).sum(1, dtype=i64)
+    c = torch.cat([f.new_zeros(1), f.cumsum(0)])
+    n = torch.arange(Ttot, device=d.device)
+    g = c[(n + h).clamp(max=Ttot - 1) + 1] - c[(n - h).clamp(min=0)]
+    nblk = -(-Ttot // blk)
+    M = torch.cat([g, g.new_zeros(nblk * blk - Ttot)]).view(nblk, blk).amax(1)
+    big = torch.iinfo(i64).max
+    five = torch.cat([M.new_full((2,), big), M, M.new_full((2,), big)]).unfold(0, 5, 1).sort(-1).values
+    k = (five != big).sum(-1)                                           # the neighbours inside [0, nblk)
+    med = five.gather(1, ((k - 1) // 2)[:, None])[:, 0]
+    thr = torch.clamp((num * med) // den, min=int(g_min))
+    edge = g.new_full((ref,), -1)
+    wmax = torch.nn.functional.max_pool1d(torch.cat([edge, g, edge]).double()[None, None], ref, 1)[0, 0]
+    left, right, gd = wmax[:Ttot], wmax[ref + 1:ref + 1 + Ttot], g.double()
+    return torch.nonzero((g >= thr[n // blk]) & (gd > left) & (gd >= right))[:, 0]
+
+
+def beats_leg(a):
+    """ecg_wfdb16_beats + ecg_beats_rhythm against the same detector in torch ops, and what beats= adds to score_recording."""
+    from ecg_hip import functional as F
+    from ecg_hip.beats import BeatSpec
+    from ecg_hip.recording import score_recording, window_plan
+    from src.models.ecg_cnn import ECGCNN
+    from src.utils.seed import set_seed
+    res = []
+    for fs, window in ((100, 1000), (500, 5000)):
+        Ttot, hop = int(a.hours * 3600 * fs), window // 2
+        rng = np.random.default_rng(fs + 3)
+        # R-like pulses (sigma 12 ms, 0.3-1.5 mV, a sign per lead) every 0.7-0.9 s in 0.02 mV of noise, 1000 counts per mV
+        at = np.cumsum(rng.uniform(0.7, 0.9, size=int(a.hours * 3600 / 0.7)) * fs).astype(np.int64)
+        train = np.zeros(Ttot)
+        train[at[at < Ttot - fs]] = 1.0
+        k = np.arange(-int(0.06 * fs), int(0.06 * fs) + 1)
+        shape = np.convolve(train, np.exp(-0.5 * (k / (0.012 * fs)) ** 2), mode="same")
+        amp = rng.choice([-1.0, 1.0], size=LEADS) * rng.uniform(300, 1500, size=LEADS)
+        x = shape[:, None] * amp[None, :] + 20.0 * rng.standard_normal((Ttot, LEADS))
+        d = torch.from_numpy(np.round(x).astype(np.int16)[None]).cuda()
+        gain = torch.full((1, LEADS), 1000.0, dtype=torch.float64).cuda()
+        base = torch.zeros(1, LEADS, dtype=torch.int32).cuda()
+        p = BeatSpec().params(fs, gain)
+        g_min = p["g_min"].cuda()
+        first, hop, W, last, _ = window_plan(Ttot, window, hop)
+        set_seed(42)
+        model = ECGCNN(num_labels=5).cuda().eval()
+
+        def detect():
+            return F.wfdb16_beats(d, p["s"], p["h"], p["ref"], p["blk"], p["num"], p["den"], g_min)
+
+        def kernel():
+            b, n = detect()
+            return F.beats_rhythm(b, n, Ttot, window, first, hop, W, last, 1, 1, p["nn_delta"])
+
+        def stock():
+            return beats_torch(d[0], p["s"], p["h"], p["ref"], p["blk"], p["num"], p["den"], int(g_min[0]))
+
+        def score(b):
+            return score_recording(model, d, gain, base, window=window, hop=hop, batch_size=a.batch, fs=fs, beats=b).prob_max
+
+        b, n = detect()
+        want = stock()
+        assert int(n[0]) == want.numel() and torch.equal(b[0, :int(n[0])].long(), want)
+        print(f"beats leg: {fs} Hz, Ttot {Ttot}, {int(n[0])} beats, {W} windows", file=sys.stderr, flush=True)
+        big = argparse.Namespace(**{**vars(a), "iters": max(a.iters, 500)})
+        ms, iters = _rounds({"kernel": kernel, "detect": detect, "torch": stock}, big)
+        ms2, iters2 = _rounds({"with_beats": lambda: score(True), "without": lambda: score(None)}, a)
+        ms.update(ms2), iters.update(iters2)
+        med = {k: float(np.median(v)) for k, v in ms.items()}
+        must = Ttot * LEADS * 2
+        line = {"metric": "wfdb16_beats_rhythm_ms", "value": round(med["kernel"], 4), "unit": "ms",
+                "config": {"workload": f"{a.hours:g} h, {LEADS} leads at {fs} Hz (Ttot {Ttot}), BeatSpec() defaults "
+                                       f"(s {p['s']}, h {p['h']}, ref {p['ref']}, blk {p['blk']}), {int(n[0])} beats; table over "
+                                       f"{W} windows of {window}, hop {hop}; kernel: wfdb16_beats + beats_rhythm, detect: "
+                                       f"wfdb16_beats alone, torch: the list in tensor ops (no table); score_recording: ECGCNN(5), "
+                                       f"chunks of {a.batch}, fp32, no CAMs"},
+                **{f"{k}_ms": [round(t, 4) for t in v] for k, v in ms.items()},
+                **{f"{k}_median_ms": round(m, 4) for k, m in med.items()},
+                **{f"{k}_spread_ms": round(max(v) - min(v), 4) for k, v in ms.items()},
+                "calls_per_round": iters, "torch_over_kernel": round(med["torch"] / med["kernel"], 3),
+                "stream_bytes": int(must), "detect_GBps_of_the_stream": round(must / (med["detect"] * 1e-3) / 1e9, 1),
+                "with_over_without": round(med["with_beats"] / med["without"], 4),
+                "added_ms": round(med["with_beats"] - med["without"], 4)}
+        print(json.dumps(line), flush=True)
+        res.append(line)
+    return res
+
+
+_SECTIONS = ("filter", "decode", "quality", "beats")
 
 
 def _write(path, lines=None, **sections):
-    """profiles/recording_bench.json: the recording leg's lines, then {"filter": [...]}, {"decode": [...]} and
-    {"quality": [...]}; a leg replaces its own part."""
+    """profiles/recording_bench.json: the recording leg's lines, then {"filter": [...]}, {"decode": [...]},
+    {"quality": [...]} and {"beats": [...]}; a leg replaces its own part."""
     old = []
     if os.path.exists(path):
         with open(path) as f:
@@ -493,6 +596,8 @@ def main():
         _write(a.out, decode=decode_leg(a))
     if "quality" in a.legs.split(","):
         _write(a.out, quality=quality_leg(a))
+    if "beats" in a.legs.split(","):
+        _write(a.out, beats=beats_leg(a))
     if "recording" not in a.legs.split(","):
         return
     res = []
