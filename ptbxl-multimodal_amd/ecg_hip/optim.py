@@ -43,6 +43,11 @@ def flatten_tensors_(tensors):
 
 
 class FlatAdamW(torch.optim.Optimizer):
+    """One launch over the whole flat buffer, so every parameter takes part in every step: a parameter whose `.grad` is None
+    is stepped with a ZERO gradient — it decays by lr * weight_decay and its momentum moves on — where stock AdamW skips it
+    entirely (`AdoptedAdamW` falls back to torch's own step for such a step).  The kernels take lr, betas, eps and
+    weight_decay as float32, read from `param_groups[0]` at every step.  Pinned in tests/test_gpu_step_end.py."""
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
                  process_group=None, world_size=None, overlap=True, early_params=8, exchange_single_rank=False):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
