@@ -525,7 +525,263 @@ bool mfma_fwd_eval_gap_supported(int Cin, int Cout, int L, int K, int pad) {
 // grid = (ceil(R/R_T), Cout/M_T, S), R = Cin*K.  4 waves laid out WM x WR x WK: WK > 1 splits the
 // staged t range between waves (their accumulators are summed through LDS at the end).
 // slab[s][co][r] (+ bias slab [s][co] behind the S weight slabs), summed by wgrad_reduce_kernel.
-//
+// Three slab kernels: register-staged (dense or unaligned dY rows), LDS-DMA with 15 taps, LDS-DMA in the fast-FIR form.
+
+// ---------------------------------------------------------------------------------------
+// weight gradient: shared tile code
+// ---------------------------------------------------------------------------------------
+// What the three kernels have in common stands here once.  What is NOT here differs on purpose: the stage loops, the
+// register-staged kernel's dY staging and the fast-FIR kernel's x loads (each says why where it stands).
+
+// Workgroup -> (column tile, C_out tile, split); wave -> its corner of the tile; lane -> half and column.
+template <int M_T, int R_T, int WM, int WR, int WK>
+struct WgTile {
+    int tid, lane, wave, half, l31;
+    int tile_r, co0, s;             // column tile (of RT), first output channel, split (= slab)
+    int wk, wr, wm, wm0, wr0;       // wave coordinates; the wave's first channel / column inside the tile
+    bool want_bias;                 // this wave also sums the bias gradient of its channels
+    __device__ __forceinline__ WgTile(int RT, int Cout) {
+        tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+        half = lane >> 5, l31 = lane & 31;
+        // logical order: the R tiles of one (C_out tile, split) are adjacent — they read the same dY slice
+        const int CT = Cout / M_T;
+        const int tile = xcd_chunked(blockIdx.x, gridDim.x);
+        const int tile_cs = tile / RT;
+        tile_r = tile % RT;
+        co0 = (tile_cs % CT) * M_T, s = tile_cs / CT;
+        wk = wave % WK, wr = (wave / WK) % WR, wm = wave / (WK * WR);
+        wm0 = wm * (M_T / WM), wr0 = wr * (R_T / WR);
+        want_bias = (tile_r == 0) && (wr == 0);
+    }
+};
+
+// The accumulators of one wave, two levels (TWO-LEVEL ACCUMULATION: conv1d_mfma_wgrad_dma_kernel), and the bias gradient
+// that rides on the A fragments.
+template <int MC, int MR>
+struct WgAcc {
+    f32x16 acc[MC][MR], acc2[MC][MR];      // acc2: the second level
+    f32x16 zero16;                         // what the first MFMA of a stage starts from
+    float bsum[MC], bsum2[MC];
+    __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
+#pragma unroll
+        for (int a = 0; a < MC; ++a)
+#pragma unroll
+            for (int b = 0; b < MR; ++b) { acc[a][b] = zero16; acc2[a][b] = zero16; }
+#pragma unroll
+        for (int a = 0; a < MC; ++a) bsum[a] = bsum2[a] = 0.f;
+    }
+    // second level: the stage's sums join the running totals, in issue order of the MFMAs
+    __device__ __forceinline__ void fold() {
+#pragma unroll
+        for (int i = 0; i < MC; ++i)
+#pragma unroll
+            for (int j = 0; j < MR; ++j) acc2[i][j] += acc[i][j];
+    }
+    __device__ __forceinline__ void fold_bias() {
+#pragma unroll
+        for (int i = 0; i < MC; ++i) bsum2[i] += bsum[i];
+    }
+    // after the last stage: the totals back into acc / bsum, the two lane halves of the bias sum added (half 0 + half 1)
+    __device__ __forceinline__ void finish(bool want_bias) {
+#pragma unroll
+        for (int i = 0; i < MC; ++i) {
+            bsum[i] = bsum2[i];
+#pragma unroll
+            for (int j = 0; j < MR; ++j) acc[i][j] = acc2[i][j];
+        }
+        if (want_bias) {
+#pragma unroll
+            for (int i = 0; i < MC; ++i) bsum[i] += __shfl_xor(bsum[i], 32, 64);
+        }
+    }
+};
+
+// Which tensor element x-tile element e = tid + 256 j is: row offset (clamped into the tensor) and position minus the
+// padding, loop-invariant per thread.
+template <int XEL, int XS, int XLOADS>
+__device__ __forceinline__ void wg_x_index(int (&xci)[XLOADS], int (&xpos)[XLOADS], int tid, int ci_base, int Cin, int L,
+                                           int pad) {
+#pragma unroll
+    for (int j = 0; j < XLOADS; ++j) {
+        const int e = min(tid + 256 * j, XEL - 1);
+        xci[j] = min(ci_base + e / XS, Cin - 1) * L;
+        xpos[j] = e % XS - pad;
+    }
+}
+
+// The x tile (B operand) on its way through registers: XLOADS elements per thread, their zero padding as one bit each.
+template <int XEL>
+struct WgXRegs {
+    static constexpr int XLOADS = (XEL + 255) / 256;
+    static_assert(XLOADS <= 32, "mask bits");
+    float xreg[XLOADS];
+    unsigned xmask = 0, cxmask = 0;     // of the tile being loaded / being committed (it must survive the following loads)
+    // element j from sample position sidx of the row at xn + rowoff.  The load is UNCONDITIONAL (clamped address, zeroed
+    // by the mask at the commit): a load that is only used under a condition gets sunk into a branch, behind vmcnt(0).
+    __device__ __forceinline__ void load(int j, const float *xn, int rowoff, int sidx, int L) {
+        xreg[j] = xn[rowoff + min(max(sidx, 0), L - 1)];
+        const unsigned bit = ((sidx >= 0) && (sidx < L)) ? (1u << j) : 0u;
+        xmask = (j == 0) ? bit : (xmask | bit);
+    }
+    __device__ __forceinline__ void latch() { cxmask = xmask; }
+    // masked write of element j into the x tile that starts at xt
+    __device__ __forceinline__ void commit(int j, float *xt, int tid) const {
+        const int e = tid + 256 * j;
+        const unsigned keep = 0u - ((cxmask >> j) & 1u);
+        if (256 * (j + 1) <= XEL || e < XEL) xt[e] = __uint_as_float(__float_as_uint(xreg[j]) & keep);
+    }
+};
+
+// dY tiles by LDS-DMA (the DMA kernel; the fast-FIR kernel keeps a copy, it says why): the per-thread piece offsets and the stage cursor.  A workgroup's
+// stages are it_begin .. it_end of the N * ntt (n, t tile) pairs; the cursor advances incrementally (uniform, no division
+// in the loop) and is CLAMPED where it is used: the last stages restage a valid tile nobody reads.
+template <int M_T, int T_T>
+struct WgDyDma {
+    static_assert(T_T == 64 || T_T == 128, "64 or 128 time steps per stage");
+    static constexpr int LPR = T_T / 4, RPP = 64 / LPR;     // 16-byte chunks (lanes) per dY row; rows per 1 KB DMA piece
+    static constexpr int AEL = M_T * T_T;                   // floats of the dY image
+    static constexpr int NDMA = AEL / 256;                  // 1 KB pieces (4 rows each)
+    static constexpr int DPW = NDMA / 4;                    // pieces per wave per stage
+    static_assert(NDMA % 4 == 0, "dY image must split evenly over the four waves");
+    const float *dy;
+    float *lds;
+    int N, Cout, co0, ldy, ntt, total;
+    int doff[DPW];          // dY piece j of this wave: element offset from the stage base
+    int sn, stt;            // stage whose x tile is loaded next
+    int dn, dtt;            // stage whose dY tile is DMA'd next
+    unsigned lds_base;
+    int wave_u;
+    template <class Tile>
+    __device__ __forceinline__ WgDyDma(const float *dy_, float *lds_, int N_, int Cout_, int Lo, int ldy_, int S, const Tile &g)
+        : dy(dy_), lds(lds_), N(N_), Cout(Cout_), co0(g.co0), ldy(ldy_) {
+        ntt = (Lo + T_T - 1) / T_T;
+        // the split runs over stages (n, t tile), not whole samples: finer balance, and enough workgroups for
+        // layers with a single output tile
+        const int it_begin = (int)((long long)N * ntt * g.s / S), it_end = (int)((long long)N * ntt * (g.s + 1) / S);
+        total = it_end - it_begin;
+#pragma unroll
+        for (int j = 0; j < DPW; ++j) {
+            const int row = (j * 4 + g.wave) * RPP + g.lane / LPR;          // row inside the M_T tile
+            doff[j] = row * ldy + (((g.lane % LPR) ^ (row & 15)) << 2);     // LDS chunk c <- global chunk c^(row&15)
+        }
+        sn = it_begin / ntt, stt = it_begin - sn * ntt;
+        dn = sn, dtt = stt;
+        lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) float *)lds;
+        wave_u = __builtin_amdgcn_readfirstlane(g.wave);
+    }
+    __device__ __forceinline__ void advance() { if (++stt == ntt) { stt = 0; ++sn; } }
+    __device__ __forceinline__ void follow() { dn = sn; dtt = stt; }        // the dY cursor catches up with the x cursor
+    // one 1 KB piece of stage (dn, dtt)'s dY tile into the image at img (asm LDS-DMA: glds16)
+    __device__ __forceinline__ void issue(int j, float *img) const {
+        const float *base = dy + ((size_t)min(dn, N - 1) * Cout + co0) * ldy + dtt * T_T;        // uniform
+        glds16(base, (unsigned)doff[j] * 4u,
+               (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_base + (unsigned)((img - lds) + (j * 4 + wave_u) * 256) * 4u)));
+    }
+};
+
+// Prologue of the DMA kernel: stage 0 -> image 0, x tile of stage 1 -> registers; the cursor ends on stage 2.
+// load_x(j) is the calling kernel's x load.
+template <class Dy, class XRegs, class LoadX>
+__device__ __forceinline__ void wg_dma_prologue(Dy &d, XRegs &X, int tid, LoadX load_x) {
+    if (d.total > 0) {
+#pragma unroll
+        for (int j = 0; j < Dy::DPW; ++j) d.issue(j, d.lds);
+#pragma unroll
+        for (int j = 0; j < XRegs::XLOADS; ++j) load_x(j);
+        X.latch();
+#pragma unroll
+        for (int j = 0; j < XRegs::XLOADS; ++j) X.commit(j, d.lds + Dy::AEL, tid);
+        d.advance();
+        d.follow();                                     // stage 1
+#pragma unroll
+        for (int j = 0; j < XRegs::XLOADS; ++j) load_x(j);
+        d.advance();                                    // stage 2
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (the asm DMA pieces are not in hipcc's books)
+    __syncthreads();
+}
+
+// WK > 1: sum the WK waves that share an output tile through LDS, in wave order (the images are dead: LDSF floats).
+// Afterwards the waves with wk == 0 hold the sums.
+template <int WM, int WR, int WK, int LDSF, int MC, int MR, class Tile>
+__device__ __forceinline__ void wg_wk_exchange(WgAcc<MC, MR> &A, float *lds, const Tile &g) {
+    constexpr int ACCF = MC * MR * 16 * 64;             // floats of one wave's accumulators
+    static_assert(WM * WR * ACCF + 4 * 32 <= LDSF, "accumulator exchange must fit the dead images");
+    static_assert(MC == 1, "the bias exchange assumes one 32-channel row per wave");
+    float *ex = lds + (g.wr + WR * g.wm) * ACCF, *bex = lds + WM * WR * ACCF;
+    for (int w = 1; w < WK; ++w) {
+        __syncthreads();
+        if (g.wk == w) {
+#pragma unroll
+            for (int i = 0; i < MC; ++i)
+#pragma unroll
+                for (int j = 0; j < MR; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) ex[((i * MR + j) * 16 + r) * 64 + g.lane] = A.acc[i][j][r];
+            if (g.want_bias && g.half == 0) bex[(g.wr + WR * g.wm) * 32 + g.l31] = A.bsum[0];
+        }
+        __syncthreads();
+        if (g.wk == 0) {
+#pragma unroll
+            for (int i = 0; i < MC; ++i)
+#pragma unroll
+                for (int j = 0; j < MR; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) A.acc[i][j][r] += ex[((i * MR + j) * 16 + r) * 64 + g.lane];
+            if (g.want_bias && g.half == 0) A.bsum[0] += bex[(g.wr + WR * g.wm) * 32 + g.l31];
+        }
+    }
+}
+
+// The wave's accumulators into slab s: rows of `row` floats, this wave's columns r0w + 32 j + l31 < rlim behind column
+// offset `off` (the fast-FIR families); the bias sums into the bias slab behind the S weight slabs.
+template <int MC, int MR, class Tile>
+__device__ __forceinline__ void wg_store_slab(const WgAcc<MC, MR> &A, float *slab, const Tile &g, int r0w, int rlim,
+                                              size_t row, int off, int Cout, int S) {
+    const size_t wslab = (size_t)Cout * row;
+    float *out = slab + (size_t)g.s * wslab + off;
+#pragma unroll
+    for (int i = 0; i < MC; ++i)
+#pragma unroll
+        for (int j = 0; j < MR; ++j) {
+            const int r = r0w + 32 * j + g.l31;
+            if (r < rlim) {
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    const int co = g.co0 + g.wm0 + 32 * i + acc_row(q, g.half);
+                    out[(size_t)co * row + r] = A.acc[i][j][q];
+                }
+            }
+        }
+    if (g.want_bias && g.half == 0) {
+#pragma unroll
+        for (int i = 0; i < MC; ++i)
+            slab[(size_t)S * wslab + (size_t)g.s * Cout + g.co0 + g.wm0 + 32 * i + g.l31] = A.bsum[i];
+    }
+}
+
+// stamps 3 and 4 of the DMA forms (diagnostic build): end of the stage loop, with what the workgroup did and where it
+// ran; end of the stores
+__device__ __forceinline__ void wg_stamp_stages_done(int total) {
+    ECG_STAMP_AT(g_stamps, 3);
+#ifdef ECG_STAMP
+    if (g_stamps && threadIdx.x == 0)          // stages | HW_ID (cu / sh / se) << 16 | XCC_ID << 48: which workgroups share a CU
+        g_stamps[(size_t)blockIdx.x * 8 + 5] = (unsigned long long)(total & 0xFFFF) |
+            ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 16) |
+            ((unsigned long long)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xF) << 48);
+#endif
+}
+__device__ __forceinline__ void wg_stamp_stored() {
+#ifdef ECG_STAMP
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+    ECG_STAMP_AT(g_stamps, 4);
+}
+
+// ---------------------------------------------------------------------------------------
+// Weight gradient, register-staged: serves dense or unaligned dY rows.
 // Pipeline: a stage is one (n, t-tile).  LDS holds TWO stage images {dY tile | x tile}.  While the
 // MFMAs of stage i run out of image i&1, the registers holding stage i+1 are written into image
 // (i+1)&1 (first half of the steps) and the loads of stage i+2 are issued (second half), one
@@ -548,27 +804,19 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_kernel(
     constexpr int XEL = NCI * XS, XLOADS = (XEL + 255) / 256;
     constexpr int NOPS = DLOADS + XLOADS;               // staging operations per stage (per thread)
     constexpr int IMG = M_T * DS + XEL;
-    constexpr int ACCF = MC * MR * 16 * 64;             // floats of one wave's accumulators
-    constexpr int LDSF = (WK > 1 && WM * WR * ACCF > 2 * IMG) ? WM * WR * ACCF : 2 * IMG;
     static_assert(XS >= XSPAN, "x row stride too small");
     static_assert(DEL % 256 == 0, "dY tile must be a whole number of 256-thread passes");
     static_assert(256 % T_T == 0 || T_T % 256 == 0, "dY tile rows per pass");
-    static_assert(XLOADS <= 32 && DLOADS <= 64, "mask bits");
+    static_assert(DLOADS <= 64, "mask bits");
 
-    __shared__ float lds[LDSF + (WK > 1 ? 4 * 32 : 0)];
+    __shared__ float lds[2 * IMG];
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int half = lane >> 5, l31 = lane & 31;
     const int R = Cin * KK;
-    // logical order: the R tiles of one (C_out tile, split) are adjacent — they read the same dY slice
-    const int RT = (R + R_T - 1) / R_T, CT = Cout / M_T;
-    const int tile = xcd_chunked(blockIdx.x, gridDim.x);
-    const int tile_r = tile % RT, tile_cs = tile / RT;
-    const int r0 = tile_r * R_T, co0 = (tile_cs % CT) * M_T, s = tile_cs / CT;
-    const int wk = wave % WK, wr = (wave / WK) % WR, wm = wave / (WK * WR);
-    const int wm0 = wm * (M_T / WM), wr0 = wr * (R_T / WR), wt0 = wk * TW;
+    const WgTile<M_T, R_T, WM, WR, WK> g((R + R_T - 1) / R_T, Cout);
+    const int tid = g.tid, half = g.half, l31 = g.l31;
+    const int r0 = g.tile_r * R_T, co0 = g.co0, wm0 = g.wm0, wr0 = g.wr0, wt0 = g.wk * TW;
     const int ci_base = r0 / KK;
-    const int n_begin = (int)((long long)N * s / S), n_end = (int)((long long)N * (s + 1) / S);
+    const int n_begin = (int)((long long)N * g.s / S), n_end = (int)((long long)N * (g.s + 1) / S);
 
     // per-lane LDS offset of column r = r0 + wr0 + 32*j + l31 inside the x tile: ci_local*XS + k
     int xcol[MR];
@@ -580,32 +828,19 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_kernel(
         xcol[j] = (ci - ci_base) * XS + (r - ci * KK);
     }
 
-    f32x16 acc[MC][MR], acc2[MC][MR];      // acc2: the second level
-    f32x16 zero16;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
-#pragma unroll
-    for (int a = 0; a < MC; ++a)
-#pragma unroll
-        for (int b = 0; b < MR; ++b) { acc[a][b] = zero16; acc2[a][b] = zero16; }
-    float bsum[MC], bsum2[MC];
-#pragma unroll
-    for (int a = 0; a < MC; ++a) bsum[a] = bsum2[a] = 0.f;
-    const bool want_bias = (tile_r == 0) && (wr == 0);
+    WgAcc<MC, MR> A;
+    A.clear();
 
     // ---- staging: loop-invariant per-thread pieces ------------------------------------------
+    // (dY goes through registers here, not by LDS-DMA: the rows this kernel serves are dense or unaligned)
     constexpr int RPP = (T_T >= 256) ? 1 : 256 / T_T;       // dY rows fetched per pass
     constexpr int PPR = (T_T >= 256) ? T_T / 256 : 1;       // passes per dY row
     const int drow0 = (T_T >= 256) ? 0 : tid / T_T, dtt = (T_T >= 256) ? tid : tid % T_T;
     int xci[XLOADS], xpos[XLOADS];
-#pragma unroll
-    for (int j = 0; j < XLOADS; ++j) {
-        const int e = min(tid + 256 * j, XEL - 1);
-        xci[j] = min(ci_base + e / XS, Cin - 1) * L;          // row offset (clamped into the tensor)
-        xpos[j] = e % XS - pad;
-    }
-    float dreg[DLOADS], xreg[XLOADS];
-    unsigned xmask = 0, dmask = 0;
+    wg_x_index<XEL, XS>(xci, xpos, tid, ci_base, Cin, L, pad);
+    float dreg[DLOADS];
+    WgXRegs<XEL> X;
+    unsigned dmask = 0;
     const int ntt = (Lo + T_T - 1) / T_T;
     const int total = (n_end - n_begin) * ntt;
 
@@ -630,25 +865,18 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_kernel(
             dreg[o] = pj[PPR == 1 ? dvoff : drow0 * ldy + min(dtt + extra, Lo - 1 - t0)];
         } else {
             const int j = o - DLOADS;
-            const int sidx = t0 + xpos[j];
-            xreg[j] = xn[xci[j] + min(max(sidx, 0), L - 1)];
-            const unsigned bit = ((sidx >= 0) && (sidx < L)) ? (1u << j) : 0u;
-            xmask = (j == 0) ? bit : (xmask | bit);
+            X.load(j, xn, xci[j], t0 + xpos[j], L);
         }
     };
     // the masks of the stage being committed must survive the loads of the following stage
-    unsigned cxmask = 0, cdmask = 0;
+    unsigned cdmask = 0;
     auto commit_op = [&](int o, float *img) {
         if (o < DLOADS) {
             const int row = drow0 + (o / PPR) * RPP, tt = dtt + (o % PPR) * 256;
             const unsigned keep = 0u - ((cdmask >> (o % PPR)) & 1u);
             img[row * DS + tt] = __uint_as_float(__float_as_uint(dreg[o]) & keep);
         } else {
-            const int j = o - DLOADS;
-            const int e = tid + 256 * j;
-            const unsigned keep = 0u - ((cxmask >> j) & 1u);
-            if (256 * (j + 1) <= XEL || e < XEL)
-                img[M_T * DS + e] = __uint_as_float(__float_as_uint(xreg[j]) & keep);
+            X.commit(o - DLOADS, img + M_T * DS, tid);
         }
     };
 
@@ -657,7 +885,7 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_kernel(
         stage_setup(0);
 #pragma unroll
         for (int o = 0; o < NOPS; ++o) load_op(o);
-        cxmask = xmask; cdmask = dmask;
+        X.latch(); cdmask = dmask;
 #pragma unroll
         for (int o = 0; o < NOPS; ++o) commit_op(o, lds);
         if (total > 1) {
@@ -672,7 +900,7 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_kernel(
         const float *dys = lds + (it & 1) * IMG, *xs = dys + M_T * DS;
         float *nxt = lds + ((it + 1) & 1) * IMG;
         const bool do_commit = it + 1 < total, do_load = it + 2 < total;
-        cxmask = xmask; cdmask = dmask;                    // masks of stage it+1 (now in registers)
+        X.latch(); cdmask = dmask;                         // masks of stage it+1 (now in registers)
         if (do_load) stage_setup(it + 2);                  // bases/masks for the loads issued below
 
         const float *arow = dys + (wm0 + l31) * DS + wt0 + half;
@@ -703,101 +931,29 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_kernel(
             }
             __builtin_amdgcn_sched_barrier(0);         // keep reads + staging ABOVE these MFMAs
 #pragma unroll
-            for (int i = 0; i < MC; ++i) bsum[i] = (st == 0) ? a_c[i] : bsum[i] + a_c[i];   // bias-grad rides on the A fragments
+            for (int i = 0; i < MC; ++i) A.bsum[i] = (st == 0) ? a_c[i] : A.bsum[i] + a_c[i];   // bias-grad rides on the A fragments
 #pragma unroll
             for (int i = 0; i < MC; ++i)
 #pragma unroll
                 for (int j = 0; j < MR; ++j)
-                    acc[i][j] = mfma32(a_c[i], b_c[j], (st == 0) ? zero16 : acc[i][j]);
+                    A.acc[i][j] = mfma32(a_c[i], b_c[j], (st == 0) ? A.zero16 : A.acc[i][j]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int i = 0; i < MC; ++i) a_c[i] = a_n[i];
 #pragma unroll
             for (int j = 0; j < MR; ++j) b_c[j] = b_n[j];
         }
-        // second level: the stage's sums join the running totals
-#pragma unroll
-        for (int i = 0; i < MC; ++i)
-#pragma unroll
-            for (int j = 0; j < MR; ++j) acc2[i][j] += acc[i][j];
-#pragma unroll
-        for (int i = 0; i < MC; ++i) bsum2[i] += bsum[i];
+        A.fold();
+        A.fold_bias();
         __syncthreads();      // image it&1 free again; image (it+1)&1 complete
     }
 
-#pragma unroll
-    for (int i = 0; i < MC; ++i) {
-        bsum[i] = bsum2[i];
-#pragma unroll
-        for (int j = 0; j < MR; ++j) acc[i][j] = acc2[i][j];
+    A.finish(g.want_bias);
+    if constexpr (WK > 1) {
+        wg_wk_exchange<WM, WR, WK, 2 * IMG>(A, lds, g);
+        if (g.wk != 0) return;
     }
-    // ---- combine the WK t-split waves through LDS (fixed order), then write the slab ---------
-    if (WK > 1) {
-        float *bred = lds + LDSF;      // [4][32] bias partials
-        float *ex = lds + (wr + WR * wm) * ACCF;      // one exchange area per group of WK waves that share an output tile
-        for (int w = 1; w < WK; ++w) {
-            __syncthreads();
-            if (wk == w) {
-#pragma unroll
-                for (int i = 0; i < MC; ++i)
-#pragma unroll
-                    for (int j = 0; j < MR; ++j)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            ex[((i * MR + j) * 16 + r) * 64 + lane] = acc[i][j][r];
-            }
-            __syncthreads();
-            if (wk == 0) {
-#pragma unroll
-                for (int i = 0; i < MC; ++i)
-#pragma unroll
-                    for (int j = 0; j < MR; ++j)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            acc[i][j][r] += ex[((i * MR + j) * 16 + r) * 64 + lane];
-            }
-        }
-        static_assert(WK == 1 || (WM == 1 && MC == 1), "the bias exchange below assumes one 32-channel row, wk fastest in the wave index");
-        {
-            // WK > 1 is only instantiated with WM == 1, MC == 1: 32 channels; waves 0 .. WK-1 are (wr = 0, wk = 0 .. WK-1).
-            // The barriers are unconditional: want_bias differs between the waves of a workgroup when WR > 1.
-            const float b = bsum[0] + __shfl_xor(bsum[0], 32, 64);
-            __syncthreads();
-            if (want_bias && half == 0) bred[wave * 32 + l31] = b;
-            __syncthreads();
-            if (want_bias && wave == 0 && half == 0) {
-                float t = bred[l31];
-                for (int w = 1; w < WK; ++w) t += bred[w * 32 + l31];
-                bsum[0] = t;
-            }
-        }
-    } else if (want_bias) {
-#pragma unroll
-        for (int i = 0; i < MC; ++i) bsum[i] += __shfl_xor(bsum[i], 32, 64);
-    }
-
-    const size_t wslab = (size_t)Cout * R;
-    if (wk == 0) {
-        float *out = slab + (size_t)s * wslab;
-#pragma unroll
-        for (int i = 0; i < MC; ++i)
-#pragma unroll
-            for (int j = 0; j < MR; ++j) {
-                const int r = r0 + wr0 + 32 * j + l31;
-                if (r < R) {
-#pragma unroll
-                    for (int q = 0; q < 16; ++q) {
-                        const int co = co0 + wm0 + 32 * i + acc_row(q, half);
-                        out[(size_t)co * R + r] = acc[i][j][q];
-                    }
-                }
-            }
-        if (want_bias && half == 0) {
-#pragma unroll
-            for (int i = 0; i < MC; ++i)
-                slab[(size_t)S * wslab + (size_t)s * Cout + co0 + wm0 + 32 * i + l31] = bsum[i];
-        }
-    }
+    wg_store_slab(A, slab, g, r0 + wr0, R, (size_t)R, 0, Cout, S);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -828,8 +984,7 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_dma_kernel(
     const float *__restrict__ dy, const float *__restrict__ x, float *__restrict__ slab, int N,
     int Cin, int Cout, int L, int Lo, int ldy, int pad, int S) {
     static_assert(WM * WR * WK == 4, "4 waves per workgroup");
-    static_assert(T_T == 64 || T_T == 128, "64 or 128 time steps per stage");
-    constexpr int LPR = T_T / 4, RPP = 64 / LPR;        // 16-byte chunks (lanes) per dY row; rows per 1 KB DMA piece
+    using Dy = WgDyDma<M_T, T_T>;
     constexpr int MC = M_T / WM / 32, MR = R_T / WR / 32;
     constexpr int TW = T_T / WK;                        // WK > 1: the waves split the stage's t range (32-channel layer)
     constexpr int NST = TW / 2, NGRP = NST / 4;         // reduction steps per stage, in groups of 4
@@ -838,35 +993,20 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_dma_kernel(
     constexpr int XS = ((XSPAN - KK + 31) / 32) * 32 + KK;   // >= XSPAN and == KK (mod 32)
     constexpr int NCI = (R_T + KK - 2) / KK + 1;
     constexpr int XEL = NCI * XS, XLOADS = (XEL + 255) / 256;
-    constexpr int AEL = M_T * T_T;                      // floats of the dY image
-    constexpr int NDMA = AEL / 256;                     // 1 KB pieces (4 rows each)
-    constexpr int DPW = NDMA / 4;                       // pieces per wave per stage
+    constexpr int AEL = Dy::AEL, DPW = Dy::DPW;
     constexpr int IMG = ((AEL + XEL + 63) / 64) * 64;   // keeps image 1 16-byte aligned
-    constexpr int ACCF = MC * MR * 16 * 64;             // floats of one wave's accumulators (WK > 1 exchange)
-    static_assert(WK == 1 || WM * WR * ACCF + 4 * 32 <= 2 * IMG, "accumulator exchange must fit the dead images");
     static_assert(XS >= XSPAN, "x row stride too small");
-    static_assert(NDMA % 4 == 0, "dY image must split evenly over the four waves");
-    static_assert(XLOADS <= 32, "mask bits");
     static_assert(NST >= 2 * XLOADS + DPW, "not enough steps to spread the staging over");
 
     __shared__ __attribute__((aligned(1024))) float lds[2 * IMG];
     ECG_STAMP_AT(g_stamps, 0);
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int half = lane >> 5, l31 = lane & 31;
     const int R = Cin * KK;
-    // logical order: the R tiles of one (C_out tile, split) are adjacent — they read the same dY slice
-    const int RT = (R + R_T - 1) / R_T, CT = Cout / M_T;
-    const int tile = xcd_chunked(blockIdx.x, gridDim.x);
-    const int tile_r = tile % RT, tile_cs = tile / RT;
-    const int r0 = tile_r * R_T, co0 = (tile_cs % CT) * M_T, s = tile_cs / CT;
-    const int wk = wave % WK, wr = (wave / WK) % WR, wm = wave / (WK * WR);
-    const int wm0 = wm * (M_T / WM), wr0 = wr * (R_T / WR), wt0 = wk * TW;
+    const WgTile<M_T, R_T, WM, WR, WK> g((R + R_T - 1) / R_T, Cout);
+    const int tid = g.tid, half = g.half, l31 = g.l31;
+    const int r0 = g.tile_r * R_T, wm0 = g.wm0, wr0 = g.wr0, wt0 = g.wk * TW;
     const int ci_base = r0 / KK;
-    const int ntt = (Lo + T_T - 1) / T_T;
-    // the split runs over stages (n, t tile), not whole samples: finer balance, and enough workgroups for
-    // layers with a single output tile
-    const int it_begin = (int)((long long)N * ntt * s / S), it_end = (int)((long long)N * ntt * (s + 1) / S);
+    Dy D(dy, lds, N, Cout, Lo, ldy, S, g);
 
     int xcol[MR];
 #pragma unroll
@@ -877,86 +1017,25 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_dma_kernel(
         xcol[j] = (ci - ci_base) * XS + (r - ci * KK);
     }
 
-    f32x16 acc[MC][MR], acc2[MC][MR];      // acc2: the second level
-    f32x16 zero16;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
-#pragma unroll
-    for (int a = 0; a < MC; ++a)
-#pragma unroll
-        for (int b = 0; b < MR; ++b) { acc[a][b] = zero16; acc2[a][b] = zero16; }
-    float bsum[MC], bsum2[MC];
-#pragma unroll
-    for (int a = 0; a < MC; ++a) bsum[a] = bsum2[a] = 0.f;
-    const bool want_bias = (tile_r == 0) && (wr == 0);
+    WgAcc<MC, MR> A;
+    A.clear();
 
     // ---- staging: loop-invariant per-thread pieces ------------------------------------------
-    int doff[DPW];          // dY piece j of this wave: element offset from the stage base
-#pragma unroll
-    for (int j = 0; j < DPW; ++j) {
-        const int row = (j * 4 + wave) * RPP + lane / LPR;          // row inside the M_T tile
-        doff[j] = row * ldy + (((lane % LPR) ^ (row & 15)) << 2);   // LDS chunk c <- global chunk c^(row&15)
-    }
     int xci[XLOADS], xpos[XLOADS];
-#pragma unroll
-    for (int j = 0; j < XLOADS; ++j) {
-        const int e = min(tid + 256 * j, XEL - 1);
-        xci[j] = min(ci_base + e / XS, Cin - 1) * L;
-        xpos[j] = e % XS - pad;
-    }
-    float xreg[XLOADS];
-    unsigned xmask = 0, cxmask = 0;
-    const int total = it_end - it_begin;
-
-    // stage coordinates advance incrementally (uniform, no division in the loop)
-    int sn = it_begin / ntt, stt = it_begin - sn * ntt;     // stage whose x tile is loaded next
-    int dn = sn, dtt = stt;                                 // stage whose dY tile is DMA'd next
-    auto advance = [&]() { if (++stt == ntt) { stt = 0; ++sn; } };
-    const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) float *)lds;
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    auto dma_a = [&](int j, float *img) {               // one 1 KB piece of stage (dn, dtt)'s dY tile (asm LDS-DMA: glds16)
-        const float *base = dy + ((size_t)min(dn, N - 1) * Cout + co0) * ldy + dtt * T_T;        // uniform
-        glds16(base, (unsigned)doff[j] * 4u,
-               (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_base + (unsigned)((img - lds) + (j * 4 + wave_u) * 256) * 4u)));
-    };
+    wg_x_index<XEL, XS>(xci, xpos, tid, ci_base, Cin, L, pad);
+    WgXRegs<XEL> X;
+    const int total = D.total;
     auto load_x = [&](int j) {                          // x tile element of stage (sn, stt)
-        const float *xn = x + (size_t)min(sn, N - 1) * Cin * L;
-        const int sidx = stt * T_T + xpos[j];
-        xreg[j] = xn[xci[j] + min(max(sidx, 0), L - 1)];
-        const unsigned bit = ((sidx >= 0) && (sidx < L)) ? (1u << j) : 0u;
-        xmask = (j == 0) ? bit : (xmask | bit);
+        X.load(j, x + (size_t)min(D.sn, N - 1) * Cin * L, xci[j], D.stt * T_T + xpos[j], L);
     };
-    auto commit_x = [&](int j, float *img) {
-        const int e = tid + 256 * j;
-        const unsigned keep = 0u - ((cxmask >> j) & 1u);
-        if (256 * (j + 1) <= XEL || e < XEL)
-            img[AEL + e] = __uint_as_float(__float_as_uint(xreg[j]) & keep);
-    };
-
-    // prologue: stage 0 -> image 0, x tile of stage 1 -> registers
-    if (total > 0) {
-#pragma unroll
-        for (int j = 0; j < DPW; ++j) dma_a(j, lds);
-#pragma unroll
-        for (int j = 0; j < XLOADS; ++j) load_x(j);
-        cxmask = xmask;
-#pragma unroll
-        for (int j = 0; j < XLOADS; ++j) commit_x(j, lds);
-        advance();
-        dn = sn; dtt = stt;                             // stage 1
-#pragma unroll
-        for (int j = 0; j < XLOADS; ++j) load_x(j);
-        advance();                                      // stage 2
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // (the asm DMA pieces are not in hipcc's books)
-    __syncthreads();
+    wg_dma_prologue(D, X, tid, load_x);
     ECG_STAMP_AT(g_stamps, 1);
 
     const int aoff = (wm0 + l31) * T_T, swz = (l31 & 15) << 2;
     for (int it = 0; it < total; ++it) {
         const float *dys = lds + (it & 1) * IMG, *xs = dys + AEL;
         float *nxt = lds + ((it + 1) & 1) * IMG;
-        cxmask = xmask;                                    // mask of stage it+1 (now in registers)
+        X.latch();                                         // mask of stage it+1 (now in registers)
 
         const float *arow = dys + aoff;
         const float *brow = xs + 4 * half + wt0;
@@ -984,17 +1063,17 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_dma_kernel(
             // nobody reads): under a branch hipcc puts s_waitcnt vmcnt(0) in front of every load.
             // (Issuing the DMA pieces FIRST — 14 instead of 4 steps of slack before the barrier on the
             // 32-channel tile — measured the same: the stage loop is not waiting for the DMA.)
-            if (st < XLOADS) commit_x(st, nxt);
+            if (st < XLOADS) X.commit(st, nxt + AEL, tid);
             else if (st < 2 * XLOADS) load_x(st - XLOADS);
-            else if (st < 2 * XLOADS + DPW) dma_a(st - 2 * XLOADS, nxt);
+            else if (st < 2 * XLOADS + DPW) D.issue(st - 2 * XLOADS, nxt);
             __builtin_amdgcn_sched_barrier(0);         // keep reads + staging ABOVE these MFMAs
 #pragma unroll
-            for (int i = 0; i < MC; ++i) bsum[i] = (st == 0) ? aq_c[i][j4] : bsum[i] + aq_c[i][j4];
+            for (int i = 0; i < MC; ++i) A.bsum[i] = (st == 0) ? aq_c[i][j4] : A.bsum[i] + aq_c[i][j4];
 #pragma unroll
             for (int i = 0; i < MC; ++i)
 #pragma unroll
                 for (int j = 0; j < MR; ++j)
-                    acc[i][j] = mfma32(aq_c[i][j4], b_c[j], (st == 0) ? zero16 : acc[i][j]);
+                    A.acc[i][j] = mfma32(aq_c[i][j4], b_c[j], (st == 0) ? A.zero16 : A.acc[i][j]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int j = 0; j < MR; ++j) b_c[j] = b_n[j];
@@ -1003,89 +1082,23 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_dma_kernel(
                 for (int i = 0; i < MC; ++i) aq_c[i] = aq_n[i];
             }
         }
-        // second level: the stage's sums join the running totals, in issue order of the MFMAs
-#pragma unroll
-        for (int i = 0; i < MC; ++i)
-#pragma unroll
-            for (int j = 0; j < MR; ++j) acc2[i][j] += acc[i][j];
-#pragma unroll
-        for (int i = 0; i < MC; ++i) bsum2[i] += bsum[i];
-        dn = sn; dtt = stt;
-        advance();
+        A.fold();
+        A.fold_bias();
+        D.follow();
+        D.advance();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();      // image it&1 free again; image (it+1)&1 complete (vmcnt(0) + barrier)
         if (it == 0) ECG_STAMP_AT(g_stamps, 2);
     }
-    ECG_STAMP_AT(g_stamps, 3);
-#ifdef ECG_STAMP
-    if (g_stamps && threadIdx.x == 0)          // stages | HW_ID (cu / sh / se) << 16 | XCC_ID << 48: which workgroups share a CU
-        g_stamps[(size_t)blockIdx.x * 8 + 5] = (unsigned long long)(total & 0xFFFF) |
-            ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 16) |
-            ((unsigned long long)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xF) << 48);
-#endif
+    wg_stamp_stages_done(total);
 
-#pragma unroll
-    for (int i = 0; i < MC; ++i) {
-        bsum[i] = bsum2[i];
-#pragma unroll
-        for (int j = 0; j < MR; ++j) acc[i][j] = acc2[i][j];
+    A.finish(g.want_bias);
+    if constexpr (WK > 1) {
+        wg_wk_exchange<WM, WR, WK, 2 * IMG>(A, lds, g);
+        if (g.wk != 0) return;
     }
-    if (want_bias) {
-#pragma unroll
-        for (int i = 0; i < MC; ++i) bsum[i] += __shfl_xor(bsum[i], 32, 64);
-    }
-    if (WK > 1) {
-        // sum the WK waves that share an output tile through LDS, in wave order (the images are dead)
-        float *ex = lds + (wr + WR * wm) * ACCF, *bex = lds + WM * WR * ACCF;
-        for (int w = 1; w < WK; ++w) {
-            __syncthreads();
-            if (wk == w) {
-#pragma unroll
-                for (int i = 0; i < MC; ++i)
-#pragma unroll
-                    for (int j = 0; j < MR; ++j)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) ex[((i * MR + j) * 16 + r) * 64 + lane] = acc[i][j][r];
-                if (want_bias && half == 0 && MC == 1) bex[(wr + WR * wm) * 32 + l31] = bsum[0];
-            }
-            __syncthreads();
-            if (wk == 0) {
-#pragma unroll
-                for (int i = 0; i < MC; ++i)
-#pragma unroll
-                    for (int j = 0; j < MR; ++j)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) acc[i][j][r] += ex[((i * MR + j) * 16 + r) * 64 + lane];
-                if (want_bias && half == 0 && MC == 1) bsum[0] += bex[(wr + WR * wm) * 32 + l31];
-            }
-        }
-        static_assert(WK == 1 || MC == 1, "the bias exchange above assumes one 32-channel row per wave");
-        if (wk != 0) return;
-    }
-    const size_t wslab = (size_t)Cout * R;
-    float *out = slab + (size_t)s * wslab;
-#pragma unroll
-    for (int i = 0; i < MC; ++i)
-#pragma unroll
-        for (int j = 0; j < MR; ++j) {
-            const int r = r0 + wr0 + 32 * j + l31;
-            if (r < R) {
-#pragma unroll
-                for (int q = 0; q < 16; ++q) {
-                    const int co = co0 + wm0 + 32 * i + acc_row(q, half);
-                    out[(size_t)co * R + r] = acc[i][j][q];
-                }
-            }
-        }
-    if (want_bias && half == 0) {
-#pragma unroll
-        for (int i = 0; i < MC; ++i)
-            slab[(size_t)S * wslab + (size_t)s * Cout + co0 + wm0 + 32 * i + l31] = bsum[i];
-    }
-#ifdef ECG_STAMP
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-    ECG_STAMP_AT(g_stamps, 4);
+    wg_store_slab(A, slab, g, r0 + wr0, R, (size_t)R, 0, Cout, S);
+    wg_stamp_stored();
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1110,42 +1123,33 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_ffa_kernel(
     int Cin, int Cout, int L, int Lo, int ldy, int pad, int S) {
     static_assert(WM * WR == 4, "4 waves per workgroup");
     static_assert(kKM == 15, "tap split 8 + 7");
-    static_assert(T_T == 64 || T_T == 128, "64 or 128 time steps per stage");
-    constexpr int LPR = T_T / 4, RPP = 64 / LPR;
+    using Dy = WgDyDma<M_T, T_T>;
+    constexpr int LPR = Dy::LPR, RPP = Dy::RPP;
     constexpr int MC = M_T / WM / 32, MR = R_T / WR / 32;
     constexpr int NST = T_T / 4, NGRP = NST / 4;        // MFMA steps per stage (two m each), in groups of 4 (= 16 t per lane half)
     constexpr int XS = T_T + 16;                        // >= T_T + 14, == 16 (mod 64), even
     static_assert(XS % 64 == 16, "x rows 16 banks apart");
     constexpr int NCI = (R_T + 6) / 7 + 1;              // channels a column tile of the 7-tap family can touch
     constexpr int XEL = NCI * XS, XLOADS = (XEL + 255) / 256;
-    constexpr int AEL = M_T * T_T;
-    constexpr int NDMA = AEL / 256;
-    constexpr int DPW = NDMA / 4;
+    constexpr int AEL = Dy::AEL, DPW = Dy::DPW;
     constexpr int IMG = ((AEL + XEL + 63) / 64) * 64;
     constexpr int OPS = 2 * XLOADS + DPW;               // staging operations of a stage, spread over its steps
-    static_assert(NDMA % 4 == 0, "dY image must split evenly over the four waves");
-    static_assert(XLOADS <= 32, "mask bits");
     static_assert(2 * IMG * 4 <= 80 * 1024, "two workgroups per CU");
 
     __shared__ __attribute__((aligned(1024))) float lds[2 * IMG];
     ECG_STAMP_AT(g_stamps, 0);
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int half = lane >> 5, l31 = lane & 31;
     const int RU = Cin * 8, RV = Cin * 7;
     const int TU = (RU + R_T - 1) / R_T, TV = (RV + R_T - 1) / R_T;
-    const int RT = 2 * TU + TV, CT = Cout / M_T;
-    const int tile = xcd_chunked(blockIdx.x, gridDim.x);
-    const int tile_r = tile % RT, tile_cs = tile / RT;
+    const WgTile<M_T, R_T, WM, WR, 1> g(2 * TU + TV, Cout);     // (want_bias: family U, its A operand sums to the bias gradient)
+    const int tid = g.tid, half = g.half, l31 = g.l31, tile_r = g.tile_r;
     const int fam = tile_r < TU ? 0 : (tile_r < TU + TV ? 1 : 2);                 // uniform per workgroup
     const int tile_rf = tile_r - (fam == 0 ? 0 : (fam == 1 ? TU : TU + TV));
     const int NJ = fam == 1 ? 7 : 8, RF = Cin * NJ, offf = fam == 0 ? 0 : (fam == 1 ? RU : RU + RV);
-    const int r0 = tile_rf * R_T, co0 = (tile_cs % CT) * M_T, s = tile_cs / CT;
-    const int wr = wave % WR, wm = wave / WR;
-    const int wm0 = wm * (M_T / WM), wr0 = wr * (R_T / WR);
+    const int r0 = tile_rf * R_T, wm0 = g.wm0, wr0 = g.wr0;
     const int ci_base = r0 / NJ;
     const int ntt = (Lo + T_T - 1) / T_T;
-    const int it_begin = (int)((long long)N * ntt * s / S), it_end = (int)((long long)N * ntt * (s + 1) / S);
+    const int it_begin = (int)((long long)N * ntt * g.s / S), it_end = (int)((long long)N * ntt * (g.s + 1) / S);
 
     int xcol[MR];
 #pragma unroll
@@ -1156,52 +1160,34 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_ffa_kernel(
         xcol[j] = (ci - ci_base) * XS + 2 * (r - ci * NJ) + 8 * half;
     }
 
-    f32x16 acc[MC][MR], acc2[MC][MR];
-    f32x16 zero16;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
-#pragma unroll
-    for (int a = 0; a < MC; ++a)
-#pragma unroll
-        for (int b = 0; b < MR; ++b) { acc[a][b] = zero16; acc2[a][b] = zero16; }
-    float bsum[MC], bsum2[MC];
-#pragma unroll
-    for (int a = 0; a < MC; ++a) bsum[a] = bsum2[a] = 0.f;
-    const bool want_bias = (tile_r == 0) && (wr == 0);     // (family U: its A operand sums to the bias gradient)
+    WgAcc<MC, MR> A;
+    A.clear();
 
+    // not WgDyDma / wg_dma_prologue: this kernel sits at 256 VGPRs with spills, and with its dY pieces and cursor in the
+    // shared stager its register allocation came out worse (scratch 80 -> 96 bytes per lane); they stay its own
     int doff[DPW];
 #pragma unroll
     for (int j = 0; j < DPW; ++j) {
-        const int row = (j * 4 + wave) * RPP + lane / LPR;
-        doff[j] = row * ldy + (((lane % LPR) ^ (row & 15)) << 2);
+        const int row = (j * 4 + g.wave) * RPP + g.lane / LPR;
+        doff[j] = row * ldy + (((g.lane % LPR) ^ (row & 15)) << 2);
     }
-    float xreg[XLOADS];                                 // (element -> (channel, position) is recomputed per load: registers)
-    unsigned xmask = 0, cxmask = 0;
+    WgXRegs<XEL> X;
     const int total = it_end - it_begin;
 
     int sn = it_begin / ntt, stt = it_begin - sn * ntt;
     int dn = sn, dtt = stt;
     auto advance = [&]() { if (++stt == ntt) { stt = 0; ++sn; } };
     const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) float *)lds;
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    const int wave_u = __builtin_amdgcn_readfirstlane(g.wave);
     auto dma_a = [&](int j, float *img) {
-        const float *base = dy + ((size_t)min(dn, N - 1) * Cout + co0) * ldy + dtt * T_T;
+        const float *base = dy + ((size_t)min(dn, N - 1) * Cout + g.co0) * ldy + dtt * T_T;
         glds16(base, (unsigned)doff[j] * 4u,
                (unsigned)__builtin_amdgcn_readfirstlane((int)(lds_base + (unsigned)((img - lds) + (j * 4 + wave_u) * 256) * 4u)));
     };
+    // not wg_x_index: for the same reason element -> (channel, position) is recomputed per load
     auto load_x = [&](int j) {
-        const float *xn = x + (size_t)min(sn, N - 1) * Cin * L;
         const int e = min(tid + 256 * j, XEL - 1), row = e / XS;
-        const int sidx = stt * T_T + (e - row * XS) - pad;
-        xreg[j] = xn[min(ci_base + row, Cin - 1) * L + min(max(sidx, 0), L - 1)];
-        const unsigned bit = ((sidx >= 0) && (sidx < L)) ? (1u << j) : 0u;
-        xmask = (j == 0) ? bit : (xmask | bit);
-    };
-    auto commit_x = [&](int j, float *img) {
-        const int e = tid + 256 * j;
-        const unsigned keep = 0u - ((cxmask >> j) & 1u);
-        if (256 * (j + 1) <= XEL || e < XEL)
-            img[AEL + e] = __uint_as_float(__float_as_uint(xreg[j]) & keep);
+        X.load(j, x + (size_t)min(sn, N - 1) * Cin * L, min(ci_base + row, Cin - 1) * L, stt * T_T + (e - row * XS) - pad, L);
     };
 
     if (total > 0) {
@@ -1209,9 +1195,9 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_ffa_kernel(
         for (int j = 0; j < DPW; ++j) dma_a(j, lds);
 #pragma unroll
         for (int j = 0; j < XLOADS; ++j) load_x(j);
-        cxmask = xmask;
+        X.latch();
 #pragma unroll
-        for (int j = 0; j < XLOADS; ++j) commit_x(j, lds);
+        for (int j = 0; j < XLOADS; ++j) X.commit(j, lds + AEL, tid);
         advance();
         dn = sn; dtt = stt;
 #pragma unroll
@@ -1229,7 +1215,7 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_ffa_kernel(
         constexpr int FAM = decltype(fam_c)::value;
         const float *dys = lds + (it & 1) * IMG, *xs = dys + AEL;
         float *nxt = lds + ((it + 1) & 1) * IMG;
-        cxmask = xmask;
+        X.latch();
         const float *arow = dys + aoff;
         // group g: this lane half's eight consecutive t (two 16-byte chunks, swizzled) [+ V: the element in front of them]
         // (the first chunk is read two steps before the group starts, the second during its first step: one spare set of
@@ -1273,7 +1259,7 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_ffa_kernel(
                 // dY pieces FIRST (a stage is 16 short steps: issued last they would be waited for at the barrier), then the
                 // x commits, then the loads of the stage after next — the youngest vector-memory operations, left in flight
                 if (o < DPW) dma_a(o, nxt);
-                else if (o < DPW + XLOADS) commit_x(o - DPW, nxt);
+                else if (o < DPW + XLOADS) X.commit(o - DPW, nxt + AEL, tid);
                 else load_x(o - DPW - XLOADS);
             }
             float av[MC], bv[MR];
@@ -1289,13 +1275,13 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_ffa_kernel(
             __builtin_amdgcn_sched_barrier(0);
             if (FAM == 0) {
 #pragma unroll
-                for (int i = 0; i < MC; ++i) bsum[i] = (st == 0) ? av[i] : bsum[i] + av[i];
+                for (int i = 0; i < MC; ++i) A.bsum[i] = (st == 0) ? av[i] : A.bsum[i] + av[i];
             }
 #pragma unroll
             for (int i = 0; i < MC; ++i)
 #pragma unroll
                 for (int j = 0; j < MR; ++j)
-                    acc[i][j] = mfma32(av[i], bv[j], (st == 0) ? zero16 : acc[i][j]);
+                    A.acc[i][j] = mfma32(av[i], bv[j], (st == 0) ? A.zero16 : A.acc[i][j]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int j = 0; j < MR; ++j) b_c[j] = b_n[j];
@@ -1312,17 +1298,11 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_ffa_kernel(
                 const float a = half ? 0.f : dl;
 #pragma unroll
                 for (int j = 0; j < MR; ++j)
-                    acc[i][j] = mfma32(a, xs[xcol[j] - 8 * half + T_T + 1], acc[i][j]);
+                    A.acc[i][j] = mfma32(a, xs[xcol[j] - 8 * half + T_T + 1], A.acc[i][j]);
             }
         }
-#pragma unroll
-        for (int i = 0; i < MC; ++i)
-#pragma unroll
-            for (int j = 0; j < MR; ++j) acc2[i][j] += acc[i][j];
-        if (FAM == 0) {
-#pragma unroll
-            for (int i = 0; i < MC; ++i) bsum2[i] += bsum[i];
-        }
+        A.fold();
+        if (FAM == 0) A.fold_bias();
         dn = sn; dtt = stt;
         advance();
         asm volatile("s_waitcnt vmcnt(%0)" :: "n"(XLOADS) : "memory");    // the DMA pieces are older than the x loads
@@ -1331,48 +1311,11 @@ __global__ __launch_bounds__(256, 2) void conv1d_mfma_wgrad_ffa_kernel(
     if (fam == 0) { for (int it = 0; it < total; ++it) { stage(std::integral_constant<int, 0>{}, it); if (it == 0) ECG_STAMP_AT(g_stamps, 2); } }
     else if (fam == 1) { for (int it = 0; it < total; ++it) { stage(std::integral_constant<int, 1>{}, it); if (it == 0) ECG_STAMP_AT(g_stamps, 2); } }
     else { for (int it = 0; it < total; ++it) { stage(std::integral_constant<int, 2>{}, it); if (it == 0) ECG_STAMP_AT(g_stamps, 2); } }
-    ECG_STAMP_AT(g_stamps, 3);
-#ifdef ECG_STAMP
-    if (g_stamps && threadIdx.x == 0)          // stages | HW_ID << 16 | XCC_ID << 48 (as conv1d_mfma_wgrad_dma_kernel)
-        g_stamps[(size_t)blockIdx.x * 8 + 5] = (unsigned long long)(total & 0xFFFF) |
-            ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 16) |
-            ((unsigned long long)(__builtin_amdgcn_s_getreg((31 << 11) | 20) & 0xF) << 48);
-#endif
+    wg_stamp_stages_done(total);
 
-#pragma unroll
-    for (int i = 0; i < MC; ++i) {
-        bsum[i] = bsum2[i];
-#pragma unroll
-        for (int j = 0; j < MR; ++j) acc[i][j] = acc2[i][j];
-    }
-    if (want_bias) {
-#pragma unroll
-        for (int i = 0; i < MC; ++i) bsum[i] += __shfl_xor(bsum[i], 32, 64);
-    }
-    const size_t RVT = (size_t)Cin * 23, wslab = (size_t)Cout * RVT;
-    float *out = slab + (size_t)s * wslab + offf;
-#pragma unroll
-    for (int i = 0; i < MC; ++i)
-#pragma unroll
-        for (int j = 0; j < MR; ++j) {
-            const int r = r0 + wr0 + 32 * j + l31;
-            if (r < RF) {
-#pragma unroll
-                for (int q = 0; q < 16; ++q) {
-                    const int co = co0 + wm0 + 32 * i + acc_row(q, half);
-                    out[(size_t)co * RVT + r] = acc[i][j][q];
-                }
-            }
-        }
-    if (want_bias && half == 0) {
-#pragma unroll
-        for (int i = 0; i < MC; ++i)
-            slab[(size_t)S * wslab + (size_t)s * Cout + co0 + wm0 + 32 * i + l31] = bsum[i];
-    }
-#ifdef ECG_STAMP
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-    ECG_STAMP_AT(g_stamps, 4);
+    A.finish(g.want_bias);
+    wg_store_slab(A, slab, g, r0 + wr0, RF, (size_t)Cin * 23, offf, Cout, S);
+    wg_stamp_stored();
 }
 
 // dw[co][ci][k] from the S slabs of the kernel above: one lane per (co, ci, tap pair j) forms dW[2j] = U[j] - G[j] and
