@@ -442,6 +442,10 @@ bool wgrad_bf16_tk_supported(int Cin, int Cout, int K, int pad) {
 
 int wgrad_bf16_tk_dy_stride(int Lo) { return cdiv(Lo, tk::TT) * tk::TT; }
 
+// the shortest input row the entry point takes (its ECG_REQUIRE below); callers that choose between this form and the
+// fp32 one ask ecg_conv1d_bf16_tk_min_len instead of carrying the number
+constexpr int TK_MIN_L = 16;
+
 size_t wgrad_bf16_tk_ws_floats(int N, int Cin, int Cout, int L, int K, int pad) {
     return tk_plan(N, Cin, Cout, L + 2 * pad - K + 1).slab_floats + 16;
 }
@@ -474,6 +478,8 @@ ECG_API int ecg_conv1d_bf16_tk_supported(int C_in, int C_out, int K, int pad) {
     return wgrad_bf16_tk_supported(C_in, C_out, K, pad) ? 1 : 0;
 }
 
+ECG_API int ecg_conv1d_bf16_tk_min_len(void) { return TK_MIN_L; }
+
 ECG_API int ecg_conv1d_bf16_tk_dy_stride(int Lo) { return Lo > 0 ? wgrad_bf16_tk_dy_stride(Lo) : 0; }
 
 ECG_API size_t ecg_conv1d_bwd_weight_bf16_ncl_ws_floats(int N, int C_in, int C_out, int L, int K, int pad) {
@@ -484,8 +490,8 @@ ECG_API size_t ecg_conv1d_bwd_weight_bf16_ncl_ws_floats(int N, int C_in, int C_o
 ECG_API int ecg_conv1d_bwd_weight_bias_bf16_ncl(const void *dy_bf16, int ldy, const void *x, int x_is_bf16, int ldx,
                                                 float *dw, float *db, float *ws, int N, int C_in, int C_out, int L,
                                                 int K, int pad, ecg_stream_t stream) {
-    ECG_REQUIRE(N > 0 && C_in > 0 && C_out > 0 && L >= 16, "conv1d_bwd_weight_bias_bf16_ncl: N=%d C_in=%d C_out=%d L=%d", N,
-                C_in, C_out, L);
+    ECG_REQUIRE(N > 0 && C_in > 0 && C_out > 0 && L >= TK_MIN_L,
+                "conv1d_bwd_weight_bias_bf16_ncl: N=%d C_in=%d C_out=%d L=%d", N, C_in, C_out, L);
     ECG_REQUIRE(wgrad_bf16_tk_supported(C_in, C_out, K, pad),
                 "conv1d_bwd_weight_bias_bf16_ncl: needs K == 15, pad == 7, C_out %% 32 == 0");
     ECG_REQUIRE(dy_bf16 && x && dw && ws, "conv1d_bwd_weight_bias_bf16_ncl: null pointer");

@@ -49,6 +49,7 @@ SIGNATURES = {
     "ecg_bn_relu_pool_bwd_h": (_i, [_vp, _i, _vp, _i, _i] + [_vp] * 5 + [_i] + [_vp] * 3 + [_i] * 4 + [_vp]),
     "ecg_conv1d_bwd_data_bf16hh": (_i, [_vp, _i, _vp, _vp, _i] + [_i] * 6 + [_vp]),
     "ecg_conv1d_bf16_tk_supported": (_i, [_i] * 4),
+    "ecg_conv1d_bf16_tk_min_len": (_i, []),
     "ecg_conv1d_bf16_tk_dy_stride": (_i, [_i]),
     "ecg_conv1d_bwd_weight_bf16_ncl_ws_floats": (_sz, [_i] * 6),
     "ecg_conv1d_bwd_weight_bias_bf16_ncl": (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _vp] + [_i] * 6 + [_vp]),

@@ -440,7 +440,8 @@ def block_form(Ci, Co, K, pad, Lin, gap, x_kind, batch_stats, need_grad, need_dx
     conv_block_chain for the block that consumes its output, by WeightPacker for the operands to pack.
       bf16       the mixed-precision training form: batch statistics, a gradient wanted, conv precision "bf16", a pooled row
                  that is not empty, and ecg_conv1d_bf16_supported has the forward (bit 0), the time-on-K weight gradient (bit 2:
-                 K == 15, pad == 7, C_out % 32 == 0) and the input gradient if one is wanted (bit 1)
+                 K == 15, pad == 7, C_out % 32 == 0) and the input gradient if one is wanted (bit 1), and an input row
+                 long enough for that weight gradient (Lin >= ecg_conv1d_bf16_tk_min_len)
       eval_bf16  one launch on bf16 operands: running statistics, no gradient, inference precision "bf16", and the bf16 eval
                  kernel covers the block for this input (bit 0 of its geometry query: bf16 rows, bit 1: fp32 read in place)
       eval       conv + folded BN + ReLU + pool [+ GAP] in one fp32 launch: running statistics, no gradient, a shape it tiles
@@ -448,7 +449,9 @@ def block_form(Ci, Co, K, pad, Lin, gap, x_kind, batch_stats, need_grad, need_dx
     if batch_stats != need_grad:
         return _FP32
     if batch_stats:
-        ok = conv_prec == "bf16" and K <= 15 and Lin + 2 * pad - K + 1 >= 2
+        # (every bf16 block's backward calls the time-on-K weight gradient, which refuses rows shorter than its own bound)
+        ok = (conv_prec == "bf16" and K <= 15 and Lin + 2 * pad - K + 1 >= 2
+              and Lin >= _query("ecg_conv1d_bf16_tk_min_len"))
         sup = _query("ecg_conv1d_bf16_supported", Ci, Co, K, pad) if ok else 0
         return _BF16 if (sup & 1) and (sup & 4) and (not need_dx or (sup & 2)) else _FP32
     if (infer_prec == "bf16" and x_kind != _X_OTHER and K <= 15 and Lin > 0 and (1 if x_kind == _X_BF16 else 2)
@@ -463,12 +466,15 @@ def block_form(Ci, Co, K, pad, Lin, gap, x_kind, batch_stats, need_grad, need_dx
 def _operand_kinds(geo, kind, Lin, batch, need_bwd, dx0, conv_prec, infer_prec):
     """Per conv of a chain ((C_out, C_in, K), pad) the operands its block reads, as (bf16 operands, input-gradient operand):
     block_form asked along the chain as conv_block_chain asks it — `kind` / `Lin`: the input of block 0, `batch`: who uses
-    batch statistics, `dx0`: block 0 owes an input gradient.  Lin None: no chain, every conv alone on the shortest row."""
+    batch statistics, `dx0`: block 0 owes an input gradient.  Lin None: no chain, every conv alone on the shortest row that
+    pools and that the mixed-precision form takes."""
     chain, n, out = Lin is not None, len(geo), []
+    alone = _query("ecg_conv1d_bf16_tk_min_len")
 
     def bf16(i, kind):          # does block i, fed `kind` rows, take a form that reads bf16 operands
         (Co, Ci, K), pad = geo[i]
-        return block_form(Ci, Co, K, pad, Lin if chain else K + 1 - 2 * pad, chain and i == n - 1, kind, batch[i], need_bwd,
+        row = Lin if chain else max(K + 1 - 2 * pad, alone)
+        return block_form(Ci, Co, K, pad, row, chain and i == n - 1, kind, batch[i], need_bwd,
                           need_bwd and (i > 0 or dx0), conv_prec, infer_prec) in _BF16_FORMS
     for i, ((_, _, K), pad) in enumerate(geo):
         out.append((bf16(i, kind), need_bwd and (i > 0 or dx0)))

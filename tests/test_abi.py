@@ -173,6 +173,35 @@ def test_block_form_table(lib):
                 Lin //= 2
 
 
+def test_bf16_form_stops_where_its_weight_gradient_stops(lib):
+    """Every mixed-precision training block's backward calls ecg_conv1d_bwd_weight_bias_bf16_ncl, which refuses input rows
+    shorter than ecg_conv1d_bf16_tk_min_len().  block_form asks that query (no literal on the Python side), so a block with
+    a shorter row runs the fp32 form, the block before it hands over fp32 rows, and the packer packs fp32 operands for it:
+    T = 100 (rows 100 / 50 / 25 / 12) and 127 (.. / 15) end on an fp32 block, T = 128 (.. / 16) is bf16 throughout."""
+    from ecg_hip import functional as F
+    lo = lib.ecg_conv1d_bf16_tk_min_len()
+    assert lo == 16
+    # the entry point itself: L = lo - 1 refused with its message before anything else is looked at, L = lo gets further
+    args = lambda L_: (None, 128, None, 1, 16, None, None, None, 1, 32, 64, L_, 15, 7, None)      # noqa: E731
+    assert lib.ecg_conv1d_bwd_weight_bias_bf16_ncl(*args(lo - 1)) == 1
+    assert b"conv1d_bwd_weight_bias_bf16_ncl: N=1 C_in=32 C_out=64 L=15" in lib.ecg_last_error()
+    assert lib.ecg_conv1d_bwd_weight_bias_bf16_ncl(*args(lo)) == 1 and b"null pointer" in lib.ecg_last_error()
+    ch = (12, 32, 64, 128, 256)
+    geo = tuple(((ch[i + 1], ch[i], 15), 7) for i in range(4))
+    for T, want in ((100, "bf16 bf16 bf16 fp32"), (127, "bf16 bf16 bf16 fp32"), (128, "bf16 bf16 bf16 bf16"),
+                    (31, "bf16 fp32 fp32 fp32"), (15, "fp32 fp32 fp32 fp32")):
+        want, Lin, kind = want.split(), T, F._X_F32
+        for i, form in enumerate(want):
+            assert F.block_form(ch[i], ch[i + 1], 15, 7, Lin, i == 3, kind, True, True, i > 0, "bf16", "fp32") == form, (T, i)
+            assert (Lin >= lo) == (form == "bf16")
+            # the look-ahead of the block before (this block asked with bf16 rows) says the same, so no bf16 rows reach an
+            # fp32 block
+            assert not i or F.block_form(ch[i], ch[i + 1], 15, 7, Lin, i == 3, F._X_BF16, True, True, True, "bf16", "fp32") == form
+            kind, Lin = F._X_BF16 if form == "bf16" else F._X_F32, Lin // 2
+        assert F._operand_kinds(geo, F._X_F32, T, (True,) * 4, True, False, "bf16", "fp32") == \
+            tuple((f == "bf16", i > 0) for i, f in enumerate(want))
+
+
 def test_library_reads_no_environment_and_allocates_nothing():
     """include/ecg_hip.h: "never allocates", "no global mutable state", "reads no environment variable" — checked on the
     dynamic symbol table of the built library (what it would have to import to break the promise)."""

@@ -543,7 +543,9 @@ def test_bf16_mixed_precision_train_step_config5(B, T):
       tensors upstream of it: rel 0.064 ... 0.188, 1-cos 0.002 ... 0.0174 -> 0.25 / 0.025.  These are NOT rounding of sums:
       a bf16 y (eps 2^-8) flips ~0.3 % of the ReLU / pooling decisions, each flip moves one dY element, and the relative
       error of a gradient grows like sqrt(2 x fraction flipped) ~ 0.08 per block (0.07 / 0.11 / 0.14 / 0.157 from block 3
-      down at the full size) — the price of bf16 activations, the same with fp32 storage of y (0.093 ... 0.14)."""
+      down at the full size) — the price of bf16 activations, the same with fp32 storage of y (0.093 ... 0.14).
+    What bars this wide cannot see (a dropped pooled column, statistics of the unrounded y, a stride or hand-over the glue
+    gets wrong) is pinned stage by stage, at fp32-level bars, by tests/test_gpu_bf16_block_chain.py."""
     from ecg_hip import functional as hipF
     from src.models.ecg_cnn import ECGCNN
     from src.utils.seed import set_seed
