@@ -700,6 +700,75 @@ enum {
 int ecg_beats_rhythm(const int *beats, const int *n_beats, long long *out, int R, int Ttot, int cap,
                      int T, int first, int hop, int W, int last_start, int up, int down, int Tq, int nn_delta,
                      ecg_stream_t stream);
+/* Beat morphology: three gather-reductions over (beat x offset x lead) of the same int16 stream d [R][Ttot][leads], read
+ * in place (2-byte aligned only), driven by a list of positions on the SOURCE axis — the beat list above, or that list
+ * moved by the lags of ecg_beats_match.  Shared by the three entry points:
+ *     pos [R][cap] int32, n [R] int32, include [R][cap] uint8 or NULL (NULL: all ones).  Entry i of recording r is LISTED
+ *     iff i < n[r], pos[r][i] >= 0 and include[r][i] != 0.  Positions need not be ascending or distinct.
+ *     A sample is VALID iff it is not -32768.
+ *     The SEGMENT of a position x is the source samples [x - pre, x + post], Lseg = pre + post + 1 of them; it is WHOLE
+ *     iff x - pre >= 0 and x + post < Ttot.
+ * Row r depends on recording r only.  No byte outside the stream is loaded.  No host synchronisation.  The library
+ * allocates nothing.  ECG_EINVAL before any launch — the integer limits first, so they can be asked with NULL pointers:
+ * R < 1, leads outside [1,16], pre < 0, post < 0, Lseg outside [1,1024], Ttot outside [1,2^30], cap < 1, J outside
+ * [0,64], up or down outside [1,512], K outside [1,65535], Tx < 1, no bit of lead_mask below `leads`; then a NULL
+ * pointer (include may be NULL) or a workspace off 4 bytes.
+ *
+ * ecg_beats_sum — the ensemble sums.  sum [R][Lseg][leads] int64 and cnt [R][Lseg][leads] int32, the stream's own
+ * interleaved layout.  Over every listed entry with a whole segment and every (t, l) whose sample v = v_l[x - pre + t] is
+ * valid:  sum[r][t][l] += v,  cnt[r][t][l] += 1.  Integers only: any split over the beats gives the one right answer.  The
+ * entry point clears both outputs itself on the stream, then adds with integer atomics.  |sum| <= 2^30 * 2^15.
+ *
+ * ecg_beats_match — the best lag against a template, and per-beat integers at that lag.  tmpl [R][Lseg][leads] int16,
+ * -32768 meaning "no value here".  For listed entry i at x the CANDIDATE lags are the j in [-J, J] for which x + j has a
+ * whole segment, and
+ *     score(j) = sum over the leads l in lead_mask (its bits below `leads`), sum over t in [0, Lseg), of
+ *                v_l[x + j - pre + t] * tmpl[r][t][l]  over the pairs where both are valid            (int64)
+ * The chosen lag is the first of the maximal scores scanning j ascending from -J (a later one replaces only when strictly
+ * greater).  lag [R][cap] int32 receives it, and m [R][cap][leads][ECG_BM_FIELDS] int64 receives, at the chosen lag and
+ * for EVERY lead (in lead_mask or not), over the pairs (v, t) = (v_l[x + lag - pre + k], tmpl[r][k][l]) where both are valid:
+ *     ECG_BM_N  their count    ECG_BM_SUM_V  sum v     ECG_BM_SUM_VV  sum v*v     ECG_BM_SUM_T  sum t
+ *     ECG_BM_SUM_TT  sum t*t   ECG_BM_SUM_VT  sum v*t  ECG_BM_SAD  sum |v - t|
+ * An entry that is not listed, or has no candidate, gets lag 0 and all fields 0.  Every value fits int64 (a score is below
+ * 2^30 * 1024 * 16 = 2^44).  Invalid samples change the NUMBER of terms of score(j) from lag to lag, so they bias the
+ * choice towards lags with more valid pairs of the right sign; nothing corrects for that — ECG_BM_N at the chosen lag is
+ * reported so that a caller can see it.
+ *
+ * ecg_beats_series_mean — the beat-locked mean of fp32 series that live on a related axis.  x [R][K][Tx] fp32 (4-byte
+ * aligned, lead-major: what ecg_windows_overlap_mean and ecg_fir_windows write).  Source sample s maps to series sample
+ *     j(s) = min(Tx - 1, floor(s * up / down))                                           (64-bit; the floor rule of a_w)
+ * out [R][K][Lseg] fp32 and count [R] int32: count[r] is the number of TAKING-PART entries — listed, with a whole segment
+ * on the source axis of Ttot samples.  The list of `cap` entries is cut into consecutive slabs of ecg_beats_slab() entries
+ * (slab b holds entries [b*slab, (b+1)*slab)); for every (r, k, t):
+ *     partial_b = 0.0f;  for the taking-part entries i of slab b ascending:  partial_b = partial_b + x[r][k][j(pos[r][i] - pre + t)]
+ *     total = 0.0f;      for b ascending:  total = total + partial_b
+ *     out[r][k][t] = total / (float)count[r]        (0 where count[r] == 0)
+ * every add separately rounded fp32, one division.  (A slab without a taking-part entry adds +0.0f, which changes no bit of
+ * a total that started at +0.0f: how many trailing slabs are visited shows in nothing.)  No atomics: reproducible bit for
+ * bit.  A NaN reaches exactly the outputs whose sum touches it.  `workspace` (4-byte aligned,
+ * ecg_beats_series_mean_workspace_bytes(R, K, cap, Lseg) bytes, 0 for sizes the call would refuse) is the caller's and holds
+ * the slab partials and slab counts between the two launches; its contents afterwards are unspecified. */
+enum {
+    ECG_BM_N = 0,
+    ECG_BM_SUM_V = 1,
+    ECG_BM_SUM_VV = 2,
+    ECG_BM_SUM_T = 3,
+    ECG_BM_SUM_TT = 4,
+    ECG_BM_SUM_VT = 5,
+    ECG_BM_SAD = 6,
+    ECG_BM_FIELDS = 7
+};
+#define ECG_BEATS_SLAB 64
+int ecg_beats_slab(void);
+int ecg_beats_sum(const int16_t *d, const int *pos, const int *n, const uint8_t *include, long long *sum, int *cnt,
+                  int R, int Ttot, int leads, int cap, int pre, int post, ecg_stream_t stream);
+int ecg_beats_match(const int16_t *d, const int *pos, const int *n, const uint8_t *include, const int16_t *tmpl,
+                    int *lag, long long *m, int R, int Ttot, int leads, int cap, int pre, int post, int J,
+                    int lead_mask, ecg_stream_t stream);
+size_t ecg_beats_series_mean_workspace_bytes(int R, int K, int cap, int Lseg);
+int ecg_beats_series_mean(const float *x, const int *pos, const int *n, const uint8_t *include, float *out, int *count,
+                          void *workspace, int R, int K, int Tx, int Ttot, int cap, int pre, int post, int up, int down,
+                          ecg_stream_t stream);
 /* Per-window time series back onto the recording's axis: v [R][W][K][T] (K series per window, windows placed by the
  * rule above) -> out [R][K][Ttot], the mean over the windows that cover a sample:
  *     acc = 0.0f;  for w ascending with start(w) <= t < start(w)+T:  acc = acc + v[r][w][k][t - start(w)]

@@ -59,11 +59,6 @@ __device__ __forceinline__ int wave_min_i(int v) {
     for (int off = 32; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, kWave));
     return v;
 }
-__device__ __forceinline__ long long wave_sum_ll(long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-    return v;
-}
 // inclusive prefix sum over the lanes of a wave
 __device__ __forceinline__ unsigned wave_scan_u(unsigned v, int lane) {
 #pragma unroll

@@ -61,6 +61,13 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// exact: integer sums have no order (beats.hip, beat_template.hip)
+__device__ __forceinline__ long long wave_sum_ll(long long v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
+    return v;
+}
+
 // BatchNorm affine exactly as every kernel (and the oracle) evaluates it.
 __device__ __forceinline__ float bn_apply1(float y, float mean, float scale, float beta) {
     return __fmaf_rn(y - mean, scale, beta);

@@ -111,6 +111,11 @@ SIGNATURES = {
     "ecg_wfdb16_beats_workspace_bytes": (_sz, [_i, _i, _i]),
     "ecg_wfdb16_beats": (_i, [_vp] * 5 + [_i] * 10 + [_vp]),
     "ecg_beats_rhythm": (_i, [_vp] * 3 + [_i] * 12 + [_vp]),
+    "ecg_beats_slab": (_i, []),
+    "ecg_beats_sum": (_i, [_vp] * 6 + [_i] * 6 + [_vp]),
+    "ecg_beats_match": (_i, [_vp] * 7 + [_i] * 8 + [_vp]),
+    "ecg_beats_series_mean_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "ecg_beats_series_mean": (_i, [_vp] * 7 + [_i] * 9 + [_vp]),
     "ecg_windows_overlap_mean": (_i, [_vp] * 3 + [_i] * 8 + [_vp]),
     "ecg_host_gather_rows": (_i, [_vp, _sz, _vp, _i, _vp]),
 }

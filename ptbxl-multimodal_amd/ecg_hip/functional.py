@@ -870,6 +870,7 @@ def sigmoid(x):
 
 
 from .leaves import BatchNormFn, Conv1dFn, FilmFn, GapFn, LinearFn, MaxPool2Fn, ReLUFn  # noqa: E402,F401
-from .input_step import (_fir_call, _resampled_call, beats_rhythm, fir_filter, fir_windows, overlap_mean,  # noqa: E402,F401
-                         wfdb16_beats, wfdb16_quality, wfdb16_to_windows, wfdb16_to_windows_sliding, wfdb16_windows,
-                         wfdb16_windows_resampled, wfdb_decode16, zscore_per_lead)
+from .input_step import (_fir_call, _resampled_call, beats_match, beats_rhythm, beats_series_mean,  # noqa: E402,F401
+                         beats_sum, fir_filter, fir_windows, overlap_mean, wfdb16_beats, wfdb16_quality,
+                         wfdb16_to_windows, wfdb16_to_windows_sliding, wfdb16_windows, wfdb16_windows_resampled,
+                         wfdb_decode16, zscore_per_lead)

@@ -1,6 +1,7 @@
 """The input step: the wrappers over the entry points that turn bytes on disk into the model's windows (WFDB decode,
-DAC conversion, resampling, zero-phase FIR, window cut, per-lead z-score), the quality indices of those windows and the
-overlap mean that brings per-window CAMs back onto the recording's axis.  None of it takes part in autograd.
+DAC conversion, resampling, zero-phase FIR, window cut, per-lead z-score), the quality indices of those windows, the
+beat list, its rhythm table and the beat-morphology reductions, and the overlap mean that brings per-window CAMs back onto
+the recording's axis.  None of it takes part in autograd.
 
 `ecg_hip.functional` re-exports every name of this module at its end and stays the place callers reach them through
 (`functional.wfdb16_windows`, ...).  A wrapper that is built on another one looks it up there as well, so that a
@@ -257,6 +258,91 @@ def beats_rhythm(beats, n_beats, Ttot, window, first, hop, W, last_start=-1, up=
           int(first), int(hop), int(W), int(last_start), int(up), int(down), source_span(window, Ttot, up, down),
           int(nn_delta), _st())
     return out
+
+
+def _beat_list(who, ref, pos, n, include):
+    """The one check of a position list pos int32 [R, cap], n int32 [R], include uint8 / bool [R, cap] or None, all on the
+    device of `ref` -> contiguous (pos, n, include as uint8 or None)."""
+    for name, t, dt in (("pos", pos, torch.int32), ("n", n, torch.int32)):
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise L.EcgHipError(f"{who}: a CPU tensor reached the HIP input step; {name} must be on the GPU")
+        if t.dtype != dt:
+            raise L.EcgHipError(f"{who}: {name} must be int32, got {t.dtype}")
+    R = ref.shape[0]
+    if pos.dim() != 2 or pos.shape[0] != R or tuple(n.shape) != (R,):
+        raise L.EcgHipError(f"{who}: pos must be [R={R}, cap] and n [R]")
+    if include is not None:
+        if not (torch.is_tensor(include) and include.is_cuda):
+            raise L.EcgHipError(f"{who}: a CPU tensor reached the HIP input step; include must be on the GPU")
+        if include.dtype == torch.bool:
+            include = include.to(torch.uint8)
+        if include.dtype != torch.uint8 or tuple(include.shape) != tuple(pos.shape):
+            raise L.EcgHipError(f"{who}: include must be uint8 or bool [R, cap] like pos")
+        include = _contig(include)
+    return _contig(pos), _contig(n), include
+
+
+def beats_sum(d, pos, n, pre, post, include=None):
+    """The ensemble sums of the segments [x - pre, x + post] of d int16 [R, Ttot, leads] at the listed positions x (pos
+    int32 [R, cap], the first n[r] of a row, >= 0, include != 0 where given; functional.wfdb16_beats' outputs are such a
+    list) by ecg_beats_sum: -> (sum int64 [R, Lseg, leads], cnt int32 [R, Lseg, leads]), over the listed entries whose
+    segment lies wholly inside the recording and the samples that are not -32768.  Exact integers."""
+    d, _, _ = _raw_stream("beats_sum", d)
+    pos, n, include = _beat_list("beats_sum", d, pos, n, include)
+    R, Ttot, leads = d.shape
+    Lseg = max(int(pre) + int(post) + 1, 0)
+    s = torch.empty(R, Lseg, leads, dtype=torch.int64, device=d.device)
+    c = torch.empty(R, Lseg, leads, dtype=torch.int32, device=d.device)
+    _call("ecg_beats_sum", L.ptr(d), L.ptr(pos), L.ptr(n), L.ptr(include), L.ptr(s), L.ptr(c), R, Ttot, leads, pos.shape[1],
+          int(pre), int(post), _st())
+    return s, c
+
+
+def beats_match(d, pos, n, tmpl, pre, post, J, lead_mask=None, include=None):
+    """The best lag in [-J, J] of every listed position against tmpl int16 [R, Lseg, leads] (-32768: no value) by
+    ecg_beats_match: -> (lag int32 [R, cap], m int64 [R, cap, leads, 7]), the fields of ecg_hip.template.FIELDS at the
+    chosen lag for every lead.  The score is the integer dot product over the leads of lead_mask (None: every lead); the
+    first of equal maxima wins, scanning from -J.  An entry that is not listed or has no lag with a whole segment gets
+    lag 0 and zeros."""
+    d, _, _ = _raw_stream("beats_match", d)
+    pos, n, include = _beat_list("beats_match", d, pos, n, include)
+    R, Ttot, leads = d.shape
+    cap = pos.shape[1]
+    Lseg = max(int(pre) + int(post) + 1, 0)
+    if not (torch.is_tensor(tmpl) and tmpl.is_cuda):
+        raise L.EcgHipError("beats_match: a CPU tensor reached the HIP input step; tmpl must be on the GPU")
+    if tmpl.dtype != torch.int16 or tuple(tmpl.shape) != (R, Lseg, leads):
+        raise L.EcgHipError(f"beats_match: tmpl must be int16 [R, Lseg={Lseg}, leads], got {tmpl.dtype} {tuple(tmpl.shape)}")
+    mask = (1 << leads) - 1 if lead_mask is None else int(lead_mask)
+    lag = torch.empty(R, cap, dtype=torch.int32, device=d.device)
+    m = torch.empty(R, cap, leads, 7, dtype=torch.int64, device=d.device)
+    _call("ecg_beats_match", L.ptr(d), L.ptr(pos), L.ptr(n), L.ptr(include), L.ptr(_contig(tmpl)), L.ptr(lag), L.ptr(m), R,
+          Ttot, leads, cap, int(pre), int(post), int(J), mask, _st())
+    return lag, m
+
+
+def beats_series_mean(x, pos, n, Ttot, pre, post, up=1, down=1, include=None):
+    """The beat-locked mean of the series x fp32 [R, K, Tx] by ecg_beats_series_mean (two launches, no atomics): ->
+    (out fp32 [R, K, Lseg], count int32 [R]).  The positions are on the SOURCE axis of Ttot samples; source sample s reads
+    series sample min(Tx - 1, s*up // down).  Entries are added in list order inside slabs of template.slab() entries and
+    the slab partials ascending, then divided once by the count of listed entries with a whole segment (0 where none).
+    Allocates the outputs and the workspace."""
+    if not (torch.is_tensor(x) and x.is_cuda):
+        raise L.EcgHipError("beats_series_mean: a CPU tensor reached the HIP input step; x must be on the GPU")
+    if x.dtype != torch.float32 or x.dim() != 3:
+        raise L.EcgHipError(f"beats_series_mean: x must be float32 [R, K, Tx], got {x.dtype} {tuple(x.shape)}")
+    pos, n, include = _beat_list("beats_series_mean", x, pos, n, include)
+    x = _contig(x)
+    R, K, Tx = x.shape
+    cap = pos.shape[1]
+    Lseg = max(int(pre) + int(post) + 1, 0)
+    out = _empty(x, R, K, Lseg)
+    count = torch.empty(R, dtype=torch.int32, device=x.device)
+    nbytes = int(L.query("ecg_beats_series_mean_workspace_bytes", R, K, cap, Lseg))
+    ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=x.device)
+    _call("ecg_beats_series_mean", _f32(x), L.ptr(pos), L.ptr(n), L.ptr(include), _f32(out), L.ptr(count), L.ptr(ws), R, K,
+          Tx, int(Ttot), cap, int(pre), int(post), int(up), int(down), _st())
+    return out, count
 
 
 def overlap_mean(v, plan, Ttot, return_cover=False):

@@ -24,6 +24,14 @@ raw int16 stream in one launch of `ecg_wfdb16_quality` and keeps the windows it 
 
 A probability says nothing about where the beats are.  `beats=` (ecg_hip/beats.py) runs an integer QRS detector over the
 raw stream (`ecg_wfdb16_beats`) and `ecg_beats_rhythm` gives every window its beat count and RR statistics, on the device.
+
+A beat list says nothing about what the beats look like.  `template=` (ecg_hip/template.py) aligns every beat to a centred
+mean template (`ecg_beats_sum`, `ecg_beats_match`: best lag within +-30 ms, two passes), gives every beat its correlation
+with that template and a verdict, adds up the mean beat of the beats that pass over a display range, and — with CAMs —
+averages the stitched CAM beat-locked (`ecg_beats_series_mean`): where in the beat the model looks.  The aligned positions
+are slope-sum peaks moved onto a common phase of the mean beat, NOT R apices; the CAM lives on the model-rate axis, so on a
+downsampled recording (down > up) cam_beat is a staircase in source samples — that is the CAM's own resolution; and the
+spec's defaults are policy, not measurements.
 """
 import torch
 
@@ -74,9 +82,18 @@ class RecordingScore:
     With quality=: quality int64 [R, W, leads, 10] (quality.FIELDS, on the source axis), lead_ok [R, W, leads] and
     usable [R, W]; prob_max / prob_mean are then over the windows that are finite AND usable.  None otherwise.
     With beats=: beats int32 [R, cap] (beat samples on the SOURCE axis, ascending, -1 from n_beats[r] on), n_beats int32
-    [R], rhythm int64 [R, W, 8] (beats.FIELDS) and heart_rate float64 [R, W] in bpm (NaN under 2 beats).  None otherwise."""
+    [R], rhythm int64 [R, W, 8] (beats.FIELDS) and heart_rate float64 [R, W] in bpm (NaN under 2 beats).  None otherwise.
+    With template= (all on the SOURCE axis, [R, cap] rows aligned with beats): beat_lag int32, the lag of every beat against
+    the centred mean template of the last pass; beat_pos int32 = beats + beat_lag (-1 where beats is); beat_corr float64, the
+    lower median over the leads of the beat's correlation with that template (NaN where there is none); beat_ok bool,
+    beat_corr >= min_corr; template float64 mV [R, L, leads], the mean of the ok beats over the display range at beat_pos (NaN
+    where template_n is 0), template_n int32 [R, L, leads] the samples averaged, template_offsets the L sample offsets
+    -pre .. post from beat_pos (a tuple; divide by the source rate for seconds); with CAMs also cam_beat fp32 [R, K, L], the
+    mean of cam at those offsets over the ok beats whose range lies on covered samples, and cam_beat_n int32 [R] their
+    number.  None otherwise."""
     __slots__ = ("starts", "logits", "prob", "finite", "prob_max", "prob_mean", "cam", "cover", "fs", "source_len",
-                 "quality", "lead_ok", "usable", "beats", "n_beats", "rhythm", "heart_rate")
+                 "quality", "lead_ok", "usable", "beats", "n_beats", "rhythm", "heart_rate", "beat_pos", "beat_lag", "beat_ok",
+                 "beat_corr", "template", "template_n", "template_offsets", "cam_beat", "cam_beat_n")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -155,6 +172,55 @@ def _beat_stage(beats, d, gain, window, plan, ratio, fs, source_len):
     return b, n, rhythm, heart_rate(rhythm, fs)        # summarize(rhythm, fs)["heart_rate"]
 
 
+def _template_spec(template, beats, fs):
+    """-> the TemplateSpec of template= (None: no stage); the argument errors of the stage, before anything is launched."""
+    if template is None or template is False:
+        return None
+    from .template import TemplateSpec
+    spec = TemplateSpec() if template is True else template
+    if not isinstance(spec, TemplateSpec):
+        raise ValueError(f"template={template!r}: a TemplateSpec, True or None")
+    if beats is None or beats is False:
+        raise ValueError("template=: the stage works on the beat list and needs beats=")
+    if fs is None:
+        raise ValueError("template=: the spec's parameters are in seconds and need the sampling rate fs of the source stream")
+    return spec
+
+
+def _template_stage(spec, d, gain, baseline, beats, n_beats, fs, cam, cover, ratio):
+    """-> dict of the RecordingScore fields of template= from the beat list (beats, n_beats) of d.  `passes` rounds of
+    beats_sum over the match range at the current positions, the centred mean template, and beats_match at the ORIGINAL
+    beats; then beats_sum over the display range at the aligned positions and — with cam [R, K, Tx] and its cover — ONE
+    beats_series_mean of the ok beats whose mapped range touches no uncovered sample.  Everything between the launches is
+    torch ops on the device."""
+    from . import template as T
+    p = spec.params(fs)
+    R, Ttot, leads = d.shape
+    mask = spec.lead_mask(leads)
+    pos, ok, lag, corr = beats, None, None, None
+    for _ in range(max(1, int(spec.passes))):
+        s, c = hipF.beats_sum(d, pos, n_beats, p["match_pre"], p["match_post"], include=ok)
+        tm = T.mean_template(s, c, centre=True)
+        lag, m = hipF.beats_match(d, beats, n_beats, tm, p["match_pre"], p["match_post"], p["J"], lead_mask=mask)
+        corr = T.beat_correlation(m, mask)
+        pos, ok = beats + lag, corr >= spec.min_corr
+    s, c = hipF.beats_sum(d, pos, n_beats, p["pre"], p["post"], include=ok)
+    out = dict(beat_pos=pos, beat_lag=lag, beat_ok=ok, beat_corr=corr, template_n=c,
+               template=T.physical(T.mean_template(s, c), gain, baseline),
+               template_offsets=tuple(range(-p["pre"], p["post"] + 1)))
+    if cam is not None:
+        up, down = ratio or (1, 1)
+        Tx = cam.shape[-1]
+        x = pos.to(torch.int64)
+        lo = torch.clamp(torch.clamp(x - p["pre"], min=0) * up // down, max=Tx - 1)
+        hi = torch.clamp(torch.clamp(x + p["post"], min=0) * up // down, max=Tx - 1)
+        holes = torch.cat([cover.new_zeros(1, dtype=torch.int64), (cover == 0).to(torch.int64).cumsum(0)])
+        inc = ok & (holes[hi + 1] == holes[lo])
+        out["cam_beat"], out["cam_beat_n"] = hipF.beats_series_mean(cam, pos, n_beats, Ttot, p["pre"], p["post"], up, down,
+                                                                    include=inc)
+    return out
+
+
 def _normalize_per_record(cam, cover):
     """cam_normalize="record": min-max of every (recording, class) row of cam [R, K, Ttot] over its covered samples
     (cover > 0), divided only where the maximum is > 0; 0 where nothing covers."""
@@ -168,7 +234,7 @@ def _normalize_per_record(cam, cover):
 
 def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift", batch_size=256, x_demo=None,
                     cam_classes=None, cam_normalize=None, fs=None, model_fs=None, filter=None, quality=None, rails=None,
-                    beats=None):
+                    beats=None, template=None):
     """Score recordings d int16 [Ttot, leads] or [R, Ttot, leads] (on the GPU, the .dat layout) with `model` in eval mode.
 
     gain float64 / baseline int32 [leads] or [R, leads]; window: samples per model input; hop: default window // 2;
@@ -216,6 +282,17 @@ def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift",
     launch takes the table of every window of the plan, mapped onto the source samples by up/down as for quality=.  The
     score gains beats, n_beats (source-axis sample indices; they are not mapped onto the model-rate axis), rhythm and
     heart_rate (beats.summarize).  Every other output is untouched.  None (default): nothing is launched.
+
+    template: an ecg_hip.template.TemplateSpec, or True for TemplateSpec() (its defaults are policy, not measurements);
+    needs beats= and fs (ValueError otherwise).  After the beats: `passes` rounds of functional.beats_sum over the match
+    range, the centred mean template (template.mean_template) and functional.beats_match at the original beats give every
+    beat its lag, its correlation and its verdict; one more beats_sum over the display range gives the mean beat of the
+    beats that passed; with cam_classes, functional.beats_series_mean averages the stitched cam (as returned, so after
+    cam_normalize) beat-locked, mapped by up/down, over the ok beats whose range [pos - pre, pos + post] maps onto covered
+    samples only.  All on the RAW stream and the SOURCE axis, like the beats.  The positions are aligned slope-sum peaks,
+    not R apices; on a downsampled recording cam_beat is a staircase in source samples, the CAM's own resolution.  The
+    score gains beat_pos, beat_lag, beat_ok, beat_corr, template, template_n, template_offsets, cam_beat and cam_beat_n
+    (RecordingScore).  Every other output is untouched.  None (default): nothing is launched.
     -> RecordingScore."""
     if not (torch.is_tensor(d) and d.is_cuda):
         raise L.EcgHipError("score_recording: a CPU tensor reached the HIP input step; d must be on the GPU "
@@ -253,6 +330,7 @@ def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift",
         axis_fs = fs if ratio is None else model_fs
         taps = one_sided(filter.taps(axis_fs) if isinstance(filter, FilterSpec) else filter)
     cams = None if cam_classes is None else [int(k) for k in cam_classes]
+    tspec = _template_spec(template, beats, fs)
     d = hipF._contig(d)
     qtab, lead_ok, usable = _quality_gate(quality, d, gain, rails, window, plan, ratio, fs, source_len)
     beat_list, n_beats, rhythm, heart_rate = _beat_stage(beats, d, gain, window, plan, ratio, fs, source_len)
@@ -287,10 +365,11 @@ def score_recording(model, d, gain, baseline, *, window, hop=None, tail="shift",
         cam, cover = hipF.overlap_mean(v, plan, Ttot, return_cover=True)
         if cam_normalize == "record":
             cam = _normalize_per_record(cam, cover)
+    morph = {} if tspec is None else _template_stage(tspec, d, gain, baseline, beat_list, n_beats, fs, cam, cover, ratio)
     return RecordingScore(starts=starts, logits=logits, prob=prob, finite=finite, prob_max=pmax, prob_mean=pmean,
                           cam=cam, cover=cover, fs=fs if ratio is None else model_fs, source_len=source_len,
                           quality=qtab, lead_ok=lead_ok, usable=usable, beats=beat_list, n_beats=n_beats, rhythm=rhythm,
-                          heart_rate=heart_rate)
+                          heart_rate=heart_rate, **morph)
 
 
 def score_wfdb_record(record_path, model, model_fs=None, leads=None, **kw):
@@ -300,7 +379,7 @@ def score_wfdb_record(record_path, model, model_fs=None, leads=None, **kw):
     through: a FilterSpec is designed at model_fs when the record is resampled, otherwise at the header's rate.
     quality= is passed through too, with the ADC rails of the selected leads (quality.rails_from_header: adc_res and
     adc_zero of the header, or the storage format's range) unless the caller gives rails= itself.  beats= is passed
-    through as well and detects at the header's rate.
+    through as well and detects at the header's rate; template= likewise.
 
     leads: the signals to score, in the model's lead order — names matched against the header's descriptions (e.g.
     wfdbraw.PTBXL_LEADS for a 15-signal PTB Diagnostic record) or signal indices; None: every signal, in header order.

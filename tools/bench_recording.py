@@ -2,7 +2,7 @@
 score_recording end to end.
 
     python tools/bench_recording.py [--hours 1] [--rounds 7] [--iters 20] [--out profiles/recording_bench.json]
-                                    [--legs recording,resample,filter,decode,quality,beats]
+                                    [--legs recording,resample,filter,decode,quality,beats,template]
                                     [--resample-out profiles/resample_bench.json]
 
 Workloads: one 12-lead recording of --hours at 500 Hz (window 5000) and at 100 Hz (window 1000), hop = window / 2.
@@ -59,6 +59,16 @@ Leg "beats" (not in the default --legs): beat detection and the rhythm table on 
                nonzero for the list (checked equal to the kernel's list; no table)
   (p) score    score_recording with beats=True against the same call without it (fp32, no CAMs): what the stage adds
 alternating in one process like the others.  Written into --out under "beats".
+
+Leg "template" (not in the default --legs): beat morphology on the same one-hour recordings and their device-made beat
+lists, TemplateSpec() defaults.
+  (q) kernels  functional.beats_sum over the display range, functional.beats_match over the match range against the centred
+               mean template, functional.beats_series_mean of five fp32 series on the recording's own axis; beats_sum is
+               also rated against the bytes it must read (the whole segments, 2 B a sample, and the list)
+  (r) torch    the same sums in torch tensor ops on the device: an index tensor [beats][Lseg], a gather of the segments
+               and a masked sum (the integer sums checked equal to the kernel's; the fp32 mean adds in another order)
+  (s) score    score_recording with beats=True, template=True against beats=True alone (fp32, no CAMs)
+alternating in one process like the others.  Written into --out under "template".
 Fails when no GPU is visible: no number here means anything on a CPU.
 """
 import argparse
@@ -481,6 +491,22 @@ def beats_torch(d, s, h, ref, blk, num, den, g_min):
     return torch.nonzero((g >= thr[n // blk]) & (gd > left) & (gd >= right))[:, 0]
 
 
+def _pulse_recording(a, fs):
+    """-> (d int16 [1, Ttot, LEADS], gain, baseline) on the device: R-like pulses (sigma 12 ms, 0.3-1.5 mV, a sign per lead)
+    every 0.7-0.9 s in 0.02 mV of noise, 1000 counts per mV."""
+    Ttot = int(a.hours * 3600 * fs)
+    rng = np.random.default_rng(fs + 3)
+    at = np.cumsum(rng.uniform(0.7, 0.9, size=int(a.hours * 3600 / 0.7)) * fs).astype(np.int64)
+    train = np.zeros(Ttot)
+    train[at[at < Ttot - fs]] = 1.0
+    k = np.arange(-int(0.06 * fs), int(0.06 * fs) + 1)
+    shape = np.convolve(train, np.exp(-0.5 * (k / (0.012 * fs)) ** 2), mode="same")
+    amp = rng.choice([-1.0, 1.0], size=LEADS) * rng.uniform(300, 1500, size=LEADS)
+    x = shape[:, None] * amp[None, :] + 20.0 * rng.standard_normal((Ttot, LEADS))
+    d = torch.from_numpy(np.round(x).astype(np.int16)[None]).cuda()
+    return d, torch.full((1, LEADS), 1000.0, dtype=torch.float64).cuda(), torch.zeros(1, LEADS, dtype=torch.int32).cuda()
+
+
 def beats_leg(a):
     """ecg_wfdb16_beats + ecg_beats_rhythm against the same detector in torch ops, and what beats= adds to score_recording."""
     from ecg_hip import functional as F
@@ -491,18 +517,7 @@ def beats_leg(a):
     res = []
     for fs, window in ((100, 1000), (500, 5000)):
         Ttot, hop = int(a.hours * 3600 * fs), window // 2
-        rng = np.random.default_rng(fs + 3)
-        # R-like pulses (sigma 12 ms, 0.3-1.5 mV, a sign per lead) every 0.7-0.9 s in 0.02 mV of noise, 1000 counts per mV
-        at = np.cumsum(rng.uniform(0.7, 0.9, size=int(a.hours * 3600 / 0.7)) * fs).astype(np.int64)
-        train = np.zeros(Ttot)
-        train[at[at < Ttot - fs]] = 1.0
-        k = np.arange(-int(0.06 * fs), int(0.06 * fs) + 1)
-        shape = np.convolve(train, np.exp(-0.5 * (k / (0.012 * fs)) ** 2), mode="same")
-        amp = rng.choice([-1.0, 1.0], size=LEADS) * rng.uniform(300, 1500, size=LEADS)
-        x = shape[:, None] * amp[None, :] + 20.0 * rng.standard_normal((Ttot, LEADS))
-        d = torch.from_numpy(np.round(x).astype(np.int16)[None]).cuda()
-        gain = torch.full((1, LEADS), 1000.0, dtype=torch.float64).cuda()
-        base = torch.zeros(1, LEADS, dtype=torch.int32).cuda()
+        d, gain, base = _pulse_recording(a, fs)
         p = BeatSpec().params(fs, gain)
         g_min = p["g_min"].cuda()
         first, hop, W, last, _ = window_plan(Ttot, window, hop)
@@ -550,12 +565,94 @@ def beats_leg(a):
     return res
 
 
-_SECTIONS = ("filter", "decode", "quality", "beats")
+def template_leg(a):
+    """ecg_beats_sum / ecg_beats_match / ecg_beats_series_mean, the sums in torch ops, and what template= adds to
+    score_recording with beats=True."""
+    from ecg_hip import functional as F
+    from ecg_hip import template as T
+    from ecg_hip.beats import BeatSpec
+    from ecg_hip.recording import score_recording
+    from src.models.ecg_cnn import ECGCNN
+    from src.utils.seed import set_seed
+    res, K = [], 5
+    for fs, window in ((100, 1000), (500, 5000)):
+        Ttot, hop = int(a.hours * 3600 * fs), window // 2
+        d, gain, base = _pulse_recording(a, fs)
+        bp = BeatSpec().params(fs, gain)
+        b, n = F.wfdb16_beats(d, bp["s"], bp["h"], bp["ref"], bp["blk"], bp["num"], bp["den"], bp["g_min"].cuda())
+        p = T.TemplateSpec().params(fs)
+        pre, post, L = p["pre"], p["post"], p["pre"] + p["post"] + 1
+        tm = T.mean_template(*F.beats_sum(d, b, n, p["match_pre"], p["match_post"]), centre=True)
+        series = torch.randn(1, K, Ttot, device="cuda")
+        set_seed(42)
+        model = ECGCNN(num_labels=5).cuda().eval()
+        cap = b.shape[1]
+        x = b[0].long()
+        whole = (torch.arange(cap, device="cuda") < n[0]) & (x - pre >= 0) & (x + post < Ttot)
+        t = torch.arange(L, device="cuda")
+
+        def sums():
+            return F.beats_sum(d, b, n, pre, post)
+
+        def match():
+            return F.beats_match(d, b, n, tm, p["match_pre"], p["match_post"], p["J"])
+
+        def mean():
+            return F.beats_series_mean(series, b, n, Ttot, pre, post)
+
+        def sums_torch():
+            idx = (x[:, None] - pre + t[None, :]).clamp(0, Ttot - 1)            # the index tensor [beats][Lseg]
+            seg = d[0][idx]                                                     # [beats][Lseg][leads]
+            valid = (seg != -32768) & whole[:, None, None]
+            return torch.where(valid, seg, torch.zeros_like(seg)).sum(0, dtype=torch.int64), valid.sum(0, dtype=torch.int32)
+
+        def mean_torch():
+            idx = (x[:, None] - pre + t[None, :]).clamp(0, Ttot - 1)
+            seg = series[0][:, idx] * whole[None, :, None]                      # [K][beats][Lseg]
+            return seg.sum(1) / whole.sum()
+
+        def score(tp):
+            return score_recording(model, d, gain, base, window=window, hop=hop, batch_size=a.batch, fs=fs, beats=True,
+                                   template=tp).prob_max
+
+        (s1, c1), (s2, c2) = sums(), sums_torch()
+        assert torch.equal(s1[0], s2) and torch.equal(c1[0], c2)
+        assert torch.allclose(mean()[0][0], mean_torch(), rtol=1e-3, atol=1e-3)
+        taking = int(whole.sum())
+        print(f"template leg: {fs} Hz, Ttot {Ttot}, {int(n[0])} beats, Lseg {L}, J {p['J']}", file=sys.stderr, flush=True)
+        big = argparse.Namespace(**{**vars(a), "iters": max(a.iters, 500)})
+        ms, iters = _rounds({"sum": sums, "match": match, "series_mean": mean, "sum_torch": sums_torch,
+                             "series_mean_torch": mean_torch}, big)
+        ms2, iters2 = _rounds({"with_template": lambda: score(True), "beats_only": lambda: score(None)}, a)
+        ms.update(ms2), iters.update(iters2)
+        med = {k: float(np.median(v)) for k, v in ms.items()}
+        must = taking * L * LEADS * 2 + cap * 4
+        line = {"metric": "beats_sum_ms", "value": round(med["sum"], 4), "unit": "ms",
+                "config": {"workload": f"{a.hours:g} h, {LEADS} leads at {fs} Hz (Ttot {Ttot}), {int(n[0])} beats ({taking} with a "
+                                       f"whole segment), TemplateSpec() defaults: display Lseg {L}, match Lseg "
+                                       f"{p['match_pre'] + p['match_post'] + 1}, J {p['J']}; series_mean: {K} fp32 series at ratio 1/1; "
+                                       f"torch: index tensor + gather + masked sum; score_recording: ECGCNN(5), chunks of "
+                                       f"{a.batch}, fp32, no CAMs, beats=True with and without template=True"},
+                **{f"{k}_ms": [round(v_, 4) for v_ in v] for k, v in ms.items()},
+                **{f"{k}_median_ms": round(m, 4) for k, m in med.items()},
+                **{f"{k}_spread_ms": round(max(v) - min(v), 4) for k, v in ms.items()},
+                "calls_per_round": iters, "sum_torch_over_kernel": round(med["sum_torch"] / med["sum"], 3),
+                "series_mean_torch_over_kernel": round(med["series_mean_torch"] / med["series_mean"], 3),
+                "sum_bytes_it_must_read": int(must), "sum_GBps_of_those_bytes": round(must / (med["sum"] * 1e-3) / 1e9, 1),
+                "sum_frac_of_hbm": round(must / (med["sum"] * 1e-3) / HBM_BYTES_PER_S, 4),
+                "with_over_beats_only": round(med["with_template"] / med["beats_only"], 4),
+                "added_ms": round(med["with_template"] - med["beats_only"], 4)}
+        print(json.dumps(line), flush=True)
+        res.append(line)
+    return res
+
+
+_SECTIONS = ("filter", "decode", "quality", "beats", "template")
 
 
 def _write(path, lines=None, **sections):
     """profiles/recording_bench.json: the recording leg's lines, then {"filter": [...]}, {"decode": [...]},
-    {"quality": [...]} and {"beats": [...]}; a leg replaces its own part."""
+    {"quality": [...]}, {"beats": [...]} and {"template": [...]}; a leg replaces its own part."""
     old = []
     if os.path.exists(path):
         with open(path) as f:
@@ -598,6 +695,8 @@ def main():
         _write(a.out, quality=quality_leg(a))
     if "beats" in a.legs.split(","):
         _write(a.out, beats=beats_leg(a))
+    if "template" in a.legs.split(","):
+        _write(a.out, template=template_leg(a))
     if "recording" not in a.legs.split(","):
         return
     res = []
