@@ -777,6 +777,65 @@ int ecg_beats_series_mean(const float *x, const int *pos, const int *n, const ui
  * receives the count.  Same argument checks; R*K <= 65535. */
 int ecg_windows_overlap_mean(const float *v, float *out, float *cover, int R, int K, int T, int Ttot,
                              int first, int hop, int W, int last_start, ecg_stream_t stream);
+/* Epoch-end metrics — replaces the host call of eval_one_epoch (src/training/loop.py:70-72 -> src/training/metrics.py:
+ * roc_auc_score, average_precision_score, f1_score) by exact integers from which AUROC and F1 are one division each,
+ * and by one stated fp64 sum for the average precision.  Inputs, in the layout the loops hold them: prob [N][C] fp32 and
+ * y [N][C] fp32 (labels 0.0 or 1.0), row-major, 4-byte aligned.
+ *     The KEY of a probability is its fp32 value, with -0.0 equal to +0.0 and every NaN equal to every other NaN and below
+ *     -inf.  Keys give a total order.
+ * The library allocates nothing and never synchronises: each call has a caller-owned `workspace` (4-byte aligned,
+ * ecg_metrics_*_workspace_bytes bytes, 0 for sizes the call would refuse; contents afterwards unspecified).
+ *
+ * ecg_metrics_order (two launches) — order [C][N] int32: order[c][r] is the row at rank r of column c in DESCENDING key
+ * order, equal keys by ascending row: a permutation of 0..N-1 for every c.  nonfinite [C] int32: the number of NaN or
+ * +-inf entries of the column.  Obtained by counting, not by sorting: rank_i = #{j: key_j > key_i} + #{j < i: key_j =
+ * key_i}; exact, deterministic, no atomics on memory.
+ * ECG_EINVAL before any launch — the integer limits first, so they can be asked with NULL pointers: N outside
+ * [1, 65536], C outside [1, 64]; then a NULL pointer or a base off 4 bytes.
+ *
+ * ecg_metrics_counts (two launches) — w [B][N] int32 weights >= 0, or NULL (B must then be 1; every weight is 1).  The
+ * caller's precondition, not checked: sum_i w[b][i] < 2^30.  `order` is ecg_metrics_order's output for the same prob (the
+ * caller's word; an entry outside [0, N) is clamped into it, so no byte outside the inputs is read).  Per (b, c):
+ *     Row i is POSITIVE iff y == 1.0f and NEGATIVE iff y == 0.0f; any other label is BAD and is counted in nothing else.
+ *     Walking the ranks r of order[c]: tp(r) and fp(r) are the weighted positives and negatives at ranks <= r; r is a
+ *     GROUP END iff it is the last rank or the key at rank r+1 differs.
+ *   fields [B][C][ECG_MT_FIELDS] int64:
+ *     ECG_MT_POS, ECG_MT_NEG   the weighted positives and negatives
+ *     ECG_MT_U2                sum over (positive i, negative j) of w_i*w_j * (2 if key_i > key_j, 1 if equal, else 0)
+ *     ECG_MT_TP/FP/FN/TN       with "predicted" meaning prob >= threshold compared in fp32 (a NaN is not predicted)
+ *     ECG_MT_NONFINITE         the weight of the positive or negative rows whose prob is NaN or +-inf
+ *     ECG_MT_BAD               the weight of the BAD rows
+ *   ap [B][C] double, in ONE stated order.  For a group end r with the previous group end r', d = tp(r) - tp(r') (tp(r') = 0
+ *     if there is none); if d > 0:   term(r) = ((double)d / (double)POS) * ((double)tp(r) / (double)(tp(r) + fp(r))).
+ *     Ranks are cut into slabs of ECG_METRICS_SLAB consecutive ranks; partial_s starts at 0.0 and adds the terms of the
+ *     group ends inside slab s, ascending; ap starts at 0.0 and adds partial_s for s ascending.  Every operation is a
+ *     separately rounded fp64 one.  POS == 0 gives 0.0.
+ *   curve: NULL, or [B][C][N][2] int32 receiving tp(r), fp(r) at every rank (meaningful at group ends: the points of the
+ *     ROC and precision-recall curves).
+ * AUROC = U2 / (2 * POS * NEG) and F1 = 2TP / (2TP + FP + FN) are left to the caller (ecg_hip/metrics.py).  A bootstrap
+ * replicate is a row of multiplicities in w: one order serves every replicate.
+ * ECG_EINVAL before any launch — the integer limits first: N outside [1, 65536], C outside [1, 64], B outside [1, 65536];
+ * B > 1 with w == NULL; threshold NaN; then a NULL pointer (w and curve may be NULL) or a misaligned base: 8 bytes for
+ * fields and ap, 4 otherwise. */
+enum {
+    ECG_MT_POS = 0,
+    ECG_MT_NEG = 1,
+    ECG_MT_U2 = 2,
+    ECG_MT_TP = 3,
+    ECG_MT_FP = 4,
+    ECG_MT_FN = 5,
+    ECG_MT_TN = 6,
+    ECG_MT_NONFINITE = 7,
+    ECG_MT_BAD = 8,
+    ECG_MT_FIELDS = 9
+};
+#define ECG_METRICS_SLAB 64
+int ecg_metrics_slab(void);
+size_t ecg_metrics_order_workspace_bytes(int N, int C);
+int ecg_metrics_order(const float *prob, int *order, int *nonfinite, void *workspace, int N, int C, ecg_stream_t stream);
+size_t ecg_metrics_counts_workspace_bytes(int N, int C, int B);
+int ecg_metrics_counts(const float *prob, const float *y, const int *order, const int *w, long long *fields, double *ap,
+                       int *curve, void *workspace, int N, int C, int B, float threshold, ecg_stream_t stream);
 /* HOST side of the same step — what torch's DataLoader collate does for the reference (one `Dataset.__getitem__` per record,
  * src/datasets/ptbxl.py:25,122-127, stacked into a batch): rows `rows[0..n)` of a row-major host table (row_bytes each, e.g.
  * the int16 records of a memory-mapped pack) copied to consecutive rows of `dst` (the pinned staging slot).  Plain memcpy

@@ -1,0 +1,366 @@
+// metrics.hip — epoch-end metrics as exact integers: the descending order of every score column, and from it the weighted
+// pair, confusion and precision-recall counts of every (weight row, class).  Definitions: include/ecg_hip.h.
+//
+// The KEY of a probability is a uint32 that orders as the contract says (metrics_key): NaN -> 0, negative values -> ~bits,
+// the others -> bits | 2^31, with -0.0 read as +0.0.  Integer compares of keys are the total order; nothing below compares
+// floats except `prob >= threshold`.
+//
+// ecg_metrics_order, two launches.
+//   keys    prob [N][C] -> keys [C][Np] in the workspace (Np = N rounded up to 4), so that a column is one contiguous
+//           stream that loads 16 bytes at a time.
+//   rank    the counting form: rank_i = #{j: key_j > key_i} + #{j < i: key_j == key_i}.  Workgroup (tile, c) holds the keys
+//           of 256 rows i in registers (one per lane) and streams the column through LDS in tiles of kMtTileJ keys; every
+//           lane reads the SAME 16 bytes (a broadcast ds_read_b128, 4 LDS cycles per wave for 4 keys) and pays one compare
+//           and one add per key, so the vector pipe and not the LDS sets the time.  A tile wholly before the workgroup's
+//           rows counts key_j >= key_i, one wholly after counts key_j > key_i, and only the tile that overlaps them pays
+//           the two-compare form.  No sort, no atomics on global memory, no second pass: rank_i is final when the loop
+//           ends and the lane stores order[c][rank_i] = i.  A rank is a position in a total order, so the stores of a
+//           column hit every slot of [0, N) exactly once.  Workgroup (0, c) also counts the column's non-finite keys.
+//
+// ecg_metrics_counts, two launches.
+//   pack    per (c, rank r): one uint32 = row | flags (positive, negative, group end, predicted, non-finite, valid), in
+//           the workspace.  Everything that does not depend on the weight row is decided here, once.
+//   scan    workgroup (b, c) walks the ranks in chunks of kMtChunk = 256 lanes x 4 consecutive ranks: a 16-byte load of
+//           the packed words, four gathers of w[b][row] (one row of w stays in cache), then
+//             pass 1  the order-free totals (POS, NEG, TP, FP, FN, TN, NONFINITE, BAD);
+//             pass 2  tp(r), fp(r) by one block-wide sum scan of (tp << 32 | fp) — both stay below 2^30, so the halves
+//                     never meet — and the previous group end's (tp, fp) by one block-wide MAX scan of the same word at
+//                     group ends (tp and fp never decrease, so the latest group end is the largest).  A group end then
+//                     gives its share of U2, (fp - fp')(tp + tp'), and its fp64 term of ap.
+//           The terms of a chunk go to LDS; lane s adds slab s of the chunk left to right, lane 0 adds the chunk's slab
+//           partials to ap ascending.  A rank that is no group end, or whose term does not exist, leaves +0.0 there: adding
+//           +0.0 changes no bit of a sum that started at +0.0 and only ever receives positive terms, so the value is the
+//           stated sum over group ends.  No atomics, no fma (the file is built with -ffp-contract=off): one value.
+#include <cmath>
+
+#include "common.h"
+
+namespace ecg {
+
+constexpr int kMtThreads = 256;
+constexpr int kMtItems = 4;                                  // consecutive ranks per lane
+constexpr int kMtChunk = kMtThreads * kMtItems;              // ranks per pass of the scan loop
+constexpr int kMtSlab = ECG_METRICS_SLAB;
+constexpr int kMtChunkSlabs = kMtChunk / kMtSlab;
+constexpr int kMtTileJ = 2048;                               // keys per LDS tile of the rank kernel
+constexpr int kMtMaxN = 65536, kMtMaxC = 64, kMtMaxB = 65536;
+static_assert(kMtChunk % kMtSlab == 0 && kMtChunkSlabs <= kWave, "a chunk is whole slabs, one lane of wave 0 each");
+static_assert(kMtTileJ % (4 * kMtThreads) == 0, "a tile is whole 16-byte loads per lane");
+
+// packed word of (c, rank): the row in the low 16 bits (N <= 65536), flags above
+constexpr unsigned kMtPos = 1u << 16, kMtNeg = 1u << 17, kMtEnd = 1u << 18, kMtPred = 1u << 19, kMtNonfinite = 1u << 20,
+                   kMtValid = 1u << 21;
+
+__host__ __device__ __forceinline__ unsigned metrics_key(float p) {
+    unsigned u = __builtin_bit_cast(unsigned, p);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0u;          // every NaN: one key, below -inf
+    if (u == 0x80000000u) u = 0u;                            // -0.0 is +0.0
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__host__ __device__ __forceinline__ bool metrics_key_nonfinite(unsigned k) {
+    return k == 0u || k == 0xff800000u || k == 0x007fffffu;  // NaN, +inf, -inf
+}
+
+__host__ __device__ __forceinline__ int metrics_padded(int N) { return (N + 3) & ~3; }
+
+// the workspaces hold 16-byte words; the caller owes 4-byte alignment only, the helpers give 16 bytes of slack
+__host__ __forceinline__ unsigned *metrics_ws_base(void *workspace) {
+    return reinterpret_cast<unsigned *>(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
+}
+__host__ __forceinline__ size_t metrics_ws_bytes(int N, int C) { return (size_t)C * metrics_padded(N) * 4 + 16; }
+
+__global__ __launch_bounds__(kMtThreads) void metrics_keys_kernel(const float *__restrict__ prob, unsigned *__restrict__ keys,
+                                                                  int N, int C, int Np) {
+    const int e = blockIdx.x * kMtThreads + threadIdx.x;     // N * C <= 2^22
+    if (e >= N * C) return;
+    const int n = e / C, c = e - n * C;
+    keys[(size_t)c * Np + n] = metrics_key(prob[e]);
+}
+
+__global__ __launch_bounds__(kMtThreads) void metrics_rank_kernel(const unsigned *__restrict__ keys, int *__restrict__ order,
+                                                                  int *__restrict__ nonfinite, int N, int Np) {
+    __shared__ uint4 tile[kMtTileJ / 4];
+    __shared__ int nf_s;
+    const int c = blockIdx.y, tid = threadIdx.x;
+    const unsigned *kc = keys + (size_t)c * Np;
+    const int i0 = blockIdx.x * kMtThreads, i = i0 + tid;
+    const unsigned ki = i < N ? kc[i] : 0u;
+    const bool count_nf = blockIdx.x == 0;
+    if (tid == 0) nf_s = 0;
+    int cnt = 0, nf = 0;
+    for (int j0 = 0; j0 < N; j0 += kMtTileJ) {
+        __syncthreads();                                     // the tile before is consumed
+#pragma unroll
+        for (int q = tid; q < kMtTileJ / 4; q += kMtThreads) {
+            const int j = j0 + 4 * q;
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);            // key 0 is the minimum: it counts in neither form below
+            if (j < N) {                                     // j is a multiple of 4 below Np: the 16 bytes are the workspace's
+                v = *reinterpret_cast<const uint4 *>(kc + j);
+                if (j + 1 >= N) v.y = 0u;                    // the column's padding was never written
+                if (j + 2 >= N) v.z = 0u;
+                if (j + 3 >= N) v.w = 0u;
+                if (count_nf)
+                    nf += (int)metrics_key_nonfinite(v.x) + (int)(j + 1 < N && metrics_key_nonfinite(v.y)) +
+                          (int)(j + 2 < N && metrics_key_nonfinite(v.z)) + (int)(j + 3 < N && metrics_key_nonfinite(v.w));
+            }
+            tile[q] = v;
+        }
+        __syncthreads();
+        const int nq = (min(kMtTileJ, N - j0) + 3) >> 2;
+        if (j0 + kMtTileJ <= i0) {                           // every j of the tile is below every i of the workgroup
+#pragma unroll 4
+            for (int q = 0; q < nq; ++q) {
+                const uint4 v = tile[q];
+                cnt += (int)(v.x >= ki) + (int)(v.y >= ki) + (int)(v.z >= ki) + (int)(v.w >= ki);
+            }
+        } else if (j0 >= i0 + kMtThreads) {                  // every j is above every i
+#pragma unroll 4
+            for (int q = 0; q < nq; ++q) {
+                const uint4 v = tile[q];
+                cnt += (int)(v.x > ki) + (int)(v.y > ki) + (int)(v.z > ki) + (int)(v.w > ki);
+            }
+        } else {
+#pragma unroll 4
+            for (int q = 0; q < nq; ++q) {
+                const uint4 v = tile[q];
+                const int j = j0 + 4 * q;
+                cnt += (int)(v.x > ki || (v.x == ki && j < i)) + (int)(v.y > ki || (v.y == ki && j + 1 < i)) +
+                       (int)(v.z > ki || (v.z == ki && j + 2 < i)) + (int)(v.w > ki || (v.w == ki && j + 3 < i));
+            }
+        }
+    }
+    if (i < N) order[(size_t)c * N + cnt] = i;               // cnt is i's position in a total order of N rows: in [0, N)
+    if (count_nf) {
+        atomicAdd(&nf_s, nf);                                // LDS, integers: one value
+        __syncthreads();
+        if (tid == 0) nonfinite[c] = nf_s;
+    }
+}
+
+__device__ __forceinline__ int metrics_row(const int *__restrict__ order_c, int r, int N) {
+    return (int)min((unsigned)max(order_c[r], 0), (unsigned)(N - 1));   // a bad order reads no byte outside the inputs
+}
+
+__global__ __launch_bounds__(kMtThreads) void metrics_pack_kernel(const float *__restrict__ prob, const float *__restrict__ y,
+                                                                  const int *__restrict__ order, unsigned *__restrict__ packed,
+                                                                  int N, int C, int Np, float threshold) {
+    const int c = blockIdx.y, r = blockIdx.x * kMtThreads + threadIdx.x;
+    if (r >= Np) return;
+    unsigned out = 0u;                                       // the padding of a column: not valid
+    if (r < N) {
+        const int *oc = order + (size_t)c * N;
+        const int row = metrics_row(oc, r, N);
+        const float p = prob[row * C + c], l = y[row * C + c];
+        const unsigned key = metrics_key(p);
+        bool end = r == N - 1;
+        if (!end) end = metrics_key(prob[metrics_row(oc, r + 1, N) * C + c]) != key;
+        out = (unsigned)row | kMtValid | (l == 1.0f ? kMtPos : 0u) | (l == 0.0f ? kMtNeg : 0u) | (end ? kMtEnd : 0u) |
+              (p >= threshold ? kMtPred : 0u) | (metrics_key_nonfinite(key) ? kMtNonfinite : 0u);
+    }
+    packed[(size_t)c * Np + r] = out;
+}
+
+typedef unsigned long long mt_u64;
+
+// exclusive scan of one value per lane over the workgroup, by + or by max; `total` is the value over all lanes.  wtot: one
+// slot per wave, private to the call site (a slot is rewritten only after a later __syncthreads of the caller's loop).
+template <bool kMax>
+__device__ __forceinline__ mt_u64 metrics_block_excl(mt_u64 v, mt_u64 *wtot, mt_u64 &total) {
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    mt_u64 inc = v;
+#pragma unroll
+    for (int off = 1; off < kWave; off <<= 1) {
+        const mt_u64 t = __shfl_up(inc, off, kWave);
+        if (lane >= off) inc = kMax ? max(inc, t) : inc + t;
+    }
+    if (lane == kWave - 1) wtot[wave] = inc;
+    mt_u64 excl = __shfl_up(inc, 1, kWave);
+    if (lane == 0) excl = 0;
+    __syncthreads();
+    mt_u64 pre = 0;
+    total = 0;
+#pragma unroll
+    for (int w = 0; w < kMtThreads / kWave; ++w) {
+        const mt_u64 t = wtot[w];
+        if (w < wave) pre = kMax ? max(pre, t) : pre + t;
+        total = kMax ? max(total, t) : total + t;
+    }
+    return kMax ? max(pre, excl) : pre + excl;
+}
+
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
+    return v;
+}
+
+// the four packed words of lane `tid` in the chunk at r0, and their weights (0 for a word that is not valid)
+__device__ __forceinline__ void metrics_load4(const unsigned *__restrict__ pc, const int *__restrict__ wb, int r0, int Np,
+                                              unsigned pk[kMtItems], int wt[kMtItems]) {
+    const int r = r0 + kMtItems * (int)threadIdx.x;
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (r < Np) v = *reinterpret_cast<const uint4 *>(pc + r);   // r and Np are multiples of 4
+    pk[0] = v.x, pk[1] = v.y, pk[2] = v.z, pk[3] = v.w;
+#pragma unroll
+    for (int k = 0; k < kMtItems; ++k)
+        wt[k] = (pk[k] & kMtValid) ? (wb ? wb[pk[k] & 0xffffu] : 1) : 0;
+}
+
+constexpr int kMtTotals = 8;
+
+__global__ __launch_bounds__(kMtThreads) void metrics_scan_kernel(const unsigned *__restrict__ packed, const int *__restrict__ w,
+                                                                  long long *__restrict__ fields, double *__restrict__ ap_out,
+                                                                  int *__restrict__ curve, int N, int C, int Np) {
+    __shared__ double terms[kMtChunk + kMtChunkSlabs];       // slab s of the chunk starts at s * (kMtSlab + 1): no bank shared
+    __shared__ double part[kMtChunkSlabs];
+    __shared__ mt_u64 wsum[kMtThreads / kWave], wmax[kMtThreads / kWave];
+    __shared__ int tot_s[kMtTotals];
+    const int b = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
+    const unsigned *pc = packed + (size_t)c * Np;
+    const int *wb = w ? w + (size_t)b * N : nullptr;
+    unsigned pk[kMtItems];
+    int wt[kMtItems];
+
+    // ---- pass 1: the totals, in any order
+    int tot[kMtTotals] = {0, 0, 0, 0, 0, 0, 0, 0};           // POS NEG TP FP FN TN NONFINITE BAD; each a part of sum w < 2^30
+    if (tid < kMtTotals) tot_s[tid] = 0;
+    for (int r0 = 0; r0 < N; r0 += kMtChunk) {
+        metrics_load4(pc, wb, r0, Np, pk, wt);
+#pragma unroll
+        for (int k = 0; k < kMtItems; ++k) {
+            const bool pos = pk[k] & kMtPos, neg = pk[k] & kMtNeg, pred = pk[k] & kMtPred;
+            tot[0] += pos ? wt[k] : 0, tot[1] += neg ? wt[k] : 0;
+            tot[2] += (pos && pred) ? wt[k] : 0, tot[3] += (neg && pred) ? wt[k] : 0;
+            tot[4] += (pos && !pred) ? wt[k] : 0, tot[5] += (neg && !pred) ? wt[k] : 0;
+            tot[6] += ((pos || neg) && (pk[k] & kMtNonfinite)) ? wt[k] : 0;
+            tot[7] += (!pos && !neg) ? wt[k] : 0;            // wt is 0 for padding
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int f = 0; f < kMtTotals; ++f) {
+        const int s = wave_sum_int(tot[f]);
+        if ((tid & (kWave - 1)) == 0) atomicAdd(&tot_s[f], s);   // LDS, integers
+    }
+    __syncthreads();
+    const long long POS = tot_s[0];
+    const double dPOS = (double)POS;
+
+    // ---- pass 2: along the ranks
+    mt_u64 carry = 0, carry_end = 0;                         // (tp << 32 | fp) before the chunk; the same at the last group end
+    long long u2 = 0;
+    double ap = 0.0;
+    int *cv = curve ? curve + ((size_t)b * C + c) * (size_t)N * 2 : nullptr;
+    for (int r0 = 0; r0 < N; r0 += kMtChunk) {
+        metrics_load4(pc, wb, r0, Np, pk, wt);
+        mt_u64 cum[kMtItems], run = 0;
+#pragma unroll
+        for (int k = 0; k < kMtItems; ++k) {
+            run += (pk[k] & kMtPos) ? (mt_u64)(unsigned)wt[k] << 32 : (pk[k] & kMtNeg) ? (mt_u64)(unsigned)wt[k] : 0;
+            cum[k] = run;
+        }
+        mt_u64 total, total_end;
+        const mt_u64 before = carry + metrics_block_excl<false>(run, wsum, total);
+        mt_u64 prev[kMtItems], last = 0;                     // the latest group end before item k inside this lane
+#pragma unroll
+        for (int k = 0; k < kMtItems; ++k) {
+            cum[k] += before;
+            prev[k] = last;
+            if (pk[k] & kMtEnd) last = cum[k];               // never smaller than the one before
+        }
+        const mt_u64 before_end = max(carry_end, metrics_block_excl<true>(last, wmax, total_end));
+        const int e0 = kMtItems * tid, r = r0 + e0;
+#pragma unroll
+        for (int k = 0; k < kMtItems; ++k) {
+            const long long tp = (long long)(cum[k] >> 32), fp = (long long)(cum[k] & 0xffffffffu);
+            double term = 0.0;
+            if (pk[k] & kMtEnd) {
+                const mt_u64 pe = max(before_end, prev[k]);
+                const long long tpp = (long long)(pe >> 32), fpp = (long long)(pe & 0xffffffffu), d = tp - tpp;
+                u2 += (fp - fpp) * (tp + tpp);
+                if (d > 0) term = ((double)d / dPOS) * ((double)tp / (double)(tp + fp));
+            }
+            terms[e0 + k + (e0 + k) / kMtSlab] = term;
+            if (cv && (pk[k] & kMtValid)) cv[2 * (size_t)(r + k)] = (int)tp, cv[2 * (size_t)(r + k) + 1] = (int)fp;
+        }
+        carry += total, carry_end = max(carry_end, total_end);
+        __syncthreads();
+        if (tid < kMtChunkSlabs) {
+            double p = 0.0;
+#pragma unroll 8
+            for (int t = 0; t < kMtSlab; ++t) p = p + terms[tid * (kMtSlab + 1) + t];
+            part[tid] = p;
+        }
+        __syncthreads();
+        if (tid == 0)
+            for (int s = 0; s < kMtChunkSlabs; ++s) ap = ap + part[s];
+    }
+    const long long u2_all = wave_sum_ll(u2);
+    __shared__ long long u2_s[kMtThreads / kWave];
+    if ((tid & (kWave - 1)) == 0) u2_s[tid / kWave] = u2_all;
+    __syncthreads();
+    if (tid == 0) {
+        long long *o = fields + ((size_t)b * C + c) * ECG_MT_FIELDS;
+        long long u = 0;
+        for (int k = 0; k < kMtThreads / kWave; ++k) u += u2_s[k];
+        o[ECG_MT_POS] = POS, o[ECG_MT_NEG] = tot_s[1], o[ECG_MT_U2] = u, o[ECG_MT_TP] = tot_s[2], o[ECG_MT_FP] = tot_s[3];
+        o[ECG_MT_FN] = tot_s[4], o[ECG_MT_TN] = tot_s[5], o[ECG_MT_NONFINITE] = tot_s[6], o[ECG_MT_BAD] = tot_s[7];
+        ap_out[(size_t)b * C + c] = ap;
+    }
+}
+
+static bool metrics_sizes_ok(int N, int C) { return N >= 1 && N <= kMtMaxN && C >= 1 && C <= kMtMaxC; }
+static bool aligned_to(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+}  // namespace ecg
+
+using namespace ecg;
+
+ECG_API int ecg_metrics_slab(void) { return kMtSlab; }
+
+ECG_API size_t ecg_metrics_order_workspace_bytes(int N, int C) { return metrics_sizes_ok(N, C) ? metrics_ws_bytes(N, C) : 0; }
+
+ECG_API size_t ecg_metrics_counts_workspace_bytes(int N, int C, int B) {
+    return metrics_sizes_ok(N, C) && B >= 1 && B <= kMtMaxB ? metrics_ws_bytes(N, C) : 0;
+}
+
+ECG_API int ecg_metrics_order(const float *prob, int *order, int *nonfinite, void *workspace, int N, int C,
+                              ecg_stream_t stream) {
+    const char *who = "metrics_order";
+    ECG_REQUIRE(N >= 1 && N <= kMtMaxN, "%s: N=%d outside [1,%d]", who, N, kMtMaxN);
+    ECG_REQUIRE(C >= 1 && C <= kMtMaxC, "%s: C=%d outside [1,%d]", who, C, kMtMaxC);
+    ECG_REQUIRE(prob && order && nonfinite && workspace, "%s: null pointer", who);
+    ECG_REQUIRE(aligned_to(prob, 4) && aligned_to(order, 4) && aligned_to(nonfinite, 4) && aligned_to(workspace, 4),
+                "%s: a base is not 4-byte aligned", who);
+    unsigned *keys = metrics_ws_base(workspace);
+    const int Np = metrics_padded(N);
+    hipLaunchKernelGGL(metrics_keys_kernel, dim3(cdiv((long long)N * C, kMtThreads)), dim3(kMtThreads), 0, as_stream(stream),
+                       prob, keys, N, C, Np);
+    if (int rc = check_launch("metrics_keys_kernel")) return rc;
+    hipLaunchKernelGGL(metrics_rank_kernel, dim3(cdiv(N, kMtThreads), C), dim3(kMtThreads), 0, as_stream(stream), keys, order,
+                       nonfinite, N, Np);
+    return check_launch("metrics_rank_kernel");
+}
+
+ECG_API int ecg_metrics_counts(const float *prob, const float *y, const int *order, const int *w, long long *fields, double *ap,
+                               int *curve, void *workspace, int N, int C, int B, float threshold, ecg_stream_t stream) {
+    const char *who = "metrics_counts";
+    ECG_REQUIRE(N >= 1 && N <= kMtMaxN, "%s: N=%d outside [1,%d]", who, N, kMtMaxN);
+    ECG_REQUIRE(C >= 1 && C <= kMtMaxC, "%s: C=%d outside [1,%d]", who, C, kMtMaxC);
+    ECG_REQUIRE(B >= 1 && B <= kMtMaxB, "%s: B=%d outside [1,%d]", who, B, kMtMaxB);
+    ECG_REQUIRE(w || B == 1, "%s: B=%d weight rows need w (NULL means one row of ones)", who, B);
+    ECG_REQUIRE(threshold == threshold, "%s: threshold is NaN", who);
+    ECG_REQUIRE(prob && y && order && fields && ap && workspace, "%s: null pointer", who);
+    ECG_REQUIRE(aligned_to(fields, 8) && aligned_to(ap, 8), "%s: fields and ap must be 8-byte aligned", who);
+    ECG_REQUIRE(aligned_to(prob, 4) && aligned_to(y, 4) && aligned_to(order, 4) && aligned_to(w, 4) && aligned_to(curve, 4) &&
+                    aligned_to(workspace, 4),
+                "%s: a base is not 4-byte aligned", who);
+    unsigned *packed = metrics_ws_base(workspace);
+    const int Np = metrics_padded(N);
+    hipLaunchKernelGGL(metrics_pack_kernel, dim3(cdiv(Np, kMtThreads), C), dim3(kMtThreads), 0, as_stream(stream), prob, y, order,
+                       packed, N, C, Np, threshold);
+    if (int rc = check_launch("metrics_pack_kernel")) return rc;
+    hipLaunchKernelGGL(metrics_scan_kernel, dim3(B, C), dim3(kMtThreads), 0, as_stream(stream), packed, w, fields, ap, curve, N, C,
+                       Np);
+    return check_launch("metrics_scan_kernel");
+}

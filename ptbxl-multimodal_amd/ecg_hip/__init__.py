@@ -13,6 +13,7 @@ A raw recording is conditioned there too: a zero-phase baseline-wander high-pass
 WFDB records in formats 16, 61, 80, 160 and 212, with skews, offsets and several files, are decoded on the device (`ecg_hip.wfdbraw`).
 Windows spoiled by flat lines, rails or artefacts are kept out of the record-level numbers (`ecg_hip.quality`, quality=).
 Beat positions and per-window RR statistics come from an integer QRS detector on the device (`ecg_hip.beats`, beats=).
+Macro AUROC / AP / F1 of an epoch and bootstrap intervals for them come from exact integers on the device (`ecg_hip.metrics`).
 """
 from ._lib import EcgHipError, LIB_PATH, load  # noqa: F401
 

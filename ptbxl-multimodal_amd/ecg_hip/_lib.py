@@ -117,6 +117,11 @@ SIGNATURES = {
     "ecg_beats_series_mean_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "ecg_beats_series_mean": (_i, [_vp] * 7 + [_i] * 9 + [_vp]),
     "ecg_windows_overlap_mean": (_i, [_vp] * 3 + [_i] * 8 + [_vp]),
+    "ecg_metrics_slab": (_i, []),
+    "ecg_metrics_order_workspace_bytes": (_sz, [_i, _i]),
+    "ecg_metrics_order": (_i, [_vp] * 4 + [_i, _i, _vp]),
+    "ecg_metrics_counts_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ecg_metrics_counts": (_i, [_vp] * 8 + [_i, _i, _i, _f, _vp]),
     "ecg_host_gather_rows": (_i, [_vp, _sz, _vp, _i, _vp]),
 }
 

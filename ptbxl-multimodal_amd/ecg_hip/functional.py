@@ -874,3 +874,4 @@ from .input_step import (_fir_call, _resampled_call, beats_match, beats_rhythm, 
                          beats_sum, fir_filter, fir_windows, overlap_mean, wfdb16_beats, wfdb16_quality,
                          wfdb16_to_windows, wfdb16_to_windows_sliding, wfdb16_windows, wfdb16_windows_resampled,
                          wfdb_decode16, zscore_per_lead)
+from .metrics import metrics_counts, metrics_order  # noqa: E402,F401

@@ -10,6 +10,7 @@ With an `ecg_hip.optim.FlatAdamW` on one GPU and an unhooked model the step CAN 
 per batch shape (ecg_hip.graph.LoopStepper; opt-in: ECG_HIP_LOOP_GRAPH=1) — same kernels, same values, one host call
 per step.  Measured: no faster than the eager loop at any batch size while the GPU is the bottleneck (graph.py).
 """
+import os
 from typing import Dict
 
 import numpy as np
@@ -19,7 +20,7 @@ from torch.utils.data import DataLoader
 from ecg_hip import functional as hipF
 from ecg_hip.graph import LoopStepper
 from ecg_hip.optim import adopt_stock_adamw
-from src.training.metrics import compute_metrics
+from src.training.metrics import compute_metrics, compute_metrics_device
 
 try:
     from tqdm import tqdm
@@ -67,8 +68,13 @@ def eval_one_epoch(model, loader: DataLoader, device) -> Dict[str, float]:
             hipF.binary_cross_entropy_with_logits(logits, y, weighted, x.size(0))
             probs.append(hipF.sigmoid(logits))
             targets.append(y)
-    y_true = torch.cat(targets).cpu().numpy()
-    y_prob = torch.cat(probs).cpu().numpy()
-    out = compute_metrics(y_true, y_prob, threshold=0.5)
+    # opt-in (read per call, as ECG_HIP_LOOP_GRAPH is): the metrics from exact integers on the device, one host read
+    if os.environ.get("ECG_HIP_DEVICE_METRICS") == "1" and probs and probs[0].is_cuda:
+        full = compute_metrics_device(torch.cat(targets), torch.cat(probs), threshold=0.5)
+        out = {k: full[k] for k in ("auroc_macro", "auprc_macro", "f1_macro")}
+    else:
+        y_true = torch.cat(targets).cpu().numpy()
+        y_prob = torch.cat(probs).cpu().numpy()
+        out = compute_metrics(y_true, y_prob, threshold=0.5)
     out["bce_loss"] = (0.0 if weighted is None else weighted.item()) / len(loader.dataset)
     return out

@@ -1,7 +1,10 @@
 """Macro AUROC / AUPRC / F1 for multi-label predictions (reference src/training/metrics.py:5-42).
-Epoch-end, host-side, O(N*C) on a few thousand rows: stays on sklearn."""
+Epoch-end, host-side, O(N*C) on a few thousand rows: stays on sklearn.
+compute_metrics_device (ecg_hip/metrics.py, re-exported here) gives the same three numbers from device tensors."""
 import numpy as np
 from sklearn import metrics as skm
+
+from ecg_hip.metrics import compute_metrics_device  # noqa: F401
 
 
 def _nan_on_value_error(fn, *args, **kw):
