@@ -836,6 +836,56 @@ int ecg_metrics_order(const float *prob, int *order, int *nonfinite, void *works
 size_t ecg_metrics_counts_workspace_bytes(int N, int C, int B);
 int ecg_metrics_counts(const float *prob, const float *y, const int *order, const int *w, long long *fields, double *ap,
                        int *curve, void *workspace, int N, int C, int B, float threshold, ecg_stream_t stream);
+/* Paired comparison of models scored on the SAME rows (DeLong, DeLong & Clarke-Pearson 1988; McNemar): again exact
+ * integers, with KEY, POSITIVE, NEGATIVE, BAD, `order` and the workspace rules exactly as above.  Unit weights only.
+ *
+ * ecg_metrics_placements (two launches) — place [C][N] int32, indexed by ROW (not by rank), so that the placements of two
+ * models of the same rows line up element by element.  Per column c, over the rows of that column:
+ *     positive row i:  a_i = 2 * #{negative j : key_j < key_i} + #{negative j : key_j == key_i}
+ *     negative row j:  b_j = 2 * #{positive i : key_i > key_j} + #{positive i : key_i == key_j}
+ *     BAD row:         -1
+ * so a_i / (2 NEG) and b_j / (2 POS) are DeLong's structural components and sum_pos a == sum_neg b == ECG_MT_U2.  Along
+ * the ranks, with tp / fp as above and a tie group's `start` their value before its first rank, `end` at its last:
+ *     a = 2 NEG - fp_start - fp_end        b = tp_start + tp_end
+ * whatever the length of the group.  0 <= a <= 2 NEG and 0 <= b <= 2 POS: at most 131 072.
+ * ECG_EINVAL before any launch — the integer limits first: N outside [1, 65536], C outside [1, 64]; then a NULL pointer or
+ * a base off 4 bytes.
+ *
+ * ecg_metrics_paired_sums (two launches) — place [M][C][N] int32: the placements of M models, stacked by the caller;
+ * prob [M][N][C] fp32 their probabilities; y [N][C]; a model is RIGHT on a row iff (prob >= threshold, compared in fp32
+ * as for ECG_MT_TP; a NaN predicts 0) equals (y == 1.0f).  BAD rows are in no sum.
+ *   single [C][M][ECG_MP_SINGLE_FIELDS] int64:   ECG_MP_U2 = sum_pos a (the ECG_MT_U2 of that model, by another route),
+ *     ECG_MP_POS, ECG_MP_NEG.
+ *   pair [C][M][M][ECG_MP_PAIR_FIELDS] int64, for every ORDERED pair (k, l), the diagonal included:
+ *     ECG_MP_SPOS = sum_pos a^k a^l            ECG_MP_SNEG = sum_neg b^k b^l
+ *     ECG_MP_K_ONLY, ECG_MP_L_ONLY, ECG_MP_BOTH, ECG_MP_NEITHER   the rows on which only k / only l / both / neither is right
+ *   Every output is a sum of integers: one value in any order.  The largest, POS * (2 NEG)^2 with POS + NEG <= 65536, stays
+ *   below 2 * 10^14, far inside int64.  From them (ecg_hip/metrics.py: delong_from_sums, mcnemar_from_sums), with m = POS,
+ *   n = NEG, U = U2:   theta_k = U_k / (2mn),
+ *     Cov[k][l] = (m SPOS - U_k U_l) / (4 n^2 m^2 (m-1)) + (n SNEG - U_k U_l) / (4 m^2 n^2 (n-1)).
+ * ECG_EINVAL before any launch — the integer limits first: N outside [1, 65536], C outside [1, 64], M outside [1, 8];
+ * threshold NaN; then a NULL pointer or a misaligned base: 8 bytes for single and pair, 4 otherwise. */
+enum {
+    ECG_MP_U2 = 0,
+    ECG_MP_POS = 1,
+    ECG_MP_NEG = 2,
+    ECG_MP_SINGLE_FIELDS = 3
+};
+enum {
+    ECG_MP_SPOS = 0,
+    ECG_MP_SNEG = 1,
+    ECG_MP_K_ONLY = 2,
+    ECG_MP_L_ONLY = 3,
+    ECG_MP_BOTH = 4,
+    ECG_MP_NEITHER = 5,
+    ECG_MP_PAIR_FIELDS = 6
+};
+size_t ecg_metrics_placements_workspace_bytes(int N, int C);
+int ecg_metrics_placements(const float *prob, const float *y, const int *order, int *place, void *workspace, int N, int C,
+                           ecg_stream_t stream);
+size_t ecg_metrics_paired_sums_workspace_bytes(int N, int C, int M);
+int ecg_metrics_paired_sums(const int *place, const float *prob, const float *y, long long *single, long long *pair,
+                            void *workspace, int N, int C, int M, float threshold, ecg_stream_t stream);
 /* HOST side of the same step — what torch's DataLoader collate does for the reference (one `Dataset.__getitem__` per record,
  * src/datasets/ptbxl.py:25,122-127, stacked into a batch): rows `rows[0..n)` of a row-major host table (row_bytes each, e.g.
  * the int16 records of a memory-mapped pack) copied to consecutive rows of `dst` (the pinned staging slot).  Plain memcpy

@@ -196,14 +196,43 @@ __device__ __forceinline__ int wave_sum_int(int v) {
 
 // the four packed words of lane `tid` in the chunk at r0, and their weights (0 for a word that is not valid)
 __device__ __forceinline__ void metrics_load4(const unsigned *__restrict__ pc, const int *__restrict__ wb, int r0, int Np,
-                                              unsigned pk[kMtItems], int wt[kMtItems]) {
-    const int r = r0 + kMtItems * (int)threadIdx.x;
+                                              unsigned pk[kMtItems], int wt[kMtItems], int lane = (int)threadIdx.x) {
+    const int r = r0 + kMtItems * lane;
     uint4 v = make_uint4(0u, 0u, 0u, 0u);
     if (r < Np) v = *reinterpret_cast<const uint4 *>(pc + r);   // r and Np are multiples of 4
     pk[0] = v.x, pk[1] = v.y, pk[2] = v.z, pk[3] = v.w;
 #pragma unroll
     for (int k = 0; k < kMtItems; ++k)
         wt[k] = (pk[k] & kMtValid) ? (wb ? wb[pk[k] & 0xffffu] : 1) : 0;
+}
+
+// One chunk of the walk along the ranks, the lane's four consecutive items in pk / wt: cum[k] = (tp << 32 | fp) at item k
+// (both stay below 2^30, so the halves never meet) by one block-wide sum scan, and start[k] = the same word at the latest
+// group end BEFORE item k (0 if there is none) by one block-wide MAX scan of the word at group ends: tp and fp never
+// decrease, so the latest group end is the largest.  carry / carry_end hold the two across chunks.  The caller's loop has
+// a __syncthreads between two calls (the slots of wsum / wmax).
+__device__ __forceinline__ void metrics_walk4(const unsigned pk[kMtItems], const int wt[kMtItems], mt_u64 &carry,
+                                              mt_u64 &carry_end, mt_u64 *wsum, mt_u64 *wmax, mt_u64 cum[kMtItems],
+                                              mt_u64 start[kMtItems]) {
+    mt_u64 run = 0;
+#pragma unroll
+    for (int k = 0; k < kMtItems; ++k) {
+        run += (pk[k] & kMtPos) ? (mt_u64)(unsigned)wt[k] << 32 : (pk[k] & kMtNeg) ? (mt_u64)(unsigned)wt[k] : 0;
+        cum[k] = run;
+    }
+    mt_u64 total, total_end;
+    const mt_u64 before = carry + metrics_block_excl<false>(run, wsum, total);
+    mt_u64 last = 0;                                         // the latest group end before item k inside this lane
+#pragma unroll
+    for (int k = 0; k < kMtItems; ++k) {
+        cum[k] += before;
+        start[k] = last;
+        if (pk[k] & kMtEnd) last = cum[k];                   // never smaller than the one before
+    }
+    const mt_u64 before_end = max(carry_end, metrics_block_excl<true>(last, wmax, total_end));
+#pragma unroll
+    for (int k = 0; k < kMtItems; ++k) start[k] = max(before_end, start[k]);
+    carry += total, carry_end = max(carry_end, total_end);
 }
 
 constexpr int kMtTotals = 8;
@@ -253,29 +282,15 @@ __global__ __launch_bounds__(kMtThreads) void metrics_scan_kernel(const unsigned
     int *cv = curve ? curve + ((size_t)b * C + c) * (size_t)N * 2 : nullptr;
     for (int r0 = 0; r0 < N; r0 += kMtChunk) {
         metrics_load4(pc, wb, r0, Np, pk, wt);
-        mt_u64 cum[kMtItems], run = 0;
-#pragma unroll
-        for (int k = 0; k < kMtItems; ++k) {
-            run += (pk[k] & kMtPos) ? (mt_u64)(unsigned)wt[k] << 32 : (pk[k] & kMtNeg) ? (mt_u64)(unsigned)wt[k] : 0;
-            cum[k] = run;
-        }
-        mt_u64 total, total_end;
-        const mt_u64 before = carry + metrics_block_excl<false>(run, wsum, total);
-        mt_u64 prev[kMtItems], last = 0;                     // the latest group end before item k inside this lane
-#pragma unroll
-        for (int k = 0; k < kMtItems; ++k) {
-            cum[k] += before;
-            prev[k] = last;
-            if (pk[k] & kMtEnd) last = cum[k];               // never smaller than the one before
-        }
-        const mt_u64 before_end = max(carry_end, metrics_block_excl<true>(last, wmax, total_end));
+        mt_u64 cum[kMtItems], start[kMtItems];
+        metrics_walk4(pk, wt, carry, carry_end, wsum, wmax, cum, start);
         const int e0 = kMtItems * tid, r = r0 + e0;
 #pragma unroll
         for (int k = 0; k < kMtItems; ++k) {
             const long long tp = (long long)(cum[k] >> 32), fp = (long long)(cum[k] & 0xffffffffu);
             double term = 0.0;
             if (pk[k] & kMtEnd) {
-                const mt_u64 pe = max(before_end, prev[k]);
+                const mt_u64 pe = start[k];
                 const long long tpp = (long long)(pe >> 32), fpp = (long long)(pe & 0xffffffffu), d = tp - tpp;
                 u2 += (fp - fpp) * (tp + tpp);
                 if (d > 0) term = ((double)d / dPOS) * ((double)tp / (double)(tp + fp));
@@ -283,7 +298,6 @@ __global__ __launch_bounds__(kMtThreads) void metrics_scan_kernel(const unsigned
             terms[e0 + k + (e0 + k) / kMtSlab] = term;
             if (cv && (pk[k] & kMtValid)) cv[2 * (size_t)(r + k)] = (int)tp, cv[2 * (size_t)(r + k) + 1] = (int)fp;
         }
-        carry += total, carry_end = max(carry_end, total_end);
         __syncthreads();
         if (tid < kMtChunkSlabs) {
             double p = 0.0;
@@ -306,6 +320,132 @@ __global__ __launch_bounds__(kMtThreads) void metrics_scan_kernel(const unsigned
         o[ECG_MT_POS] = POS, o[ECG_MT_NEG] = tot_s[1], o[ECG_MT_U2] = u, o[ECG_MT_TP] = tot_s[2], o[ECG_MT_FP] = tot_s[3];
         o[ECG_MT_FN] = tot_s[4], o[ECG_MT_TN] = tot_s[5], o[ECG_MT_NONFINITE] = tot_s[6], o[ECG_MT_BAD] = tot_s[7];
         ap_out[(size_t)b * C + c] = ap;
+    }
+}
+
+// ---- placements.  One workgroup per column walks the packed ranks twice with metrics_walk4 (unit weights):
+//   ascending    start = (tp, fp) before the rank's tie group; the rank keeps  half = -fp_start (positive) / tp_start (negative)
+//                in the second plane of the workspace, and the walk ends with (POS, NEG) in its carry;
+//   descending   the same walk over the ranks read backwards — thread t takes lane 255 - t of the chunk, its items last
+//                to first, the chunks last to first — where a rank carries the group-end flag of the rank BEFORE it (a
+//                boundary after rank r-1 is a boundary before rank r).  Its `start` is then the (tp, fp) of everything
+//                ranked after the rank's group, S, so tp_end = POS - S.tp and fp_end = NEG - S.fp whatever number of chunks
+//                the group spans, and   a = 2 NEG - fp_start - fp_end = NEG + half + S.fp,   b = tp_start + tp_end = half +
+//                POS - S.tp   go to place[c][row].
+__global__ __launch_bounds__(kMtThreads) void metrics_place_kernel(const unsigned *__restrict__ packed, int *__restrict__ half,
+                                                                   int *__restrict__ place, int N, int Np) {
+    __shared__ mt_u64 wsum[kMtThreads / kWave], wmax[kMtThreads / kWave];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    const unsigned *pc = packed + (size_t)c * Np;
+    int *hc = half + (size_t)c * Np, *out = place + (size_t)c * N;
+    unsigned pk[kMtItems];
+    int wt[kMtItems];
+    mt_u64 cum[kMtItems], start[kMtItems];
+
+    mt_u64 carry = 0, carry_end = 0;
+    for (int r0 = 0; r0 < N; r0 += kMtChunk) {
+        metrics_load4(pc, nullptr, r0, Np, pk, wt);
+        metrics_walk4(pk, wt, carry, carry_end, wsum, wmax, cum, start);
+        const int r = r0 + kMtItems * tid;
+        int h[kMtItems];
+#pragma unroll
+        for (int k = 0; k < kMtItems; ++k)
+            h[k] = (pk[k] & kMtPos) ? -(int)(start[k] & 0xffffffffu) : (int)(start[k] >> 32);
+        if (r < Np) *reinterpret_cast<int4 *>(hc + r) = make_int4(h[0], h[1], h[2], h[3]);   // r and Np are multiples of 4
+        __syncthreads();                                     // the scan's slots; after the last chunk, the plane is visible
+    }
+    const int POS = (int)(carry >> 32), NEG = (int)(carry & 0xffffffffu);
+
+    const int lane = kMtThreads - 1 - tid;
+    carry = 0, carry_end = 0;
+    for (int r0 = ((N - 1) / kMtChunk) * kMtChunk; r0 >= 0; r0 -= kMtChunk) {
+        metrics_load4(pc, nullptr, r0, Np, pk, wt, lane);
+        const int r = r0 + kMtItems * lane;
+        const unsigned before = (r > 0 && r <= Np) ? pc[r - 1] : 0u;
+        int4 hv = make_int4(0, 0, 0, 0);
+        if (r < Np) hv = *reinterpret_cast<const int4 *>(hc + r);
+        const int h[kMtItems] = {hv.x, hv.y, hv.z, hv.w};
+        unsigned rk[kMtItems];                               // the items last to first, group ends moved one rank up
+        int rw[kMtItems];
+#pragma unroll
+        for (int k = 0; k < kMtItems; ++k) {
+            const int i = kMtItems - 1 - k;
+            const unsigned prev = i > 0 ? pk[i - 1] : before;
+            rk[k] = (pk[i] & ~kMtEnd) | (prev & kMtEnd);
+            rw[k] = wt[i];
+        }
+        metrics_walk4(rk, rw, carry, carry_end, wsum, wmax, cum, start);
+#pragma unroll
+        for (int k = 0; k < kMtItems; ++k) {
+            const int i = kMtItems - 1 - k;
+            if (!(pk[i] & kMtValid)) continue;
+            const int stp = (int)(start[k] >> 32), sfp = (int)(start[k] & 0xffffffffu);
+            out[pk[i] & 0xffffu] = (pk[i] & kMtPos) ? NEG + h[i] + sfp : (pk[i] & kMtNeg) ? h[i] + POS - stp : -1;   // row < N
+        }
+        __syncthreads();
+    }
+}
+
+// ---- paired sums.  Workgroup (k * M + l, c, s) with k <= l adds, over the rows [s * kPsRows, (s + 1) * kPsRows) of class c,
+// the nine integers from which the finish kernel makes single[c][k] (on the diagonal) and pair[c][k][l], pair[c][l][k].
+constexpr int kPsRows = 2048, kPsMaxM = 8;
+enum { kPsSpos, kPsSneg, kPsBoth, kPsRk, kPsRl, kPsValid, kPsU2, kPsPos, kPsNeg, kPsParts };
+
+__host__ __device__ __forceinline__ int metrics_pair_slices(int N) { return (N + kPsRows - 1) / kPsRows; }
+
+__global__ __launch_bounds__(kMtThreads) void metrics_pair_part_kernel(const int *__restrict__ place, const float *__restrict__ prob,
+                                                                       const float *__restrict__ y, long long *__restrict__ part,
+                                                                       int N, int C, int M, float threshold) {
+    __shared__ long long red[kMtThreads / kWave][kPsParts];
+    const int k = blockIdx.x / M, l = blockIdx.x - k * M, c = blockIdx.y, s = blockIdx.z, tid = threadIdx.x;
+    if (k > l) return;                                       // the whole workgroup: (l, k) is (k, l) read the other way
+    const int *ak = place + ((size_t)k * C + c) * N, *al = place + ((size_t)l * C + c) * N;
+    const float *qk = prob + (size_t)k * N * C + c, *ql = prob + (size_t)l * N * C + c;
+    long long acc[kPsParts] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const int n1 = min(N, (s + 1) * kPsRows);
+    for (int n = s * kPsRows + tid; n < n1; n += kMtThreads) {
+        const float lab = y[(size_t)n * C + c];
+        const bool pos = lab == 1.0f, neg = lab == 0.0f;
+        if (!pos && !neg) continue;                          // BAD: in no sum
+        const long long pk_ = ak[n], pl_ = al[n];
+        const bool rk = (qk[(size_t)n * C] >= threshold) == pos, rl = (ql[(size_t)n * C] >= threshold) == pos;
+        acc[kPsSpos] += pos ? pk_ * pl_ : 0, acc[kPsSneg] += pos ? 0 : pk_ * pl_;
+        acc[kPsBoth] += rk && rl, acc[kPsRk] += rk, acc[kPsRl] += rl, acc[kPsValid] += 1;
+        acc[kPsU2] += pos ? pk_ : 0, acc[kPsPos] += pos, acc[kPsNeg] += neg;
+    }
+#pragma unroll
+    for (int f = 0; f < kPsParts; ++f) {
+        const long long v = wave_sum_ll(acc[f]);
+        if ((tid & (kWave - 1)) == 0) red[tid / kWave][f] = v;
+    }
+    __syncthreads();
+    if (tid < kPsParts) {
+        long long v = 0;
+        for (int w = 0; w < kMtThreads / kWave; ++w) v += red[w][tid];
+        part[((((size_t)c * M + k) * M + l) * gridDim.z + s) * kPsParts + tid] = v;
+    }
+}
+
+__global__ __launch_bounds__(kMtThreads) void metrics_pair_finish_kernel(const long long *__restrict__ part,
+                                                                         long long *__restrict__ single,
+                                                                         long long *__restrict__ pair, int C, int M, int S) {
+    const int e = blockIdx.x * kMtThreads + threadIdx.x;     // (c, k, l): C * M * M <= 4096
+    if (e >= C * M * M) return;
+    const int l = e % M, k = (e / M) % M, c = e / (M * M);
+    const int lo = min(k, l), hi = max(k, l);
+    const long long *p = part + (((size_t)c * M + lo) * M + hi) * S * kPsParts;
+    long long v[kPsParts] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (int s = 0; s < S; ++s)
+#pragma unroll
+        for (int f = 0; f < kPsParts; ++f) v[f] += p[(size_t)s * kPsParts + f];
+    const long long right_k = k <= l ? v[kPsRk] : v[kPsRl], right_l = k <= l ? v[kPsRl] : v[kPsRk];
+    long long *o = pair + (size_t)e * ECG_MP_PAIR_FIELDS;
+    o[ECG_MP_SPOS] = v[kPsSpos], o[ECG_MP_SNEG] = v[kPsSneg];
+    o[ECG_MP_K_ONLY] = right_k - v[kPsBoth], o[ECG_MP_L_ONLY] = right_l - v[kPsBoth];
+    o[ECG_MP_BOTH] = v[kPsBoth], o[ECG_MP_NEITHER] = v[kPsValid] - right_k - right_l + v[kPsBoth];
+    if (k == l) {
+        long long *q = single + ((size_t)c * M + k) * ECG_MP_SINGLE_FIELDS;
+        q[ECG_MP_U2] = v[kPsU2], q[ECG_MP_POS] = v[kPsPos], q[ECG_MP_NEG] = v[kPsNeg];
     }
 }
 
@@ -363,4 +503,53 @@ ECG_API int ecg_metrics_counts(const float *prob, const float *y, const int *ord
     hipLaunchKernelGGL(metrics_scan_kernel, dim3(B, C), dim3(kMtThreads), 0, as_stream(stream), packed, w, fields, ap, curve, N, C,
                        Np);
     return check_launch("metrics_scan_kernel");
+}
+
+static size_t metrics_pair_part_count(int N, int C, int M) { return (size_t)C * M * M * metrics_pair_slices(N) * kPsParts; }
+
+ECG_API size_t ecg_metrics_placements_workspace_bytes(int N, int C) {
+    return metrics_sizes_ok(N, C) ? 2 * (size_t)C * metrics_padded(N) * 4 + 16 : 0;
+}
+
+ECG_API size_t ecg_metrics_paired_sums_workspace_bytes(int N, int C, int M) {
+    return metrics_sizes_ok(N, C) && M >= 1 && M <= kPsMaxM ? metrics_pair_part_count(N, C, M) * 8 + 16 : 0;
+}
+
+ECG_API int ecg_metrics_placements(const float *prob, const float *y, const int *order, int *place, void *workspace, int N,
+                                   int C, ecg_stream_t stream) {
+    const char *who = "metrics_placements";
+    ECG_REQUIRE(N >= 1 && N <= kMtMaxN, "%s: N=%d outside [1,%d]", who, N, kMtMaxN);
+    ECG_REQUIRE(C >= 1 && C <= kMtMaxC, "%s: C=%d outside [1,%d]", who, C, kMtMaxC);
+    ECG_REQUIRE(prob && y && order && place && workspace, "%s: null pointer", who);
+    ECG_REQUIRE(aligned_to(prob, 4) && aligned_to(y, 4) && aligned_to(order, 4) && aligned_to(place, 4) && aligned_to(workspace, 4),
+                "%s: a base is not 4-byte aligned", who);
+    unsigned *packed = metrics_ws_base(workspace);
+    const int Np = metrics_padded(N);
+    int *half = reinterpret_cast<int *>(packed + (size_t)C * Np);   // C * Np * 4 is a multiple of 16
+    hipLaunchKernelGGL(metrics_pack_kernel, dim3(cdiv(Np, kMtThreads), C), dim3(kMtThreads), 0, as_stream(stream), prob, y, order,
+                       packed, N, C, Np, 0.0f);
+    if (int rc = check_launch("metrics_pack_kernel")) return rc;
+    hipLaunchKernelGGL(metrics_place_kernel, dim3(C), dim3(kMtThreads), 0, as_stream(stream), packed, half, place, N, Np);
+    return check_launch("metrics_place_kernel");
+}
+
+ECG_API int ecg_metrics_paired_sums(const int *place, const float *prob, const float *y, long long *single, long long *pair,
+                                    void *workspace, int N, int C, int M, float threshold, ecg_stream_t stream) {
+    const char *who = "metrics_paired_sums";
+    ECG_REQUIRE(N >= 1 && N <= kMtMaxN, "%s: N=%d outside [1,%d]", who, N, kMtMaxN);
+    ECG_REQUIRE(C >= 1 && C <= kMtMaxC, "%s: C=%d outside [1,%d]", who, C, kMtMaxC);
+    ECG_REQUIRE(M >= 1 && M <= kPsMaxM, "%s: M=%d outside [1,%d]", who, M, kPsMaxM);
+    ECG_REQUIRE(threshold == threshold, "%s: threshold is NaN", who);
+    ECG_REQUIRE(place && prob && y && single && pair && workspace, "%s: null pointer", who);
+    ECG_REQUIRE(aligned_to(single, 8) && aligned_to(pair, 8), "%s: single and pair must be 8-byte aligned", who);
+    ECG_REQUIRE(aligned_to(place, 4) && aligned_to(prob, 4) && aligned_to(y, 4) && aligned_to(workspace, 4),
+                "%s: a base is not 4-byte aligned", who);
+    long long *part = reinterpret_cast<long long *>(metrics_ws_base(workspace));
+    const int S = metrics_pair_slices(N);
+    hipLaunchKernelGGL(metrics_pair_part_kernel, dim3(M * M, C, S), dim3(kMtThreads), 0, as_stream(stream), place, prob, y, part,
+                       N, C, M, threshold);
+    if (int rc = check_launch("metrics_pair_part_kernel")) return rc;
+    hipLaunchKernelGGL(metrics_pair_finish_kernel, dim3(cdiv((long long)C * M * M, kMtThreads)), dim3(kMtThreads), 0,
+                       as_stream(stream), part, single, pair, C, M, S);
+    return check_launch("metrics_pair_finish_kernel");
 }

@@ -122,6 +122,10 @@ SIGNATURES = {
     "ecg_metrics_order": (_i, [_vp] * 4 + [_i, _i, _vp]),
     "ecg_metrics_counts_workspace_bytes": (_sz, [_i, _i, _i]),
     "ecg_metrics_counts": (_i, [_vp] * 8 + [_i, _i, _i, _f, _vp]),
+    "ecg_metrics_placements_workspace_bytes": (_sz, [_i, _i]),
+    "ecg_metrics_placements": (_i, [_vp] * 5 + [_i, _i, _vp]),
+    "ecg_metrics_paired_sums_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ecg_metrics_paired_sums": (_i, [_vp] * 6 + [_i, _i, _i, _f, _vp]),
     "ecg_host_gather_rows": (_i, [_vp, _sz, _vp, _i, _vp]),
 }
 

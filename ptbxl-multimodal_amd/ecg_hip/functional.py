@@ -874,4 +874,5 @@ from .input_step import (_fir_call, _resampled_call, beats_match, beats_rhythm, 
                          beats_sum, fir_filter, fir_windows, overlap_mean, wfdb16_beats, wfdb16_quality,
                          wfdb16_to_windows, wfdb16_to_windows_sliding, wfdb16_windows, wfdb16_windows_resampled,
                          wfdb_decode16, zscore_per_lead)
-from .metrics import metrics_counts, metrics_order  # noqa: E402,F401
+from .metrics import (compare_models, delong_from_sums, mcnemar_from_sums, metrics_counts, metrics_order,  # noqa: E402,F401
+                      metrics_paired_sums, metrics_placements)

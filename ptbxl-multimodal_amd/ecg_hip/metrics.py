@@ -6,6 +6,11 @@ tp / fp along the ranks — and one fp64 sum in a stated order for the average p
 definitions).  `summarize` makes the numbers scikit-learn reports out of them, with its edge rules; a bootstrap replicate
 is the same computation with integer multiplicities as weights, so `bootstrap_metrics` sorts once for all replicates.
 `compute_metrics_device` is the drop-in for src/training/metrics.py's compute_metrics on device tensors.
+
+Paired comparison of models scored on the same rows: `metrics_placements` (ecg_metrics_placements) gives every row its
+placement among the rows of the other label, `metrics_paired_sums` (ecg_metrics_paired_sums) the integer sums of their
+products and the counts of who is right where; `delong_from_sums` and `mcnemar_from_sums` turn those into DeLong's and
+McNemar's tests in Python integers, and `compare_models` is the whole path with a paired bootstrap on request.
 """
 import numpy as np
 import torch
@@ -166,6 +171,239 @@ def bootstrap_metrics(y_true, y_prob, n_boot=1000, seed=0, threshold=0.5, alpha=
                   "hi": float(hi) if scalar else hi}
         out["n_nan"][k] = int(nan.sum()) if scalar else nan.sum(0)
         out["replicates"][k] = reps
+    return out
+
+
+SINGLE_FIELDS = ("u2", "pos", "neg")
+PAIR_FIELDS = ("spos", "sneg", "k_only", "l_only", "both", "neither")
+(P_SPOS, P_SNEG, P_K_ONLY, P_L_ONLY, P_BOTH, P_NEITHER) = range(6)
+MAX_MODELS = 8
+
+
+def metrics_placements(prob, y, order=None):
+    """prob, y fp32 [N, C]; order int32 [C, N] (metrics_order(prob) when None) -> place int32 [C, N], indexed by ROW: for a
+    positive row twice the negatives of the column that score below it plus those that tie with it, for a negative row
+    twice the positives that score above it plus the ties, -1 for a row whose label is neither 0 nor 1 (ecg_metrics_placements).
+    place / (2 NEG) and place / (2 POS) are DeLong's structural components."""
+    who = "metrics_placements"
+    prob = _device_matrix(who, "prob", prob, torch.float32)
+    y = _device_matrix(who, "y", y, torch.float32)
+    if y.shape != prob.shape:
+        raise L.EcgHipError(f"{who}: y {tuple(y.shape)} and prob {tuple(prob.shape)} differ in shape")
+    N, C = prob.shape
+    if order is None:
+        order = metrics_order(prob)[0]
+    order = _device_matrix(who, "order", order, torch.int32)
+    if tuple(order.shape) != (C, N):
+        raise L.EcgHipError(f"{who}: order must be [C={C}, N={N}], got {tuple(order.shape)}")
+    place = torch.empty((C, N), dtype=torch.int32, device=prob.device)
+    ws = _workspace(L.query("ecg_metrics_placements_workspace_bytes", N, C), prob.device)
+    L.call("ecg_metrics_placements", L.ptr(prob), L.ptr(y), L.ptr(order), L.ptr(place), L.ptr(ws), N, C, L.stream())
+    return place
+
+
+def metrics_paired_sums(place, probs, y, threshold=0.5):
+    """place int32 [M, C, N] (the metrics_placements of M models, stacked), probs fp32 [M, N, C], y fp32 [N, C] ->
+    (single int64 [C, M, 3] in the order of SINGLE_FIELDS, pair int64 [C, M, M, 6] in the order of PAIR_FIELDS, for every
+    ordered pair of models): ecg_metrics_paired_sums."""
+    who = "metrics_paired_sums"
+    y = _device_matrix(who, "y", y, torch.float32)
+    N, C = y.shape
+    for name, t, dtype in (("place", place, torch.int32), ("probs", probs, torch.float32)):
+        if not (torch.is_tensor(t) and t.is_cuda):
+            raise L.EcgHipError(f"{who}: a CPU tensor reached the HIP metrics step; {name} must be on the GPU")
+        if t.dtype != dtype or t.dim() != 3:
+            raise L.EcgHipError(f"{who}: {name} must be {dtype} with three dimensions, got {t.dtype} {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise L.EcgHipError(f"{who}: {name} must be contiguous")
+    M = probs.shape[0]
+    if tuple(probs.shape) != (M, N, C) or tuple(place.shape) != (M, C, N):
+        raise L.EcgHipError(f"{who}: probs must be [M, N={N}, C={C}] and place [M, C={C}, N={N}], got {tuple(probs.shape)} "
+                            f"and {tuple(place.shape)}")
+    single = torch.empty((C, M, len(SINGLE_FIELDS)), dtype=torch.int64, device=y.device)
+    pair = torch.empty((C, M, M, len(PAIR_FIELDS)), dtype=torch.int64, device=y.device)
+    ws = _workspace(L.query("ecg_metrics_paired_sums_workspace_bytes", N, C, M), y.device)
+    L.call("ecg_metrics_paired_sums", L.ptr(place), L.ptr(probs), L.ptr(y), L.ptr(single), L.ptr(pair), L.ptr(ws), N, C, M,
+           float(threshold), L.stream())
+    return single, pair
+
+
+def _ratio(num, den):
+    """One correctly rounded division of two Python integers (CPython's int / int)."""
+    return num / den
+
+
+def delong_from_sums(single, pair):
+    """single int [C, M, 3], pair int [C, M, M, 6] (arrays or tensors, as metrics_paired_sums gives them) -> a dict of
+    float64 arrays: "theta" [C, M], "cov", "var", "delta", "z", "p" [C, M, M] — DeLong's test for every ordered pair
+    (k, l) of models and every class.  Host only, in Python integers: with m = POS, n = NEG, U_k = U2 of model k,
+        theta_k  = U_k / (2mn)
+        Cov[k,l] = ((m SPOS - U_k U_l)(n-1) + (n SNEG - U_k U_l)(m-1)) / (4 m^2 n^2 (m-1)(n-1))
+        var[k,l] = Cov[k,k] + Cov[l,l] - 2 Cov[k,l], its three numerators combined over the same denominator
+    each ONE integer ratio turned into a double by one correctly rounded division.  Then, in fp64 and in this sequence,
+    delta = theta_k - theta_l, z = delta / sqrt(var), p = erfc(|z| / sqrt(2)) (two-sided).  theta is NaN when m == 0 or
+    n == 0 (summarize's rule); cov, var, z and p are NaN when m < 2 or n < 2, and z and p also when var == 0 (two models
+    that rank the rows alike)."""
+    import math
+    s, q = _host(single, np.int64), _host(pair, np.int64)
+    C, M = s.shape[0], s.shape[1]
+    nan = float("nan")
+    out = {k: np.full((C, M) if k == "theta" else (C, M, M), nan, np.float64) for k in ("theta", "cov", "var", "delta", "z", "p")}
+    for c in range(C):
+        m, n = int(s[c, 0, 1]), int(s[c, 0, 2])
+        U = [int(s[c, k, 0]) for k in range(M)]
+        if m > 0 and n > 0:
+            for k in range(M):
+                out["theta"][c, k] = _ratio(U[k], 2 * m * n)
+        for k in range(M):
+            for l in range(M):
+                out["delta"][c, k, l] = out["theta"][c, k] - out["theta"][c, l]
+        if m < 2 or n < 2:
+            continue
+        den = 4 * m * m * n * n * (m - 1) * (n - 1)
+        num = [[(m * int(q[c, k, l, P_SPOS]) - U[k] * U[l]) * (n - 1) + (n * int(q[c, k, l, P_SNEG]) - U[k] * U[l]) * (m - 1)
+                for l in range(M)] for k in range(M)]
+        for k in range(M):
+            for l in range(M):
+                vnum = num[k][k] + num[l][l] - 2 * num[k][l]
+                out["cov"][c, k, l] = _ratio(num[k][l], den)
+                out["var"][c, k, l] = var = _ratio(vnum, den)
+                if vnum != 0:
+                    out["z"][c, k, l] = z = float(out["delta"][c, k, l]) / math.sqrt(var)
+                    out["p"][c, k, l] = math.erfc(abs(z) / math.sqrt(2.0))
+    return out
+
+
+def mcnemar_from_sums(pair):
+    """pair int [C, M, M, 6] -> float64 [C, M, M]: the exact two-sided binomial (McNemar) p-value of every ordered pair from
+    b = K_ONLY and c = L_ONLY, the rows on which exactly one of the two models is right:
+        p = min(1, 2 * sum_{i <= min(b, c)} comb(b + c, i) / 2^(b + c))
+    as one integer ratio and one division; 1.0 when b == c == 0.  With n = b + c and lo = min(b, c) the doubled tail is
+    reached by the shorter of two exact routes: the sum itself, from its largest term math.comb(n, lo) down by the
+    recurrence C(n, i-1) = C(n, i) * i / (n-i+1); or, the rows of Pascal's triangle being symmetric, 2^n minus the middle
+    terms lo < i < n - lo, from math.comb(n, lo + 1) up by C(n, i+1) = C(n, i) * (n-i) / (i+1).  Two models that disagree
+    on thousands of rows are about equally often right alone, so the middle is a few hundred terms where the tail is
+    thousands: one big-integer step per term either way, never one binomial coefficient from scratch per term.  (k, l) and
+    (l, k) share their value."""
+    import math
+    q = _host(pair, np.int64)
+    out = np.ones(q.shape[:-1], np.float64)
+    seen = {}
+    for idx in np.ndindex(*q.shape[:-1]):
+        b, c = int(q[idx + (P_K_ONLY,)]), int(q[idx + (P_L_ONLY,)])
+        n, lo = b + c, min(b, c)
+        if (n, lo) not in seen:
+            middle = n - 2 * lo - 1                         # the number of terms strictly between the two tails
+            if middle <= 0:                                 # b == c, or they differ by one: the doubled tail is >= 2^n
+                seen[(n, lo)] = 1.0
+            else:
+                if lo + 1 <= middle:
+                    term = total = math.comb(n, lo)
+                    for i in range(lo, 0, -1):
+                        term = term * i // (n - i + 1)      # exact: term is C(n, i) and becomes C(n, i-1)
+                        total += term
+                    num = 2 * total
+                else:
+                    term = total = math.comb(n, lo + 1)
+                    for i in range(lo + 1, n - lo - 1):
+                        term = term * (n - i) // (i + 1)    # exact: term is C(n, i) and becomes C(n, i+1)
+                        total += term
+                    num = (1 << n) - total
+                seen[(n, lo)] = _ratio(num, 1 << n)         # below 1: at least one middle term is missing from it
+        out[idx] = seen[(n, lo)]
+    return out
+
+
+def _percentiles(reps, alpha):
+    """(lo, hi, n_nan) of replicates [n_boot, ...] along axis 0, NaN replicates left out — bootstrap_metrics' rule."""
+    q = (100.0 * alpha / 2, 100.0 * (1 - alpha / 2))
+    cols = reps.reshape(reps.shape[0], -1)
+    bounds = np.array([np.percentile(col[~np.isnan(col)], q) if (~np.isnan(col)).any() else (np.nan, np.nan)
+                       for col in cols.T]).reshape(reps.shape[1:] + (2,))
+    return bounds[..., 0], bounds[..., 1], np.isnan(reps).sum(0)
+
+
+def compare_models(y_true, probs, names=None, threshold=0.5, n_boot=0, seed=0, alpha=0.05):
+    """Paired comparison of M <= 8 models scored on the SAME rows: y_true [N, C] and probs, a sequence or a mapping (name ->
+    tensor) of [N, C] device tensors.  Per model one metrics_order, one metrics_counts and one metrics_placements; then one
+    metrics_paired_sums and ONE host read.  Returns
+        "names"      the models' names (the mapping's keys, `names`, or "0", "1", ...)
+        "models"     per name, the keys of compute_metrics_device
+        "nonfinite"  int [M, C], metrics_order's count of NaN / +-inf per (model, class)
+        "pairs"      per ordered pair (name_k, name_l), k != l:  per class [C] "delta_auroc" = theta_k - theta_l, "var", "z",
+                     "p_delong" (delong_from_sums), "k_only", "l_only", "p_mcnemar" (mcnemar_from_sums, at `threshold`);
+                     "delta_auroc_macro", "delta_auprc_macro", "delta_f1_macro" = the difference of the two models' values.
+    The per-class values follow the key order with NaN ranked last, as summarize's do; a macro value is NaN under summarize's
+    rules (any non-finite probability makes auroc_macro and auprc_macro NaN), so those macro deltas are NaN if either model
+    is dirty.  DeLong's test has no macro form: the macro deltas get intervals from the bootstrap only.
+    With n_boot > 0 the bootstrap is PAIRED: one bootstrap_weights(N, n_boot, seed, device) serves every model, and per pair
+    "bootstrap" holds, for each of summarize's six keys, {"point", "lo", "hi"} of the replicate-wise DIFFERENCE (percentiles
+    alpha/2 and 1 - alpha/2 over the replicates where it is not NaN), with "n_nan" and "replicates" per key beside it.
+    Intervals of two separate bootstrap_metrics calls say nothing about a difference; these do."""
+    if isinstance(probs, dict):
+        names, probs = list(probs.keys()) if names is None else list(names), list(probs.values())
+    else:
+        probs = list(probs)
+        names = [str(i) for i in range(len(probs))] if names is None else list(names)
+    M = len(probs)
+    if not 1 <= M <= MAX_MODELS or len(names) != M or len(set(names)) != M:
+        raise L.EcgHipError(f"compare_models: {M} models and names {names}: 1 to {MAX_MODELS} models, one distinct name each")
+    for name, p in zip(names, probs):
+        if torch.is_tensor(p) and p.is_cuda and not p.is_contiguous():
+            raise L.EcgHipError(f"compare_models: the probabilities of model {name!r} must be contiguous")
+    y = None
+    ps = []
+    for p in probs:
+        y, p = _inputs(y_true, p)
+        ps.append(p)
+    N, C = y.shape
+    if any(p.shape != y.shape for p in ps):
+        raise L.EcgHipError(f"compare_models: every model needs probabilities of y_true's shape {tuple(y.shape)}, got "
+                            f"{[tuple(p.shape) for p in ps]}")
+    w = bootstrap_weights(N, int(n_boot), seed, y.device) if n_boot > 0 else None
+    B = 1 + max(int(n_boot), 0)
+    flat, places = [], []
+    for p in ps:
+        order, nonfinite = metrics_order(p)
+        fields, ap = metrics_counts(p, y, order=order, weights=w, threshold=threshold)
+        places.append(metrics_placements(p, y, order=order))
+        flat += [fields.reshape(-1), ap.view(torch.int64).reshape(-1), nonfinite.to(torch.int64)]
+    single, pair = metrics_paired_sums(torch.stack(places), torch.stack(ps), y, threshold=threshold)
+    host = torch.cat(flat + [single.reshape(-1), pair.reshape(-1)]).cpu().numpy()      # the one read
+    per, at = B * C * len(FIELDS) + B * C + C, 0
+    summaries, nonf = [], np.empty((M, C), np.int64)
+    for k in range(M):
+        blk = host[k * per:(k + 1) * per]
+        f = blk[:B * C * len(FIELDS)].reshape(B, C, len(FIELDS))
+        a = np.ascontiguousarray(blk[B * C * len(FIELDS):B * C * (len(FIELDS) + 1)]).view(np.float64).reshape(B, C)
+        nonf[k] = blk[B * C * (len(FIELDS) + 1):]
+        summaries.append(summarize(f, a))
+    at = M * per
+    s_host = host[at:at + single.numel()].reshape(single.shape)
+    q_host = host[at + single.numel():].reshape(pair.shape)
+    dl, mc = delong_from_sums(s_host, q_host), mcnemar_from_sums(q_host)
+    out = {"names": names, "nonfinite": nonf, "pairs": {},
+           "models": {nm: {k: (float(v[0]) if k in MACRO_KEYS else v[0]) for k, v in s.items()} for nm, s in zip(names, summaries)}}
+    for k in range(M):
+        for l in range(M):
+            if k == l:
+                continue
+            d = {"delta_auroc": dl["delta"][:, k, l], "var": dl["var"][:, k, l], "z": dl["z"][:, k, l],
+                 "p_delong": dl["p"][:, k, l], "k_only": q_host[:, k, l, P_K_ONLY], "l_only": q_host[:, k, l, P_L_ONLY],
+                 "p_mcnemar": mc[:, k, l]}
+            for key in MACRO_KEYS:
+                d["delta_" + key] = float(summaries[k][key][0] - summaries[l][key][0])
+            if n_boot > 0:
+                d["bootstrap"], d["n_nan"], d["replicates"] = {}, {}, {}
+                for key in summaries[k]:
+                    diff = summaries[k][key] - summaries[l][key]
+                    lo, hi, n_nan = _percentiles(diff[1:], alpha)
+                    scalar = key in MACRO_KEYS
+                    d["bootstrap"][key] = {"point": float(diff[0]) if scalar else diff[0], "lo": float(lo) if scalar else lo,
+                                           "hi": float(hi) if scalar else hi}
+                    d["n_nan"][key] = int(n_nan) if scalar else n_nan
+                    d["replicates"][key] = diff[1:]
+            out["pairs"][(names[k], names[l])] = d
     return out
 
 

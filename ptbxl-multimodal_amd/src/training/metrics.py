@@ -1,10 +1,11 @@
 """Macro AUROC / AUPRC / F1 for multi-label predictions (reference src/training/metrics.py:5-42).
 Epoch-end, host-side, O(N*C) on a few thousand rows: stays on sklearn.
-compute_metrics_device (ecg_hip/metrics.py, re-exported here) gives the same three numbers from device tensors."""
+compute_metrics_device (ecg_hip/metrics.py, re-exported here) gives the same three numbers from device tensors, and
+compare_models beside it says whether two models scored on the same rows differ (DeLong, McNemar, paired bootstrap)."""
 import numpy as np
 from sklearn import metrics as skm
 
-from ecg_hip.metrics import compute_metrics_device  # noqa: F401
+from ecg_hip.metrics import compare_models, compute_metrics_device  # noqa: F401
 
 
 def _nan_on_value_error(fn, *args, **kw):

@@ -1,6 +1,7 @@
 """Epoch-end metrics: the device path (ecg_hip.metrics) against what it replaces.
 
     python tools/bench_metrics.py [--sizes 2198 21799] [--classes 5] [--n-boot 1000] [--host-reps 50] [--out profiles/metrics_bench.json]
+                                  [--legs metrics compare]
 
 Per (N, C), on seeded synthetic predictions of a PTB-XL fold's shape, one JSON line with:
   compute_metrics_device   device tensors -> the three macro numbers on the host (two calls of two launches, one read), against
@@ -9,6 +10,10 @@ Per (N, C), on seeded synthetic predictions of a PTB-XL fold's shape, one JSON l
   metrics_order            against torch.argsort(columns, stable=True, descending=True), both from device events;
   bootstrap_metrics        at B = n_boot, against a host loop of compute_metrics over rows drawn by the SAME multiplicities:
                            --host-reps replicates are timed and the time is SCALED to n_boot ("host_loop_scaled": true).
+--legs compare adds (or, alone, refreshes in the existing file) a "compare" entry per size: compare_models on two models
+of the same rows at n_boot = 0 and at --n-boot, against
+  host_numpy_delong        the copy of both models to the host plus DeLong's test by fp64 midranks in numpy and McNemar's counts, and
+  torch_device_ops         the same integers (placements by sort + searchsorted, the paired sums) from torch ops, one read.
 The baselines are those paths, never the code under test.  Whole-call times are host clocks around work that ends in a device
 read; the legs of a comparison run alternately in one process and the minimum of the rounds is kept; each leg is primed by
 time first.  Values are checked too: the device numbers against sklearn's within N * 2^-50.
@@ -86,6 +91,121 @@ def torch_device_metrics(y, p, threshold=0.5):
     return {"auroc_macro": float(out[0]), "auprc_macro": float(out[1]), "f1_macro": float(out[2])}
 
 
+def _midranks(x):
+    """fp64 midranks of the rows of x [R, n] (1-based), by one argsort per row."""
+    order = np.argsort(x, axis=1, kind="stable")
+    out = np.empty(x.shape)
+    for r in range(x.shape[0]):
+        xs = x[r, order[r]]
+        first = np.flatnonzero(np.append(True, xs[1:] != xs[:-1]))
+        size = np.diff(np.append(first, len(xs)))
+        out[r, order[r]] = np.repeat(first + 0.5 * (size + 1), size)
+    return out
+
+
+def host_numpy_compare(y, probs, threshold=0.5):
+    """DeLong's test (Sun & Xu's midrank form) and McNemar's counts per class on host arrays: probs [M, N, C], y [N, C]."""
+    import math
+    from ecg_hip.metrics import mcnemar_from_sums
+    M, N, C = probs.shape
+    out = {"theta": np.empty((C, M)), "z": np.empty(C), "p": np.empty(C)}
+    pair = np.zeros((C, 2, 2, 6), np.int64)
+    for c in range(C):
+        pos = y[:, c] == 1.0
+        m, n = int(pos.sum()), int(N - pos.sum())
+        x, yy = probs[:, pos, c].astype(np.float64), probs[:, ~pos, c].astype(np.float64)
+        tz, tx, ty = _midranks(np.concatenate([x, yy], 1)), _midranks(x), _midranks(yy)
+        v10, v01 = (tz[:, :m] - tx) / n, 1.0 - (tz[:, m:] - ty) / m
+        theta = v10.mean(1)
+        cov = np.cov(v10) / m + np.cov(v01) / n
+        var = cov[0, 0] + cov[1, 1] - 2 * cov[0, 1]
+        z = (theta[0] - theta[1]) / math.sqrt(var) if var > 0 else float("nan")
+        out["theta"][c], out["z"][c], out["p"][c] = theta, z, math.erfc(abs(z) / math.sqrt(2.0))
+        right = (probs[:, :, c] >= np.float32(threshold)) == pos
+        pair[c, 0, 1, 2], pair[c, 0, 1, 3] = (right[0] & ~right[1]).sum(), (~right[0] & right[1]).sum()
+    out["p_mcnemar"] = mcnemar_from_sums(pair)[:, 0, 1]
+    return out
+
+
+def torch_device_compare(y, ps, threshold=0.5):
+    """The integers of ecg_metrics_placements and ecg_metrics_paired_sums from stock torch ops on the device (finite scores,
+    labels 0 / 1), one read, then the same host arithmetic as compare_models."""
+    from ecg_hip.metrics import delong_from_sums, mcnemar_from_sums
+    yt = y.t().contiguous()
+    posm = yt == 1.0
+    m, n = posm.sum(1, keepdim=True), (~posm).sum(1, keepdim=True)
+    inf = torch.full_like(yt, float("inf"))
+    places, rights = [], []
+    for p in ps:
+        pt = p.t().contiguous()
+        negs, poss = torch.where(posm, inf, pt).sort(1).values, torch.where(posm, pt, inf).sort(1).values
+        a = torch.searchsorted(negs, pt, right=False) + torch.searchsorted(negs, pt, right=True)
+        b = 2 * m - torch.searchsorted(poss, pt, right=False) - torch.searchsorted(poss, pt, right=True)
+        places.append(torch.where(posm, a, b))
+        rights.append((pt >= threshold) == posm)
+    M = len(ps)
+    single = torch.stack([torch.stack([(places[k] * posm).sum(1), m[:, 0], n[:, 0]], -1) for k in range(M)], 1)
+    pair = torch.stack([torch.stack([torch.stack([(places[k] * places[l] * posm).sum(1), (places[k] * places[l] * ~posm).sum(1),
+                                                  (rights[k] & ~rights[l]).sum(1), (~rights[k] & rights[l]).sum(1),
+                                                  (rights[k] & rights[l]).sum(1), (~rights[k] & ~rights[l]).sum(1)], -1)
+                                     for l in range(M)], 1) for k in range(M)], 1)
+    host = torch.cat([single.reshape(-1), pair.reshape(-1)]).cpu().numpy()
+    s, q = host[:single.numel()].reshape(single.shape), host[single.numel():].reshape(pair.shape)
+    return s, q, delong_from_sums(s, q), mcnemar_from_sums(q)
+
+
+def bench_compare(a):
+    """{N: the "compare" entry}: compare_models for two models of the same rows against its two counterparts."""
+    from ecg_hip import _lib, metrics as M
+    _lib.call("ecg_check_device")
+    warnings.simplefilter("ignore")
+    dev, out = torch.device("cuda"), {}
+    for N in a.sizes:
+        C = a.classes
+        rng = np.random.default_rng(N)
+        y = (rng.random((N, C)) < 0.25).astype(np.float32)
+        shared = rng.standard_normal((N, C))
+        p = np.stack([1.0 / (1.0 + np.exp(-(0.8 * shared + 0.6 * rng.standard_normal((N, C)) + g * y - 1.0)))
+                      for g in (1.5, 1.6)]).astype(np.float32)
+        yd, pds = torch.from_numpy(y).to(dev), [torch.from_numpy(q).to(dev) for q in p]
+        legs = {"compare_models": lambda: M.compare_models(yd, pds),
+                "host_numpy_delong": lambda: host_numpy_compare(yd.cpu().numpy(), np.stack([q.cpu().numpy() for q in pds])),
+                "torch_device_ops": lambda: torch_device_compare(yd, pds)}
+        got, ref, (s, q, dl, mc) = legs["compare_models"](), legs["host_numpy_delong"](), legs["torch_device_ops"]()
+        d = got["pairs"][("0", "1")]
+        worst_z = float(np.abs(d["z"] - ref["z"]).max())
+        assert worst_z <= 1e-6 * max(1.0, float(np.abs(ref["z"]).max())), worst_z      # fp64 midranks against exact integers
+        assert np.array_equal(d["p_mcnemar"], ref["p_mcnemar"])
+        assert np.array_equal(d["z"], dl["z"][:, 0, 1]) and np.array_equal(d["p_mcnemar"], mc[:, 0, 1])
+        whole = alternately(legs, {"compare_models": 30, "host_numpy_delong": 3, "torch_device_ops": 10}, wall_ms)
+        boot_ms = wall_ms(lambda: M.compare_models(yd, pds, n_boot=a.n_boot, seed=0), 3, 0.5)
+        with _lib.kernel_timing() as kt:
+            for _ in range(10):
+                M.compare_models(yd, pds)
+        entry_ms = {n: float(np.mean(v)) for (n, _), v in kt.result.items()}
+        boot = M.compare_models(yd, pds, n_boot=a.n_boot, seed=0)["pairs"][("0", "1")]
+        host_ms = []                                        # the share of every leg that is Python integers on the host
+        for _ in range(5):
+            t0 = time.perf_counter()
+            M.delong_from_sums(s, q), M.mcnemar_from_sums(q)
+            host_ms.append((time.perf_counter() - t0) * 1e3)
+        line = {"config": {"workload": f"compare_models, 2 models of {N} x {C} fp32 predictions on one MI355X", "N": N, "C": C, "M": 2},
+                "whole_call_ms": {k: round(v, 4) for k, v in whole.items()},
+                "host_numpy_delong_over_device": round(whole["host_numpy_delong"] / whole["compare_models"], 2),
+                "torch_device_ops_over_device": round(whole["torch_device_ops"] / whole["compare_models"], 2),
+                "compare_models_ms_at_n_boot": {"n_boot": a.n_boot, "ms": round(boot_ms, 3)},
+                "entry_point_ms": {k: round(v, 4) for k, v in entry_ms.items()},
+                "host_integer_arithmetic_ms": round(min(host_ms), 4),
+                "max_abs_z_diff_to_numpy": worst_z,
+                "delta_auroc": d["delta_auroc"].tolist(), "z": d["z"].tolist(), "p_delong": d["p_delong"].tolist(),
+                "p_mcnemar": d["p_mcnemar"].tolist(),
+                "delta_auroc_macro": {k: boot["bootstrap"]["auroc_macro"][k] for k in ("point", "lo", "hi")}}
+        print(json.dumps({"metric": "compare_models_ms", "value": line["whole_call_ms"]["compare_models"], "unit": "ms", **line}),
+              flush=True)
+        out[N] = line
+    return out
+
+
 def bench(a):
     from ecg_hip import _lib, metrics as M
     from src.training.metrics import compute_metrics
@@ -159,8 +279,21 @@ def main():
     ap.add_argument("--n-boot", type=int, default=1000)
     ap.add_argument("--host-reps", type=int, default=50)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "metrics_bench.json"))
+    ap.add_argument("--legs", nargs="+", choices=("metrics", "compare"), default=["metrics"])
     a = ap.parse_args()
-    res = bench(a)
+    if "metrics" in a.legs:
+        res = bench(a)
+    else:                                                   # refresh "compare" in the entries the file already has
+        with open(a.out) as f:
+            res = json.load(f)
+    if "compare" in a.legs:
+        for N, entry in bench_compare(a).items():
+            for line in res:
+                if line["config"]["N"] == N and line["config"]["C"] == a.classes:
+                    line["compare"] = entry
+                    break
+            else:
+                res.append({"config": entry["config"], "compare": entry})
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
