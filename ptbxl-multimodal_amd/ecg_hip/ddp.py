@@ -20,6 +20,8 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
+from . import params as P
+
 
 def init_distributed(backend=None, timeout_s=None):
     """Read RANK / WORLD_SIZE / LOCAL_RANK / MASTER_* from the environment (torchrun contract).
@@ -104,17 +106,12 @@ class FlatGradDDP(nn.Module):
             for p in self._params:
                 p.register_post_accumulate_grad_hook(self._on_grad)
             # the one all-reduce is issued from the hook of the LAST gradient, i.e. behind every backward kernel on the
-            # stream: nothing communicates while the BatchNorm backward kernels run ("quiet", functional.py)
+            # stream: nothing communicates while the BatchNorm backward kernels run ("quiet", params.py)
             if self._params and self._params[0].is_cuda:
-                import weakref
-                from . import functional as F
                 # (an optimizer that re-homes the parameters later and states its own exchange mode overrides this, as it
-                # should: a hooked FlatAdamW exchange IS busy under backward; a stock / adopted optimizer says nothing)
-                token = ("FlatGradDDP", id(self))
-                F.declare_backward_collectives(self._params, False, owner=token)
-                # withdraw the statement when the wrapper goes away (by object id + owner token: a later parameter that
-                # reuses an id was declared by someone else and keeps its statement)
-                weakref.finalize(self, F.declare_backward_collectives, [id(p) for p in self._params], None, token)
+                # should: a hooked FlatAdamW exchange IS busy under backward; a stock / adopted optimizer says nothing);
+                # withdrawn when the wrapper goes away
+                P.declare_backward_collectives(self._params, False, owner=P.owner_token(self))
 
     def _on_grad(self, _param):
         self._pending += 1

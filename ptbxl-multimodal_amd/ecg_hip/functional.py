@@ -5,11 +5,13 @@ torch's current stream; torch only owns the memory.  Hand-written backward formu
 the ones restated (and pinned against the reference) in oracle/ecg_oracle.c.
 """
 import functools
+import os as _os
 
 import torch
 
 from . import _lib as L
 from . import eval_bf16 as _EB
+from . import params as P
 
 _call, _query, _f32, _st = L.call, L.query, L.f32, L.stream
 
@@ -18,139 +20,14 @@ def _empty(ref, *shape):
     return torch.empty(shape, dtype=torch.float32, device=ref.device)
 
 
-# --------------------------------------------------------------------------------------
-# Gradient sinks.  FlatAdamW keeps ONE flat gradient buffer; when it registers a view of that buffer for
-# a parameter, the backward kernels write that parameter's gradient straight into it and autograd's
-# AccumulateGrad adopts the view as `.grad` (no copy) — the optimizer's per-step gather (`torch.cat` of
-# ~28 tensors) and the all-reduce staging disappear.  A sink is only handed out while the parameter's
-# `.grad` is None (zero_grad(set_to_none=True), the default): if a gradient is already there, autograd will
-# ADD the new one to it, and the kernel must not have overwritten the accumulated value.
-# --------------------------------------------------------------------------------------
-import weakref as _weakref
+# Gradient sinks and collectives statements — what is known about a parameter, asked by the address of the weight a
+# backward wrapper was given — live in params.py; the public names stay reachable here.
+_grad_out = P.grad_out
+register_grad_sinks, unregister_grad_sinks = P.register_grad_sinks, P.unregister_grad_sinks
+declare_backward_collectives, parameters_rehomed = P.declare_backward_collectives, P.parameters_rehomed
+bn_backward_one_launch_allowed, set_bn_backward_one_launch = P.bn_backward_one_launch_allowed, P.set_bn_backward_one_launch
 
-_grad_sinks = {}          # parameter data_ptr -> (weakref(parameter), flat view)
-
-
-def register_grad_sinks(params, views):
-    for p, v in zip(params, views):
-        _grad_sinks[p.data_ptr()] = (_weakref.ref(p), v)
-
-
-def unregister_grad_sinks(keys):
-    for k in keys:
-        _grad_sinks.pop(k, None)
-
-
-_sinks_handed = set()     # sinks already given to a kernel in the backward pass that is running now
-
-
-def _forget_handed_sinks():
-    _sinks_handed.clear()
-
-
-def _grad_out(key, ref, *shape):
-    """Destination of a parameter gradient: a FRESH view of the registered sink (AccumulateGrad only adopts
-    a tensor nobody else holds) or a new tensor.  A sink is handed out AT MOST ONCE per backward pass: a
-    parameter used twice in one graph (model called twice before backward(), shared weights) gets a private
-    tensor for its second gradient, which autograd then adds to the first — two kernels writing the same
-    sink would leave 2*dw2 instead of dw1 + dw2.  The set is cleared by an engine callback when the pass ends — and,
-    because the engine runs no callbacks for a backward pass that RAISED, again whenever a new step begins
-    (backward_from_loss, FlatAdamW.zero_grad / step): one failed backward must not disable the sinks for good."""
-    ent = _grad_sinks.get(key) if key is not None else None
-    if ent is not None and key not in _sinks_handed:
-        p, v = ent[0](), ent[1]
-        if p is not None and p.grad is None and v.device == ref.device and v.numel() == _numel(shape):
-            try:
-                if not _sinks_handed:
-                    torch.autograd.Variable._execution_engine.queue_callback(_forget_handed_sinks)
-                _sinks_handed.add(key)
-            except RuntimeError:         # not inside a backward pass (direct call of a backward formula): no tracking
-                return torch.empty(shape, dtype=torch.float32, device=ref.device)
-            return v.view(shape)
-    return torch.empty(shape, dtype=torch.float32, device=ref.device)
-
-
-# --------------------------------------------------------------------------------------
-# The one-launch BatchNorm backward (csrc/bn_relu_pool.hip, bn_bwd_resident_kernel) and collectives.
-# Its workgroups exchange partial sums through a bounded wait, which is only instant while every workgroup of the grid
-# is resident.  A communication kernel that runs DURING backward and waits for a late peer keeps its CUs; this kernel's
-# workgroups would then run out their wait and take the slow self-service path on every call.  The decision is taken
-# PER CALL, from what is known about the parameters of the block whose backward is running — no process-wide switch:
-#   * the owner of the parameters (FlatAdamW, FlatGradDDP) declares "busy" (its hooks issue all-reduces under backward)
-#     or "quiet" (its exchange starts after the last backward kernel);
-#   * parameters nobody has declared are quiet in a single-rank process and BUSY as soon as torch.distributed runs more
-#     than one rank — so a model wrapped in stock torch.nn.parallel.DistributedDataParallel (bucketed all-reduces under
-#     backward, invisible from here) gets the two-pass form without having to ask for it.
-# ECG_BN_BWD_RESIDENT=0 keeps the two-pass form everywhere; ECG_HIP_REHEARSE_ON_ONE_GPU=1 (several ranks sharing ONE
-# device: workgroups of different processes would wait for each other's CUs) does the same.  Read here, on the host side
-# of the ABI: the library reads no environment.
-# --------------------------------------------------------------------------------------
-import os as _os
-
-_bn_one_launch = (_os.environ.get("ECG_BN_BWD_RESIDENT", "1") != "0"
-                  and _os.environ.get("ECG_HIP_REHEARSE_ON_ONE_GPU") != "1")
-_bn_spin_polls = int(_os.environ.get("ECG_BN_BWD_RESIDENT_SPIN", "-1"))     # tests: 0 = nobody waits (self-service path)
-_backward_collectives = {}      # id(parameter) -> (weakref(parameter), busy, owner): keyed by the OBJECT, not its address —
-                                # FlatAdamW / adopt_stock_adamw re-home parameter storage after a wrapper has spoken
-_collectives_by_ptr = None      # {data_ptr now: busy}, rebuilt lazily after a declaration or a re-homing
 _bn_counters = {}               # (device index, raw stream) -> zeroed int32 tensor: the kernel's exchange words
-
-
-def set_bn_backward_one_launch(on, spin_polls=None):
-    """Process default for the one-launch BatchNorm backward (True unless the environment says otherwise); returns the
-    previous setting.  `spin_polls` (tests) bounds the inter-workgroup wait: 0 forces the self-service path."""
-    global _bn_one_launch, _bn_spin_polls
-    prev, _bn_one_launch = _bn_one_launch, bool(on)
-    if spin_polls is not None:
-        _bn_spin_polls = int(spin_polls)
-    return prev
-
-
-def declare_backward_collectives(params, busy, owner=None):
-    """The owner of `params` says whether collectives can run on the device while their backward kernels do (True: the
-    BatchNorm backward of their blocks keeps the two-pass form), that they cannot (False), or withdraws its statement
-    (None; with an `owner` token only a statement made under the same token is withdrawn, so an optimizer going away
-    does not take a live wrapper's statement with it).  `params` are the parameter tensors themselves (or their id()s,
-    for a withdrawal from a finalizer).  Cheap; call it whenever the exchange mode changes."""
-    global _collectives_by_ptr
-    for p in params:
-        k = p if isinstance(p, int) else id(p)
-        if busy is None:
-            ent = _backward_collectives.get(k)
-            if ent is not None and (owner is None or ent[2] == owner):
-                del _backward_collectives[k]
-        elif not isinstance(p, int):
-            _backward_collectives[k] = (_weakref.ref(p), bool(busy), owner)
-    _collectives_by_ptr = None
-
-
-def parameters_rehomed():
-    """Parameter storage moved (flatten_tensors_): the address -> statement table is rebuilt at the next backward."""
-    global _collectives_by_ptr
-    _collectives_by_ptr = None
-
-
-def _multi_rank():
-    d = torch.distributed
-    return d.is_available() and d.is_initialized() and d.get_world_size() > 1
-
-
-def bn_backward_one_launch_allowed(key):
-    """The per-call decision described above for the block whose conv weight has data_ptr `key`."""
-    global _collectives_by_ptr
-    if not _bn_one_launch:
-        return False
-    if _collectives_by_ptr is None:
-        tab = {}
-        for k, (ref, busy, _owner) in list(_backward_collectives.items()):
-            p = ref()
-            if p is None:
-                del _backward_collectives[k]          # the parameter is gone (and its id may be reused)
-            else:
-                tab[p.data_ptr()] = busy
-        _collectives_by_ptr = tab
-    busy = _collectives_by_ptr.get(key)
-    return (not _multi_rank()) if busy is None else (not busy)
 
 
 def _bn_bwd_counters(ref, n_uints):
@@ -166,13 +43,6 @@ def _bn_bwd_counters(ref, n_uints):
         t = torch.zeros(max(n_uints, 4352), dtype=torch.int32, device=ref.device)
         _bn_counters[key] = t
     return t
-
-
-def _numel(shape):
-    n = 1
-    for d in shape:
-        n *= int(d)
-    return n
 
 
 def _key(t):
@@ -586,7 +456,7 @@ class ConvBlockFn(torch.autograd.Function):
             cnt = _bn_bwd_counters(y, n_u) if n_u else None
             _call("ecg_bn_relu_pool_bwd_one_launch", _f32(y), _f32(dp), _f32(gamma), _f32(beta), _f32(mean),
                   _f32(invstd), _f32(dy), ldy, _f32(dgamma), _f32(dbeta), L.ptr(cnt), N, Co, Lo,
-                  1 if ctx.batch_stats else 0, 1 if ctx.gap else 0, _bn_spin_polls, _st())
+                  1 if ctx.batch_stats else 0, 1 if ctx.gap else 0, P._bn_spin_polls, _st())
         else:
             ws = _empty(y, _query("ecg_bn_relu_pool_bwd_ws_floats", N, Co, Lo))
             _call("ecg_bn_relu_pool_gap_bwd_ld" if ctx.gap else "ecg_bn_relu_pool_bwd_ld", _f32(y), _f32(dp),
@@ -728,7 +598,7 @@ def backward_from_loss(loss):
     one = _unit_grads.get(loss.device)
     if one is None:
         one = _unit_grads[loss.device] = torch.ones((), dtype=loss.dtype, device=loss.device)
-    _sinks_handed.clear()                  # left over only if an earlier backward pass raised (no engine callback then)
+    P.forget_handed_sinks()                # left over only if an earlier backward pass raised (no engine callback then)
     loss.backward(one)
 
 

@@ -18,6 +18,7 @@ import torch
 import torch.optim.optimizer as _opt_mod
 
 from . import _lib as L
+from . import params as P
 
 
 def flatten_tensors_(tensors):
@@ -36,10 +37,69 @@ def flatten_tensors_(tensors):
         view.copy_(t.detach())
         t.data = view
         off += n
-    if flat.is_cuda:
-        from . import functional as F
-        F.parameters_rehomed()           # statements keyed by parameter object stay; their addresses are looked up afresh
+    P.parameters_rehomed()               # sinks and statements follow the parameter objects to their new addresses
     return flat
+
+
+class _FlatState:
+    """What FlatAdamW and AdoptedAdamW both step: the parameters as views of ONE flat buffer, the two AdamW moments and
+    a persistent flat gradient.  The backward kernels write each parameter's gradient straight into its slice of that
+    gradient (params.register_grad_sinks; withdrawn when this object is collected), so `gather` usually has nothing to do."""
+
+    def __init__(self, params):
+        self.params = params
+        self.param = flatten_tensors_(params)
+        self.m, self.v, self.grad = (torch.zeros_like(self.param) for _ in range(3))
+        self.offs = [0]
+        for p in params:
+            self.offs.append(self.offs[-1] + p.numel())
+        views = [self.grad[a:b] for a, b in zip(self.offs, self.offs[1:])]
+        self._gptrs = [v.data_ptr() for v in views]
+        self.owner = P.owner_token(self)
+        P.register_grad_sinks(params, views, self.owner)
+
+    def gather(self, lo, hi):
+        """Make the flat gradient hold the gradients of parameters lo..hi-1.  Nothing to do when every .grad
+        already IS its slice of the flat buffer (written there by the backward kernels); one concatenation
+        when none is; element-wise repair when only some are (a cat must not read what it overwrites)."""
+        ps = self.params[lo:hi]
+        placed = [p.grad is not None and p.grad.data_ptr() == q for p, q in zip(ps, self._gptrs[lo:hi])]
+        if all(placed):
+            return
+        if not any(placed):
+            torch.cat([(torch.zeros_like(p) if p.grad is None else p.grad).reshape(-1) for p in ps],
+                      out=self.grad[self.offs[lo]:self.offs[hi]])
+            return
+        for i, (p, ok) in enumerate(zip(ps, placed), start=lo):
+            if ok:
+                continue
+            dst = self.grad[self.offs[i]:self.offs[i + 1]]
+            if p.grad is None:
+                dst.zero_()
+            else:
+                dst.copy_(p.grad.reshape(-1))
+
+    def apply(self, step, grp, scale):
+        """One AdamW update of the whole flat buffer with the flat gradient times `scale`, hyper-parameters from the param
+        group `grp`.  `step` is the number of this step (the first is 1) — or the int32 device counter of a capturable
+        optimizer, which the kernel reads and bumps itself."""
+        (b1, b2), p, g, m, v = grp["betas"], self.param, self.grad, self.m, self.v
+        lr, eps, wd = float(grp["lr"]), float(grp["eps"]), float(grp["weight_decay"])
+        if torch.is_tensor(step) or g.is_cuda:
+            name, t = ("ecg_adamw_step_graph", L.ptr(step)) if torch.is_tensor(step) else ("ecg_adamw_step", step)
+            L.call(name, L.f32(p), L.f32(g), L.f32(m), L.f32(v), g.numel(), t, lr, float(b1), float(b2), eps, wd, scale,
+                   L.stream())
+            return
+        # CPU parameters (a GPU-less box): the same update with stock torch ops on the flat buffers —
+        # torch.optim.AdamW's single-tensor formula (decoupled decay, bias-corrected moments)
+        if scale != 1.0:
+            g = g * scale
+        p.mul_(1.0 - lr * wd)
+        m.lerp_(g, 1.0 - b1)
+        v.mul_(b2).addcmul_(g, g, value=1.0 - b2)
+        bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
+        denom = (v.sqrt() / (bc2 ** 0.5)).add_(eps)
+        p.addcdiv_(m, denom, value=-lr / bc1)
 
 
 class FlatAdamW(torch.optim.Optimizer):
@@ -59,24 +119,9 @@ class FlatAdamW(torch.optim.Optimizer):
         for p in self._params:
             if p.dtype != torch.float32:
                 raise L.EcgHipError("FlatAdamW: float32 parameters only")
-        self.flat_param = flatten_tensors_(self._params)
-        self.flat_m = torch.zeros_like(self.flat_param)
-        self.flat_v = torch.zeros_like(self.flat_param)
-        # persistent flat gradient; on the GPU the backward kernels write each parameter's gradient straight
-        # into its slice (functional.register_grad_sinks), so the per-step gather usually has nothing to do
-        self.flat_grad = torch.zeros_like(self.flat_param)
-        self._gptrs, self._offs, views, off = [], [0], [], 0
-        for p in self._params:
-            v = self.flat_grad[off:off + p.numel()]
-            views.append(v)
-            self._gptrs.append(v.data_ptr())
-            off += p.numel()
-            self._offs.append(off)
-        self._sink_keys = []
-        if self.flat_param.is_cuda:
-            from . import functional as F
-            F.register_grad_sinks(self._params, views)
-            self._sink_keys = [p.data_ptr() for p in self._params]
+        self._flat = f = _FlatState(self._params)
+        self.flat_param, self.flat_m, self.flat_v, self.flat_grad = f.param, f.m, f.v, f.grad
+        self._gather = f.gather
         self._step = 0
         self._step_dev = None            # device-side step counter (graph-capturable mode)
         self.process_group = process_group
@@ -112,44 +157,6 @@ class FlatAdamW(torch.optim.Optimizer):
                 p.register_post_accumulate_grad_hook(self._on_early_grad)
         self._note_overlap()
 
-    def __del__(self):
-        try:
-            from . import functional as F
-            F.unregister_grad_sinks(self._sink_keys)
-        except Exception:
-            pass
-        try:
-            if self.flat_param.is_cuda:
-                from . import functional as F
-                F.declare_backward_collectives(self._params, None, owner=id(self))     # only what this optimizer declared
-        except Exception:
-            pass
-
-    @staticmethod
-    def _flat(p):
-        g = p.grad
-        return torch.zeros_like(p).view(-1) if g is None else g.reshape(-1)
-
-    def _gather(self, lo, hi):
-        """Make the flat gradient hold the gradients of parameters lo..hi-1.  Nothing to do when every .grad
-        already IS its slice of the flat buffer (written there by the backward kernels); one concatenation
-        when none is; element-wise repair when only some are (a cat must not read what it overwrites)."""
-        ps = self._params[lo:hi]
-        placed = [p.grad is not None and p.grad.data_ptr() == q for p, q in zip(ps, self._gptrs[lo:hi])]
-        if all(placed):
-            return
-        if not any(placed):
-            torch.cat([self._flat(p) for p in ps], out=self.flat_grad[self._offs[lo]:self._offs[hi]])
-            return
-        for i, (p, ok) in enumerate(zip(ps, placed), start=lo):
-            if ok:
-                continue
-            dst = self.flat_grad[self._offs[i]:self._offs[i + 1]]
-            if p.grad is None:
-                dst.zero_()
-            else:
-                dst.copy_(p.grad.reshape(-1))
-
     def set_overlap(self, on):
         """Switch between the bucketed exchange issued from the backward hooks (True; needs `overlap=True` at
         construction) and ONE all-reduce of the whole flat gradient in step() (False).  Which is faster depends on the
@@ -169,8 +176,7 @@ class FlatAdamW(torch.optim.Optimizer):
         # never depends on a communication kernel leaving a CU); the single all-reduce in step() starts after the last
         # backward kernel ("quiet": the one-launch form).  Without an exchange nothing is declared.
         if self.flat_param.is_cuda and self._exchange:
-            from . import functional as F
-            F.declare_backward_collectives(self._params, bool(self._overlap_active), owner=id(self))
+            P.declare_backward_collectives(self._params, bool(self._overlap_active), owner=self._flat.owner)
 
     def calibrate_overlap(self, run_steps, steps=10, warm=3):
         """Pick the faster exchange form ON THIS NODE: `run_steps(n)` must run n complete train steps (forward,
@@ -292,55 +298,21 @@ class FlatAdamW(torch.optim.Optimizer):
         return g, 1.0
 
     def zero_grad(self, set_to_none=True):
-        self._forget_handed_sinks()
+        P.forget_handed_sinks()
         return super().zero_grad(set_to_none=set_to_none)
-
-    def _forget_handed_sinks(self):
-        """A backward pass that raised leaves functional._sinks_handed non-empty (the autograd engine runs no
-        end-of-pass callbacks then) and every later pass would get private gradient tensors instead of the flat-buffer
-        sinks, silently.  A new step starts from a clean slate."""
-        if self._sink_keys:
-            from . import functional as F
-            F._sinks_handed.clear()
 
     @torch.no_grad()
     def step(self, closure=None):
-        self._forget_handed_sinks()
+        P.forget_handed_sinks()
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        grp = self.param_groups[0]
-        g, scale = self.reduce_gradients()
-        b1, b2 = grp["betas"]
-        if self._step_dev is not None:        # capturable: the kernel reads and bumps the device counter
-            L.call("ecg_adamw_step_graph", L.f32(self.flat_param), L.f32(g), L.f32(self.flat_m),
-                   L.f32(self.flat_v), g.numel(), L.ptr(self._step_dev), float(grp["lr"]), float(b1),
-                   float(b2), float(grp["eps"]), float(grp["weight_decay"]), scale, L.stream())
-            return loss
-        self._step += 1
-        if g.is_cuda:
-            L.call("ecg_adamw_step", L.f32(self.flat_param), L.f32(g), L.f32(self.flat_m),
-                   L.f32(self.flat_v), g.numel(), self._step, float(grp["lr"]), float(b1), float(b2),
-                   float(grp["eps"]), float(grp["weight_decay"]), scale, L.stream())
-        else:
-            self._step_cpu(g, grp, scale)
+        _g, scale = self.reduce_gradients()
+        if self._step_dev is None:
+            self._step += 1
+        self._flat.apply(self._step if self._step_dev is None else self._step_dev, self.param_groups[0], scale)
         return loss
-
-    def _step_cpu(self, g, grp, scale):
-        """CPU parameters (a GPU-less box): the same update with stock torch ops on the flat buffers —
-        torch.optim.AdamW's single-tensor formula (decoupled decay, bias-corrected moments)."""
-        b1, b2 = grp["betas"]
-        lr, eps, wd, t = float(grp["lr"]), float(grp["eps"]), float(grp["weight_decay"]), self._step
-        if scale != 1.0:
-            g = g * scale
-        p, m, v = self.flat_param, self.flat_m, self.flat_v
-        p.mul_(1.0 - lr * wd)
-        m.lerp_(g, 1.0 - b1)
-        v.mul_(b2).addcmul_(g, g, value=1.0 - b2)
-        bc1, bc2 = 1.0 - b1 ** t, 1.0 - b2 ** t
-        denom = (v.sqrt() / (bc2 ** 0.5)).add_(eps)
-        p.addcdiv_(m, denom, value=-lr / bc1)
 
     def make_capturable(self):
         """Move the step counter to the device so `step()` can be captured in a HIP graph."""
@@ -373,7 +345,7 @@ class FlatAdamW(torch.optim.Optimizer):
 # tensors: 0.08 ms of host gap per step at B = 256 (round 4: 149.5 k windows/s against 160.7 k with FlatAdamW).
 # `adopt_stock_adamw` turns such an optimizer, IN PLACE, into one that steps through the same fused launch as FlatAdamW:
 #   * parameters become views of one flat buffer (values unchanged), gradients are written by the backward kernels straight
-#     into views of one flat gradient (functional.register_grad_sinks);
+#     into views of one flat gradient (params.register_grad_sinks);
 #   * `optimizer.state[p]` holds what stock AdamW would hold — `step` (a CPU scalar tensor), `exp_avg`, `exp_avg_sq` — the
 #     two moments being views of flat buffers, so `optimizer.state_dict()` is a stock AdamW state_dict: it loads into a fresh
 #     `torch.optim.AdamW` (and one saved by stock AdamW loads here) and training continues from it;
@@ -399,13 +371,23 @@ def _adoptable(opt, allow_cpu=False):
         return False
     if not (ps[0].is_cuda or allow_cpu):
         return False
+    return _adoptable_state(opt)
+
+
+def _uniform_step(opt, ps):
+    """The step count that EVERY parameter of `ps` has in opt.state beside both moments — only such a state fits one
+    launch — or None."""
     st = [opt.state.get(p) for p in ps]
-    if any(s for s in st):           # already stepped by stock torch: adopt its state — only a uniform one fits one launch
-        if not all(s and set(s) >= {"step", "exp_avg", "exp_avg_sq"} for s in st):
-            return False
-        if len({float(s["step"]) for s in st}) != 1:
-            return False
-    return True
+    if not all(s and set(s) >= {"step", "exp_avg", "exp_avg_sq"} for s in st):
+        return None
+    steps = {float(s["step"]) for s in st}
+    return int(steps.pop()) if len(steps) == 1 else None
+
+
+def _adoptable_state(opt):
+    """One group whose parameters have no state yet, or (already stepped by stock torch) a uniform one."""
+    ps = opt.param_groups[0]["params"] if len(opt.param_groups) == 1 else []
+    return bool(ps) and (not any(opt.state.get(p) for p in ps) or _uniform_step(opt, ps) is not None)
 
 
 class AdoptedAdamW(torch.optim.AdamW):
@@ -416,14 +398,12 @@ class AdoptedAdamW(torch.optim.AdamW):
         ps = list(grp["params"])
         old = [dict(self.state.get(p, {})) for p in ps]
         self._params = ps
-        self.flat_param = flatten_tensors_(ps)
-        self.flat_m, self.flat_v = torch.zeros_like(self.flat_param), torch.zeros_like(self.flat_param)
-        self.flat_grad = torch.zeros_like(self.flat_param)
-        self._offs, self._gptrs, self._pptrs, self._steps, gviews, off = [0], [], [], [], [], 0
+        self._flat = f = _FlatState(ps)      # (a state this replaces withdraws nothing: its sinks were just re-registered)
+        self.flat_param, self.flat_m, self.flat_v, self.flat_grad = f.param, f.m, f.v, f.grad
+        self._pptrs, self._steps = [p.data_ptr() for p in ps], []
         fused_steps = bool(grp.get("fused"))
-        for p, s in zip(ps, old):
-            n = p.numel()
-            m, v = self.flat_m[off:off + n].view(p.shape), self.flat_v[off:off + n].view(p.shape)
+        for p, s, a, b in zip(ps, old, f.offs, f.offs[1:]):
+            m, v = f.m[a:b].view(p.shape), f.v[a:b].view(p.shape)
             if s:
                 m.copy_(s["exp_avg"]); v.copy_(s["exp_avg_sq"])
                 step = s["step"]
@@ -432,26 +412,8 @@ class AdoptedAdamW(torch.optim.AdamW):
                         else torch.tensor(0.0, dtype=torch.get_default_dtype()))
             self.state[p] = {"step": step, "exp_avg": m, "exp_avg_sq": v}
             self._steps.append(step)
-            gv = self.flat_grad[off:off + n]
-            gviews.append(gv)
-            self._gptrs.append(gv.data_ptr())
-            self._pptrs.append(p.data_ptr())
-            off += n
-            self._offs.append(off)
-        self._step_count = int(float(self._steps[0]))
+        self._ecg_step_count = int(float(self._steps[0]))      # (`_step_count` belonged to torch's LR schedulers up to torch 2.3)
         self._uniform = True
-        self._sink_keys = []
-        if self.flat_param.is_cuda:
-            from . import functional as F
-            if not any(k in F._grad_sinks for k in self._pptrs):     # (a FlatGradDDP-style owner may hold them already)
-                F.register_grad_sinks(ps, gviews)
-                self._sink_keys = list(self._pptrs)
-                import weakref
-                weakref.finalize(self, F.unregister_grad_sinks, list(self._sink_keys))
-
-    _gather = FlatAdamW._gather
-    _flat = staticmethod(FlatAdamW._flat)
-    _step_cpu = FlatAdamW._step_cpu
 
     def _rehome_if_moved(self):
         """model.to(...) / p.data = ... after adoption re-points parameters: take them back into a fresh flat buffer
@@ -460,32 +422,12 @@ class AdoptedAdamW(torch.optim.AdamW):
             return True
         if any(p.device != self.flat_m.device or p.dtype != torch.float32 for p in self._params):
             return False
-        if self._sink_keys:
-            from . import functional as F
-            F.unregister_grad_sinks(self._sink_keys)
         self._adopt()          # (gradients that are views of the old flat gradient stay valid: the views keep it alive)
         return True
 
     def zero_grad(self, set_to_none=True):
-        if self._sink_keys:
-            from . import functional as F
-            F._sinks_handed.clear()
+        P.forget_handed_sinks()
         return super().zero_grad(set_to_none=set_to_none)
-
-    @torch.no_grad()
-    def _fused_step(self):
-        grp = self.param_groups[0]
-        self._gather(0, len(self._params))
-        self._step_count += 1
-        b1, b2 = grp["betas"]
-        if self.flat_param.is_cuda:
-            L.call("ecg_adamw_step", L.f32(self.flat_param), L.f32(self.flat_grad), L.f32(self.flat_m), L.f32(self.flat_v),
-                   self.flat_grad.numel(), self._step_count, float(grp["lr"]), float(b1), float(b2), float(grp["eps"]),
-                   float(grp["weight_decay"]), 1.0, L.stream())
-        else:
-            self._step = self._step_count
-            self._step_cpu(self.flat_grad, grp, 1.0)
-        torch._foreach_add_(self._steps, 1)
 
     def step(self, closure=None):
         if closure is not None or not self._uniform or len(self.param_groups) != 1 \
@@ -494,16 +436,18 @@ class AdoptedAdamW(torch.optim.AdamW):
             # stock semantics for everything the one launch does not cover; the state tensors are the flat views, so
             # torch's own step updates them in place and the fused form can resume when the step counts are still uniform
             out = _raw_stock_step()(self, closure)
-            steps = {float(s["step"]) for s in (self.state.get(p) for p in self._params) if s}
-            self._uniform = (len(steps) == 1 and all(self.state.get(p) for p in self._params)
-                             and len(self.param_groups) == 1 and len(self.param_groups[0]["params"]) == len(self._params))
+            step = _uniform_step(self, self._params)
+            self._uniform = (step is not None and len(self.param_groups) == 1
+                             and len(self.param_groups[0]["params"]) == len(self._params))
             if self._uniform:
-                self._step_count = int(steps.pop())
+                self._ecg_step_count = step
             return out
-        if self._sink_keys:
-            from . import functional as F
-            F._sinks_handed.clear()
-        self._fused_step()
+        P.forget_handed_sinks()
+        with torch.no_grad():
+            self._flat.gather(0, len(self._params))
+            self._ecg_step_count += 1
+            self._flat.apply(self._ecg_step_count, self.param_groups[0], 1.0)
+            torch._foreach_add_(self._steps, 1)
         return None
 
     # step pre / post hooks run as for any torch optimizer (Optimizer.__setstate__ would add this wrapper on its own the
@@ -516,9 +460,6 @@ class AdoptedAdamW(torch.optim.AdamW):
         flat buffers."""
         super().load_state_dict(state_dict)
         if _adoptable_state(self):
-            if self._sink_keys:
-                from . import functional as F
-                F.unregister_grad_sinks(self._sink_keys)
             self._adopt()
         else:
             self._uniform = False
@@ -528,14 +469,6 @@ def _raw_stock_step():
     """torch.optim.AdamW's own step WITHOUT torch's hook-running wrapper (AdoptedAdamW.step carries that wrapper itself)."""
     f = torch.optim.AdamW.step
     return f.__wrapped__ if getattr(f, "hooked", False) else f
-
-
-def _adoptable_state(opt):
-    ps = opt.param_groups[0]["params"] if len(opt.param_groups) == 1 else []
-    st = [opt.state.get(p) for p in ps]
-    if not ps or not any(st):
-        return bool(ps)
-    return all(s and set(s) >= {"step", "exp_avg", "exp_avg_sq"} for s in st) and len({float(s["step"]) for s in st}) == 1
 
 
 def adopt_stock_adamw(optimizer, allow_cpu=False):

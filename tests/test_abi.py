@@ -80,10 +80,10 @@ def test_one_launch_batchnorm_backward_is_decided_per_call_from_the_parameters(m
     one-launch form; undeclared parameters are quiet in a single-rank process and busy as soon as more than one rank
     exists (stock DistributedDataParallel users get the safe form without asking)."""
     import torch
-    from ecg_hip import functional as F
-    monkeypatch.setattr(F, "_bn_one_launch", True)
-    monkeypatch.setattr(F, "_backward_collectives", {})
-    monkeypatch.setattr(F, "_collectives_by_ptr", None)
+    from ecg_hip import functional as F, params as P
+    monkeypatch.setattr(P, "_bn_one_launch", True)
+    monkeypatch.setattr(P, "_records", {})
+    monkeypatch.setattr(P, "_by_ptr", {})
     a, b = torch.nn.Parameter(torch.zeros(3)), torch.nn.Parameter(torch.zeros(3))
     ka, kb = a.data_ptr(), b.data_ptr()
     assert F.bn_backward_one_launch_allowed(ka) and F.bn_backward_one_launch_allowed(kb)
@@ -91,18 +91,18 @@ def test_one_launch_batchnorm_backward_is_decided_per_call_from_the_parameters(m
     assert not F.bn_backward_one_launch_allowed(ka) and F.bn_backward_one_launch_allowed(kb)      # per parameter, not global
     F.declare_backward_collectives([a], False)
     assert F.bn_backward_one_launch_allowed(ka)
-    monkeypatch.setattr(F, "_multi_rank", lambda: True)
+    monkeypatch.setattr(P, "_multi_rank", lambda: True)
     assert F.bn_backward_one_launch_allowed(ka) and not F.bn_backward_one_launch_allowed(kb)      # undeclared + multi-rank
     F.declare_backward_collectives([a], None)
     assert not F.bn_backward_one_launch_allowed(ka)
-    monkeypatch.setattr(F, "_multi_rank", lambda: False)
+    monkeypatch.setattr(P, "_multi_rank", lambda: False)
     assert F.set_bn_backward_one_launch(False) is True
     assert not F.bn_backward_one_launch_allowed(ka) and not F.bn_backward_one_launch_allowed(kb)
     assert F.set_bn_backward_one_launch(True) is False
     # statements follow the parameter OBJECT: an optimizer that re-homes the storage afterwards (FlatAdamW, the adopted stock
     # AdamW) does not leave a wrapper's statement on a dead address, and an owner only withdraws what it said itself
     from ecg_hip.optim import flatten_tensors_
-    monkeypatch.setattr(F, "_multi_rank", lambda: True)
+    monkeypatch.setattr(P, "_multi_rank", lambda: True)
     F.declare_backward_collectives([a, b], False, owner="wrapper")
     old = (a.data_ptr(), b.data_ptr())
     flat = flatten_tensors_([a, b])

@@ -84,7 +84,7 @@ def test_checkpoint_of_an_adopted_optimizer_continues_in_stock_torch_and_back():
     oc = adopt_stock_adamw(torch.optim.AdamW(mc.parameters(), lr=1.0), allow_cpu=True)
     mc.load_state_dict(mb.state_dict())
     oc.load_state_dict(copy.deepcopy(ob.state_dict()))
-    assert oc._uniform and oc._step_count == 5
+    assert oc._uniform and oc._ecg_step_count == 5
     assert oc.state[next(iter(mc.parameters()))]["exp_avg"].data_ptr() == oc.flat_m.data_ptr()      # back in the flat buffers
     for s in range(5, 7):
         _fake_grads((mb, mc), s)
@@ -139,7 +139,7 @@ def test_adopted_adamw_keeps_stock_semantics_where_the_one_launch_does_not_apply
     _fake_grads((mf, mg), 1)
     of.step(), og.step()
     _assert_same(mf, mg)
-    assert mf.proj.weight.data_ptr() != 0 and of._uniform and of._step_count == 2
+    assert mf.proj.weight.data_ptr() != 0 and of._uniform and of._ecg_step_count == 2
     base = of.flat_param.data_ptr()
     assert base <= mf.proj.weight.data_ptr() < base + 4 * of.flat_param.numel()
 

@@ -407,6 +407,35 @@ def test_gradients_land_in_the_flat_buffer_and_still_accumulate():
     del keep_flat
 
 
+def test_a_parameter_re_pointed_behind_the_optimizer_gets_an_ordinary_gradient():
+    """A sink answers for an address only while its parameter lives there (ecg_hip/params.py): a conv weight re-pointed
+    with `p.data = ...` gets a private gradient tensor, every other gradient still lands in the flat buffer, the values
+    are those of the pass before, and the step gathers the stray gradient."""
+    from ecg_hip.optim import FlatAdamW
+    from src.models.ecg_multimodal import ECGMultimodal
+    from src.training.loop_demo import bce_loss_fn
+    from src.utils.seed import set_seed
+    set_seed(42)
+    m = ECGMultimodal().to(DEV).train()
+    opt = FlatAdamW(m.parameters(), lr=1e-4, weight_decay=1e-4)
+    x, xd, y = (t.to(DEV) for t in R.synthetic_batch(8, 1000, 5, demo=True))
+    opt.zero_grad()
+    bce_loss_fn(m(x, xd), y).backward()
+    g1 = {n: p.grad.clone() for n, p in m.named_parameters()}
+    moved = m.ecg_backbone.backbone[1].net[0].weight
+    moved.data = moved.data.clone()
+    for p in m.parameters():
+        p.grad = None
+    bce_loss_fn(m(x, xd), y).backward()
+    lo, hi = opt.flat_grad.data_ptr(), opt.flat_grad.data_ptr() + 4 * opt.flat_grad.numel()
+    for n, p in m.named_parameters():
+        assert (lo <= p.grad.data_ptr() < hi) is (p is not moved), n
+        assert torch.allclose(p.grad, g1[n], rtol=1e-6, atol=1e-12), n
+    before = opt.flat_param.clone()
+    opt.step()
+    assert not torch.equal(before, opt.flat_param)
+
+
 def test_hooked_block_trains_like_the_fused_path_with_flat_optimizer():
     """A forward hook on an inner module switches that block to the unfused leaves, whose gradients are ordinary
     tensors while the other blocks write into FlatAdamW's flat buffer: the optimizer must repair the mix
