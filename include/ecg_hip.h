@@ -886,6 +886,68 @@ int ecg_metrics_placements(const float *prob, const float *y, const int *order, 
 size_t ecg_metrics_paired_sums_workspace_bytes(int N, int C, int M);
 int ecg_metrics_paired_sums(const int *place, const float *prob, const float *y, long long *single, long long *pair,
                             void *workspace, int N, int C, int M, float threshold, ecg_stream_t stream);
+/* Operating points and calibration: where to cut each class, what a cut gives on other rows, and whether a probability
+ * means what it says — again exact integers, with KEY, POSITIVE, NEGATIVE, BAD, GROUP END, `order`, w (its precondition
+ * sum_i w[b][i] < 2^30 and NULL meaning one row of ones) and the workspace rules exactly as for ecg_metrics_counts.
+ *
+ * ecg_metrics_operating (two launches) — the cut of every (b, c) by four rules, chosen inside the walk along the ranks;
+ * nothing of size N is written.  With P = POS, Q = NEG and tp(r), fp(r) as above:
+ *     A CANDIDATE is a group end r whose key is not NaN (a NaN is never predicted, so cutting below it is no threshold).
+ *     Cutting at r means: predicted <=> rank <= r <=> prob >= prob[order[c][r]][c] compared in fp32.
+ *     Every rule takes the eligible candidate with the largest objective, the FIRST (lowest rank, highest threshold) of
+ *     equal maxima; every comparison is one of integers:
+ *       ECG_OP_F1      all candidates; 2tp / (tp + fp + P), two of them compared by cross-multiplication, a zero
+ *                      denominator counting as 0 / 1
+ *       ECG_OP_YOUDEN  all candidates; tp * Q - fp * P
+ *       ECG_OP_SENS    tp * sens_den >= sens_num * P and P > 0; -fp (the first cut that reaches the sensitivity)
+ *       ECG_OP_SPEC    (Q - fp) * spec_den >= spec_num * Q and Q > 0; tp
+ *     With sum w < 2^30 every product stays below 2^63: tp, fp, P, Q < 2^30, so 2tp < 2^31 and tp' + fp' + P < 3 * 2^30
+ *     give 2tp * (tp' + fp' + P) < 3 * 2^61; tp * Q and fp * P are below 2^60; the targets' parts are at most 10^6 < 2^20.
+ *   points [B][C][ECG_OP_RULES][ECG_OP_FIELDS] int64: ECG_OP_RANK, ECG_OP_ROW = order[c][RANK] (clamped as above),
+ *     ECG_OP_TP and ECG_OP_FP at that rank; no eligible candidate gives RANK = ROW = -1 and TP = FP = 0.
+ *   totals [B][C][2] int64: POS, NEG.
+ *   Under bootstrap weights a tie group whose rows all have weight 0 repeats the (tp, fp) of the group before it and is
+ *   passed by, being later.
+ * ECG_EINVAL before any launch — the integer limits first: N outside [1, 65536], C outside [1, 64], B outside [1, 65536],
+ * a target that is not 0 <= num <= den with 1 <= den <= 1 000 000; B > 1 with w == NULL; then a NULL pointer (w may be
+ * NULL) or a misaligned base: 8 bytes for points and totals, 4 otherwise.
+ *
+ * ecg_metrics_confusion (two launches) — thr [T][C] fp32, T sets of per-class thresholds; predicted <=> prob >= thr[t][c]
+ * compared in fp32, so a NaN on either side predicts 0.  No order is needed.
+ *   out [B][T][C][ECG_CF_FIELDS] int64: the weighted TP, FP, FN, TN; BAD rows are in no field.  With every class at one
+ *   threshold these are ECG_MT_TP/FP/FN/TN.  Sums of integers: one value however the rows are split.
+ * ECG_EINVAL before any launch — the limits above and T outside [1, 16]; B > 1 with w == NULL; then a NULL pointer (w may
+ * be NULL) or a misaligned base: 8 bytes for out, 4 otherwise.
+ *
+ * ecg_metrics_reliability (two launches) — the calibration table of M equal-width bins, as integers:
+ *     A positive or negative row is IN RANGE iff 0.0f <= p && p <= 1.0f (-0.0 is in; a NaN is not); otherwise its weight
+ *     goes to ECG_RL_OUT and nowhere else.  BAD rows go to ECG_RL_BAD and nowhere else.
+ *     A row in range has q = (int64) floorf(p * 16777216.0f): a power-of-two scaling, so exact, and 0 <= q <= 2^24; its
+ *     bin is m = min(M - 1, (q * M) >> 24): the bins are [lo, hi) on q, the last one closed.
+ *   bins [B][C][M][ECG_RL_BIN_FIELDS] int64:  ECG_RL_N += w,  ECG_RL_POS += w * [y == 1],  ECG_RL_SQ += w * q.
+ *   tot [B][C][ECG_RL_TOT_FIELDS] int64: with e = |q - 2^24 * [y == 1]| and s = e * e <= 2^48,
+ *     ECG_RL_SE_HI += w * (s >> 24),  ECG_RL_SE_LO += w * (s & 0xffffff)  (each stays <= 2^54),  ECG_RL_OUT,  ECG_RL_BAD.
+ *   From them (ecg_hip/metrics.py, calibration_from_tables), with W = sum_m N_m:
+ *     ECE = sum_m |2^24 POS_m - SQ_m| / (2^24 W),  MCE = max_m |2^24 POS_m - SQ_m| / (2^24 N_m),
+ *     Brier = (2^24 SE_HI + SE_LO) / (2^48 W).
+ *   Integer sums in LDS and registers: one value in any order.
+ * ECG_EINVAL before any launch — the limits above and M outside [1, 64]; B > 1 with w == NULL; then a NULL pointer (w may
+ * be NULL) or a misaligned base: 8 bytes for bins and tot, 4 otherwise. */
+enum { ECG_OP_F1 = 0, ECG_OP_YOUDEN = 1, ECG_OP_SENS = 2, ECG_OP_SPEC = 3, ECG_OP_RULES = 4 };
+enum { ECG_OP_RANK = 0, ECG_OP_ROW = 1, ECG_OP_TP = 2, ECG_OP_FP = 3, ECG_OP_FIELDS = 4 };
+enum { ECG_CF_TP = 0, ECG_CF_FP = 1, ECG_CF_FN = 2, ECG_CF_TN = 3, ECG_CF_FIELDS = 4 };
+enum { ECG_RL_N = 0, ECG_RL_POS = 1, ECG_RL_SQ = 2, ECG_RL_BIN_FIELDS = 3 };
+enum { ECG_RL_SE_HI = 0, ECG_RL_SE_LO = 1, ECG_RL_OUT = 2, ECG_RL_BAD = 3, ECG_RL_TOT_FIELDS = 4 };
+size_t ecg_metrics_operating_workspace_bytes(int N, int C, int B);
+int ecg_metrics_operating(const float *prob, const float *y, const int *order, const int *w, long long *points,
+                          long long *totals, void *workspace, int N, int C, int B, int sens_num, int sens_den,
+                          int spec_num, int spec_den, ecg_stream_t stream);
+size_t ecg_metrics_confusion_workspace_bytes(int N, int C, int B, int T);
+int ecg_metrics_confusion(const float *prob, const float *y, const int *w, const float *thr, long long *out,
+                          void *workspace, int N, int C, int B, int T, ecg_stream_t stream);
+size_t ecg_metrics_reliability_workspace_bytes(int N, int C, int B, int M);
+int ecg_metrics_reliability(const float *prob, const float *y, const int *w, long long *bins, long long *tot,
+                            void *workspace, int N, int C, int B, int M, ecg_stream_t stream);
 /* HOST side of the same step — what torch's DataLoader collate does for the reference (one `Dataset.__getitem__` per record,
  * src/datasets/ptbxl.py:25,122-127, stacked into a batch): rows `rows[0..n)` of a row-major host table (row_bytes each, e.g.
  * the int16 records of a memory-mapped pack) copied to consecutive rows of `dst` (the pinned staging slot).  Plain memcpy

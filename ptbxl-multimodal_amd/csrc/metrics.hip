@@ -31,6 +31,16 @@
 //           partials to ap ascending.  A rank that is no group end, or whose term does not exist, leaves +0.0 there: adding
 //           +0.0 changes no bit of a sum that started at +0.0 and only ever receives positive terms, so the value is the
 //           stated sum over group ends.  No atomics, no fma (the file is built with -ffp-contract=off): one value.
+//
+// ecg_metrics_operating, two launches: the same pack, then workgroup (b, c) walks the ranks with metrics_walk4 and every
+//   lane keeps, per rule, the best candidate (a group end whose key is no NaN) it has met as (tp << 32 | fp, rank); the
+//   objectives are compared as exact integers (op_better), the lanes' bests meet once at the end in the same compare.
+//   Nothing of size N is written.
+// ecg_metrics_confusion, two launches: bits   per (c, row) one word = [prob >= thr[t][c]] for t < T | positive | negative;
+//   sums   workgroup (b, c, t) adds w[b][row] into TP, FP, POS and NEG; FN = POS - TP, TN = NEG - FP.
+// ecg_metrics_reliability, two launches: quant   per (c, row) one word = q | positive | in range / out / bad;
+//   bins   workgroup (b, c) adds w, w [y == 1] and w q into the bin of q in LDS (integer atomics, one set of bins per
+//   wave), the two halves of the squared error and OUT, BAD per lane.  Integer sums only: one value in any order.
 #include <cmath>
 
 #include "common.h"
@@ -49,7 +59,7 @@ static_assert(kMtTileJ % (4 * kMtThreads) == 0, "a tile is whole 16-byte loads p
 
 // packed word of (c, rank): the row in the low 16 bits (N <= 65536), flags above
 constexpr unsigned kMtPos = 1u << 16, kMtNeg = 1u << 17, kMtEnd = 1u << 18, kMtPred = 1u << 19, kMtNonfinite = 1u << 20,
-                   kMtValid = 1u << 21;
+                   kMtValid = 1u << 21, kMtNan = 1u << 22;
 
 __host__ __device__ __forceinline__ unsigned metrics_key(float p) {
     unsigned u = __builtin_bit_cast(unsigned, p);
@@ -155,7 +165,7 @@ __global__ __launch_bounds__(kMtThreads) void metrics_pack_kernel(const float *_
         bool end = r == N - 1;
         if (!end) end = metrics_key(prob[metrics_row(oc, r + 1, N) * C + c]) != key;
         out = (unsigned)row | kMtValid | (l == 1.0f ? kMtPos : 0u) | (l == 0.0f ? kMtNeg : 0u) | (end ? kMtEnd : 0u) |
-              (p >= threshold ? kMtPred : 0u) | (metrics_key_nonfinite(key) ? kMtNonfinite : 0u);
+              (p >= threshold ? kMtPred : 0u) | (metrics_key_nonfinite(key) ? kMtNonfinite : 0u) | (key == 0u ? kMtNan : 0u);
     }
     packed[(size_t)c * Np + r] = out;
 }
@@ -449,6 +459,208 @@ __global__ __launch_bounds__(kMtThreads) void metrics_pair_finish_kernel(const l
     }
 }
 
+// ---- operating points.  A candidate is (word = tp << 32 | fp, rank); rank < 0 means none yet.  op_better(a, b): a's
+// objective is larger, or equal at a lower rank — a total order on candidates of distinct ranks, so the lanes' bests can
+// meet in any order.  P, Q < 2^30 and tp, fp < 2^30: 2tp < 2^31 and tp + fp + P < 3 * 2^30, so every product is below 2^63.
+struct OpBest {
+    mt_u64 word;
+    int rank;
+};
+
+__device__ __forceinline__ bool op_better(int rule, mt_u64 aw, int ar, mt_u64 bw, int br, long long P, long long Q) {
+    if (ar < 0) return false;
+    if (br < 0) return true;
+    const long long ta = (long long)(aw >> 32), fa = (long long)(aw & 0xffffffffu);
+    const long long tb = (long long)(bw >> 32), fb = (long long)(bw & 0xffffffffu);
+    long long oa, ob;
+    if (rule == ECG_OP_F1) {
+        const long long da = ta + fa + P, db = tb + fb + P;   // a zero denominator counts as 0 / 1
+        oa = (da ? 2 * ta : 0) * (db ? db : 1), ob = (db ? 2 * tb : 0) * (da ? da : 1);
+    } else if (rule == ECG_OP_YOUDEN) {
+        oa = ta * Q - fa * P, ob = tb * Q - fb * P;
+    } else if (rule == ECG_OP_SENS) {
+        oa = -fa, ob = -fb;
+    } else {
+        oa = ta, ob = tb;
+    }
+    return oa > ob || (oa == ob && ar < br);
+}
+
+__global__ __launch_bounds__(kMtThreads) void metrics_operating_kernel(const unsigned *__restrict__ packed, const int *__restrict__ w,
+                                                                       long long *__restrict__ points, long long *__restrict__ totals,
+                                                                       int N, int C, int Np, int sens_num, int sens_den,
+                                                                       int spec_num, int spec_den) {
+    __shared__ mt_u64 wsum[kMtThreads / kWave], wmax[kMtThreads / kWave];
+    __shared__ int tot_s[2];
+    __shared__ mt_u64 best_w[ECG_OP_RULES][kMtThreads / kWave];
+    __shared__ int best_r[ECG_OP_RULES][kMtThreads / kWave];
+    const int b = blockIdx.x, c = blockIdx.y, tid = threadIdx.x;
+    const unsigned *pc = packed + (size_t)c * Np;
+    const int *wb = w ? w + (size_t)b * N : nullptr;
+    unsigned pk[kMtItems];
+    int wt[kMtItems];
+
+    int pos = 0, neg = 0;                                    // pass 1: POS and NEG, which the objectives need
+    if (tid < 2) tot_s[tid] = 0;
+    for (int r0 = 0; r0 < N; r0 += kMtChunk) {
+        metrics_load4(pc, wb, r0, Np, pk, wt);
+#pragma unroll
+        for (int k = 0; k < kMtItems; ++k) pos += (pk[k] & kMtPos) ? wt[k] : 0, neg += (pk[k] & kMtNeg) ? wt[k] : 0;
+    }
+    __syncthreads();
+    pos = wave_sum_int(pos), neg = wave_sum_int(neg);
+    if ((tid & (kWave - 1)) == 0) atomicAdd(&tot_s[0], pos), atomicAdd(&tot_s[1], neg);   // LDS, integers
+    __syncthreads();
+    const long long P = tot_s[0], Q = tot_s[1];
+
+    OpBest best[ECG_OP_RULES];
+#pragma unroll
+    for (int u = 0; u < ECG_OP_RULES; ++u) best[u].word = 0, best[u].rank = -1;
+    mt_u64 carry = 0, carry_end = 0;
+    for (int r0 = 0; r0 < N; r0 += kMtChunk) {
+        metrics_load4(pc, wb, r0, Np, pk, wt);
+        mt_u64 cum[kMtItems], start[kMtItems];
+        metrics_walk4(pk, wt, carry, carry_end, wsum, wmax, cum, start);
+        const int r = r0 + kMtItems * tid;
+#pragma unroll
+        for (int k = 0; k < kMtItems; ++k) {
+            if ((pk[k] & (kMtEnd | kMtNan | kMtValid)) != (kMtEnd | kMtValid)) continue;
+            const long long tp = (long long)(cum[k] >> 32), fp = (long long)(cum[k] & 0xffffffffu);
+            const bool ok[ECG_OP_RULES] = {true, true, P > 0 && tp * sens_den >= (long long)sens_num * P,
+                                           Q > 0 && (Q - fp) * spec_den >= (long long)spec_num * Q};
+#pragma unroll
+            for (int u = 0; u < ECG_OP_RULES; ++u)
+                if (ok[u] && op_better(u, cum[k], r + k, best[u].word, best[u].rank, P, Q))
+                    best[u].word = cum[k], best[u].rank = r + k;
+        }
+        __syncthreads();                                     // the scan's slots
+    }
+#pragma unroll
+    for (int u = 0; u < ECG_OP_RULES; ++u) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const mt_u64 ow = __shfl_xor(best[u].word, off, kWave);
+            const int orank = __shfl_xor(best[u].rank, off, kWave);
+            if (op_better(u, ow, orank, best[u].word, best[u].rank, P, Q)) best[u].word = ow, best[u].rank = orank;
+        }
+        if ((tid & (kWave - 1)) == 0) best_w[u][tid / kWave] = best[u].word, best_r[u][tid / kWave] = best[u].rank;
+    }
+    __syncthreads();
+    if (tid < ECG_OP_RULES) {
+        mt_u64 bw = best_w[tid][0];
+        int br = best_r[tid][0];
+        for (int v = 1; v < kMtThreads / kWave; ++v)
+            if (op_better(tid, best_w[tid][v], best_r[tid][v], bw, br, P, Q)) bw = best_w[tid][v], br = best_r[tid][v];
+        long long *o = points + (((size_t)b * C + c) * ECG_OP_RULES + tid) * ECG_OP_FIELDS;
+        o[ECG_OP_RANK] = br, o[ECG_OP_ROW] = br < 0 ? -1 : (long long)(pc[br] & 0xffffu);   // br < N <= Np
+        o[ECG_OP_TP] = br < 0 ? 0 : (long long)(bw >> 32), o[ECG_OP_FP] = br < 0 ? 0 : (long long)(bw & 0xffffffffu);
+    }
+    if (tid == 0) totals[((size_t)b * C + c) * 2] = P, totals[((size_t)b * C + c) * 2 + 1] = Q;
+}
+
+// ---- confusion at per-class thresholds
+constexpr int kCfMaxT = 16;
+constexpr unsigned kCfPos = 1u << 16, kCfNeg = 1u << 17;
+
+__global__ __launch_bounds__(kMtThreads) void metrics_cf_bits_kernel(const float *__restrict__ prob, const float *__restrict__ y,
+                                                                     const float *__restrict__ thr, unsigned *__restrict__ bits,
+                                                                     int N, int C, int Np, int T) {
+    const int e = blockIdx.x * kMtThreads + threadIdx.x;     // N * C <= 2^22
+    if (e >= N * C) return;
+    const int n = e / C, c = e - n * C;
+    const float p = prob[e], l = y[e];
+    unsigned out = (l == 1.0f ? kCfPos : 0u) | (l == 0.0f ? kCfNeg : 0u);
+    for (int t = 0; t < T; ++t) out |= (p >= thr[t * C + c] ? 1u : 0u) << t;
+    bits[(size_t)c * Np + n] = out;
+}
+
+__global__ __launch_bounds__(kMtThreads) void metrics_cf_sums_kernel(const unsigned *__restrict__ bits, const int *__restrict__ w,
+                                                                     long long *__restrict__ out, int N, int C, int Np) {
+    __shared__ int sum_s[4];
+    const int b = blockIdx.x, c = blockIdx.y, t = blockIdx.z, T = gridDim.z, tid = threadIdx.x;
+    const unsigned *bc = bits + (size_t)c * Np;
+    const int *wb = w ? w + (size_t)b * N : nullptr;
+    int acc[4] = {0, 0, 0, 0};                               // TP, FP, POS, NEG; each a part of sum w < 2^30
+    if (tid < 4) sum_s[tid] = 0;
+    for (int n = tid; n < N; n += kMtThreads) {
+        const unsigned v = bc[n];
+        const int wt = wb ? wb[n] : 1;
+        const int wp = (v & kCfPos) ? wt : 0, wn = (v & kCfNeg) ? wt : 0;
+        const bool pred = (v >> t) & 1u;
+        acc[0] += pred ? wp : 0, acc[1] += pred ? wn : 0, acc[2] += wp, acc[3] += wn;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {
+        const int s = wave_sum_int(acc[f]);
+        if ((tid & (kWave - 1)) == 0) atomicAdd(&sum_s[f], s);   // LDS, integers
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const long long tp = sum_s[0], fp = sum_s[1], P = sum_s[2], Q = sum_s[3];
+        long long *o = out + (((size_t)b * T + t) * C + c) * ECG_CF_FIELDS;
+        o[ECG_CF_TP] = tp, o[ECG_CF_FP] = fp, o[ECG_CF_FN] = P - tp, o[ECG_CF_TN] = Q - fp;
+    }
+}
+
+// ---- reliability table
+constexpr int kRlMaxM = 64;
+constexpr unsigned kRlOne = 1u << 24, kRlPos = 1u << 25, kRlOut = 1u << 26, kRlBad = 1u << 27;
+
+__global__ __launch_bounds__(kMtThreads) void metrics_rl_quant_kernel(const float *__restrict__ prob, const float *__restrict__ y,
+                                                                      unsigned *__restrict__ quant, int N, int C, int Np) {
+    const int e = blockIdx.x * kMtThreads + threadIdx.x;     // N * C <= 2^22
+    if (e >= N * C) return;
+    const int n = e / C, c = e - n * C;
+    const float p = prob[e], l = y[e];
+    unsigned out;
+    if (l != 1.0f && l != 0.0f) out = kRlBad;
+    else if (!(0.0f <= p && p <= 1.0f)) out = kRlOut;
+    else out = (unsigned)(long long)floorf(p * 16777216.0f) | (l == 1.0f ? kRlPos : 0u);   // a power-of-two scaling: exact
+    quant[(size_t)c * Np + n] = out;
+}
+
+__global__ __launch_bounds__(kMtThreads) void metrics_rl_bins_kernel(const unsigned *__restrict__ quant, const int *__restrict__ w,
+                                                                     long long *__restrict__ bins, long long *__restrict__ tot,
+                                                                     int N, int C, int Np, int M) {
+    __shared__ mt_u64 bin_s[kMtThreads / kWave][kRlMaxM][ECG_RL_BIN_FIELDS];
+    __shared__ long long tot_s[kMtThreads / kWave][ECG_RL_TOT_FIELDS];
+    const int b = blockIdx.x, c = blockIdx.y, tid = threadIdx.x, wave = tid / kWave;
+    const unsigned *qc = quant + (size_t)c * Np;
+    const int *wb = w ? w + (size_t)b * N : nullptr;
+    for (int e = tid; e < (kMtThreads / kWave) * kRlMaxM * ECG_RL_BIN_FIELDS; e += kMtThreads) (&bin_s[0][0][0])[e] = 0;
+    __syncthreads();
+    long long se_hi = 0, se_lo = 0, out = 0, bad = 0;
+    for (int n = tid; n < N; n += kMtThreads) {
+        const unsigned v = qc[n];
+        const int wt = wb ? wb[n] : 1;
+        if (wt == 0) continue;
+        if (v & kRlBad) { bad += wt; continue; }
+        if (v & kRlOut) { out += wt; continue; }
+        const unsigned q = v & (2 * kRlOne - 1);             // 0 .. 2^24
+        const int m = min(M - 1, (int)((q * (unsigned)M) >> 24));   // q * M <= 2^30
+        atomicAdd(&bin_s[wave][m][ECG_RL_N], (mt_u64)(unsigned)wt);   // LDS, integers
+        if (v & kRlPos) atomicAdd(&bin_s[wave][m][ECG_RL_POS], (mt_u64)(unsigned)wt);
+        atomicAdd(&bin_s[wave][m][ECG_RL_SQ], (mt_u64)(unsigned)wt * q);
+        const mt_u64 e = (v & kRlPos) ? kRlOne - q : q, s = e * e;   // <= 2^48
+        se_hi += (long long)((mt_u64)(unsigned)wt * (s >> 24)), se_lo += (long long)((mt_u64)(unsigned)wt * (s & 0xffffffu));
+    }
+    se_hi = wave_sum_ll(se_hi), se_lo = wave_sum_ll(se_lo), out = wave_sum_ll(out), bad = wave_sum_ll(bad);
+    if ((tid & (kWave - 1)) == 0)
+        tot_s[wave][ECG_RL_SE_HI] = se_hi, tot_s[wave][ECG_RL_SE_LO] = se_lo, tot_s[wave][ECG_RL_OUT] = out, tot_s[wave][ECG_RL_BAD] = bad;
+    __syncthreads();
+    for (int e = tid; e < M * ECG_RL_BIN_FIELDS; e += kMtThreads) {
+        mt_u64 v = 0;
+        for (int k = 0; k < kMtThreads / kWave; ++k) v += (&bin_s[k][0][0])[e];
+        bins[((size_t)b * C + c) * M * ECG_RL_BIN_FIELDS + e] = (long long)v;
+    }
+    if (tid < ECG_RL_TOT_FIELDS) {
+        long long v = 0;
+        for (int k = 0; k < kMtThreads / kWave; ++k) v += tot_s[k][tid];
+        tot[((size_t)b * C + c) * ECG_RL_TOT_FIELDS + tid] = v;
+    }
+}
+
 static bool metrics_sizes_ok(int N, int C) { return N >= 1 && N <= kMtMaxN && C >= 1 && C <= kMtMaxC; }
 static bool aligned_to(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
@@ -503,6 +715,87 @@ ECG_API int ecg_metrics_counts(const float *prob, const float *y, const int *ord
     hipLaunchKernelGGL(metrics_scan_kernel, dim3(B, C), dim3(kMtThreads), 0, as_stream(stream), packed, w, fields, ap, curve, N, C,
                        Np);
     return check_launch("metrics_scan_kernel");
+}
+
+constexpr int kOpMaxDen = 1000000;
+static bool metrics_fraction_ok(int num, int den) { return num >= 0 && num <= den && den >= 1 && den <= kOpMaxDen; }
+
+ECG_API size_t ecg_metrics_operating_workspace_bytes(int N, int C, int B) { return ecg_metrics_counts_workspace_bytes(N, C, B); }
+
+ECG_API size_t ecg_metrics_confusion_workspace_bytes(int N, int C, int B, int T) {
+    return T >= 1 && T <= kCfMaxT ? ecg_metrics_counts_workspace_bytes(N, C, B) : 0;
+}
+
+ECG_API size_t ecg_metrics_reliability_workspace_bytes(int N, int C, int B, int M) {
+    return M >= 1 && M <= kRlMaxM ? ecg_metrics_counts_workspace_bytes(N, C, B) : 0;
+}
+
+ECG_API int ecg_metrics_operating(const float *prob, const float *y, const int *order, const int *w, long long *points,
+                                  long long *totals, void *workspace, int N, int C, int B, int sens_num, int sens_den,
+                                  int spec_num, int spec_den, ecg_stream_t stream) {
+    const char *who = "metrics_operating";
+    ECG_REQUIRE(N >= 1 && N <= kMtMaxN, "%s: N=%d outside [1,%d]", who, N, kMtMaxN);
+    ECG_REQUIRE(C >= 1 && C <= kMtMaxC, "%s: C=%d outside [1,%d]", who, C, kMtMaxC);
+    ECG_REQUIRE(B >= 1 && B <= kMtMaxB, "%s: B=%d outside [1,%d]", who, B, kMtMaxB);
+    ECG_REQUIRE(metrics_fraction_ok(sens_num, sens_den), "%s: sensitivity %d/%d is not 0 <= num <= den, 1 <= den <= %d", who,
+                sens_num, sens_den, kOpMaxDen);
+    ECG_REQUIRE(metrics_fraction_ok(spec_num, spec_den), "%s: specificity %d/%d is not 0 <= num <= den, 1 <= den <= %d", who,
+                spec_num, spec_den, kOpMaxDen);
+    ECG_REQUIRE(w || B == 1, "%s: B=%d weight rows need w (NULL means one row of ones)", who, B);
+    ECG_REQUIRE(prob && y && order && points && totals && workspace, "%s: null pointer", who);
+    ECG_REQUIRE(aligned_to(points, 8) && aligned_to(totals, 8), "%s: points and totals must be 8-byte aligned", who);
+    ECG_REQUIRE(aligned_to(prob, 4) && aligned_to(y, 4) && aligned_to(order, 4) && aligned_to(w, 4) && aligned_to(workspace, 4),
+                "%s: a base is not 4-byte aligned", who);
+    unsigned *packed = metrics_ws_base(workspace);
+    const int Np = metrics_padded(N);
+    hipLaunchKernelGGL(metrics_pack_kernel, dim3(cdiv(Np, kMtThreads), C), dim3(kMtThreads), 0, as_stream(stream), prob, y, order,
+                       packed, N, C, Np, 0.0f);
+    if (int rc = check_launch("metrics_pack_kernel")) return rc;
+    hipLaunchKernelGGL(metrics_operating_kernel, dim3(B, C), dim3(kMtThreads), 0, as_stream(stream), packed, w, points, totals, N,
+                       C, Np, sens_num, sens_den, spec_num, spec_den);
+    return check_launch("metrics_operating_kernel");
+}
+
+ECG_API int ecg_metrics_confusion(const float *prob, const float *y, const int *w, const float *thr, long long *out,
+                                  void *workspace, int N, int C, int B, int T, ecg_stream_t stream) {
+    const char *who = "metrics_confusion";
+    ECG_REQUIRE(N >= 1 && N <= kMtMaxN, "%s: N=%d outside [1,%d]", who, N, kMtMaxN);
+    ECG_REQUIRE(C >= 1 && C <= kMtMaxC, "%s: C=%d outside [1,%d]", who, C, kMtMaxC);
+    ECG_REQUIRE(B >= 1 && B <= kMtMaxB, "%s: B=%d outside [1,%d]", who, B, kMtMaxB);
+    ECG_REQUIRE(T >= 1 && T <= kCfMaxT, "%s: T=%d outside [1,%d]", who, T, kCfMaxT);
+    ECG_REQUIRE(w || B == 1, "%s: B=%d weight rows need w (NULL means one row of ones)", who, B);
+    ECG_REQUIRE(prob && y && thr && out && workspace, "%s: null pointer", who);
+    ECG_REQUIRE(aligned_to(out, 8), "%s: out must be 8-byte aligned", who);
+    ECG_REQUIRE(aligned_to(prob, 4) && aligned_to(y, 4) && aligned_to(w, 4) && aligned_to(thr, 4) && aligned_to(workspace, 4),
+                "%s: a base is not 4-byte aligned", who);
+    unsigned *bits = metrics_ws_base(workspace);
+    const int Np = metrics_padded(N);
+    hipLaunchKernelGGL(metrics_cf_bits_kernel, dim3(cdiv((long long)N * C, kMtThreads)), dim3(kMtThreads), 0, as_stream(stream),
+                       prob, y, thr, bits, N, C, Np, T);
+    if (int rc = check_launch("metrics_cf_bits_kernel")) return rc;
+    hipLaunchKernelGGL(metrics_cf_sums_kernel, dim3(B, C, T), dim3(kMtThreads), 0, as_stream(stream), bits, w, out, N, C, Np);
+    return check_launch("metrics_cf_sums_kernel");
+}
+
+ECG_API int ecg_metrics_reliability(const float *prob, const float *y, const int *w, long long *bins, long long *tot,
+                                    void *workspace, int N, int C, int B, int M, ecg_stream_t stream) {
+    const char *who = "metrics_reliability";
+    ECG_REQUIRE(N >= 1 && N <= kMtMaxN, "%s: N=%d outside [1,%d]", who, N, kMtMaxN);
+    ECG_REQUIRE(C >= 1 && C <= kMtMaxC, "%s: C=%d outside [1,%d]", who, C, kMtMaxC);
+    ECG_REQUIRE(B >= 1 && B <= kMtMaxB, "%s: B=%d outside [1,%d]", who, B, kMtMaxB);
+    ECG_REQUIRE(M >= 1 && M <= kRlMaxM, "%s: M=%d outside [1,%d]", who, M, kRlMaxM);
+    ECG_REQUIRE(w || B == 1, "%s: B=%d weight rows need w (NULL means one row of ones)", who, B);
+    ECG_REQUIRE(prob && y && bins && tot && workspace, "%s: null pointer", who);
+    ECG_REQUIRE(aligned_to(bins, 8) && aligned_to(tot, 8), "%s: bins and tot must be 8-byte aligned", who);
+    ECG_REQUIRE(aligned_to(prob, 4) && aligned_to(y, 4) && aligned_to(w, 4) && aligned_to(workspace, 4),
+                "%s: a base is not 4-byte aligned", who);
+    unsigned *quant = metrics_ws_base(workspace);
+    const int Np = metrics_padded(N);
+    hipLaunchKernelGGL(metrics_rl_quant_kernel, dim3(cdiv((long long)N * C, kMtThreads)), dim3(kMtThreads), 0, as_stream(stream),
+                       prob, y, quant, N, C, Np);
+    if (int rc = check_launch("metrics_rl_quant_kernel")) return rc;
+    hipLaunchKernelGGL(metrics_rl_bins_kernel, dim3(B, C), dim3(kMtThreads), 0, as_stream(stream), quant, w, bins, tot, N, C, Np, M);
+    return check_launch("metrics_rl_bins_kernel");
 }
 
 static size_t metrics_pair_part_count(int N, int C, int M) { return (size_t)C * M * M * metrics_pair_slices(N) * kPsParts; }

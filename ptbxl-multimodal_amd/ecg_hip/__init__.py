@@ -14,6 +14,8 @@ WFDB records in formats 16, 61, 80, 160 and 212, with skews, offsets and several
 Windows spoiled by flat lines, rails or artefacts are kept out of the record-level numbers (`ecg_hip.quality`, quality=).
 Beat positions and per-window RR statistics come from an integer QRS detector on the device (`ecg_hip.beats`, beats=).
 Macro AUROC / AP / F1 of an epoch and bootstrap intervals for them come from exact integers on the device (`ecg_hip.metrics`).
+Per-class thresholds (best F1, Youden's J, a target sensitivity or specificity) and the calibration table with ECE, MCE
+and the Brier score come from there too (`operating_points`, `select_thresholds`, `tuned_metrics`, `calibration`).
 """
 from ._lib import EcgHipError, LIB_PATH, load  # noqa: F401
 

@@ -126,6 +126,12 @@ SIGNATURES = {
     "ecg_metrics_placements": (_i, [_vp] * 5 + [_i, _i, _vp]),
     "ecg_metrics_paired_sums_workspace_bytes": (_sz, [_i, _i, _i]),
     "ecg_metrics_paired_sums": (_i, [_vp] * 6 + [_i, _i, _i, _f, _vp]),
+    "ecg_metrics_operating_workspace_bytes": (_sz, [_i, _i, _i]),
+    "ecg_metrics_operating": (_i, [_vp] * 7 + [_i] * 7 + [_vp]),
+    "ecg_metrics_confusion_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "ecg_metrics_confusion": (_i, [_vp] * 6 + [_i] * 4 + [_vp]),
+    "ecg_metrics_reliability_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "ecg_metrics_reliability": (_i, [_vp] * 6 + [_i] * 4 + [_vp]),
     "ecg_host_gather_rows": (_i, [_vp, _sz, _vp, _i, _vp]),
 }
 

@@ -744,5 +744,7 @@ from .input_step import (_fir_call, _resampled_call, beats_match, beats_rhythm, 
                          beats_sum, fir_filter, fir_windows, overlap_mean, wfdb16_beats, wfdb16_quality,
                          wfdb16_to_windows, wfdb16_to_windows_sliding, wfdb16_windows, wfdb16_windows_resampled,
                          wfdb_decode16, zscore_per_lead)
-from .metrics import (compare_models, delong_from_sums, mcnemar_from_sums, metrics_counts, metrics_order,  # noqa: E402,F401
-                      metrics_paired_sums, metrics_placements)
+from .metrics import (calibration, calibration_from_tables, compare_models, delong_from_sums, mcnemar_from_sums,  # noqa: E402,F401
+                      metrics_confusion, metrics_counts, metrics_operating, metrics_order, metrics_paired_sums,
+                      metrics_placements, metrics_reliability, operating_from_points, operating_points, select_thresholds,
+                      tuned_metrics)

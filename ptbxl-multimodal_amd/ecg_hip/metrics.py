@@ -11,7 +11,15 @@ Paired comparison of models scored on the same rows: `metrics_placements` (ecg_m
 placement among the rows of the other label, `metrics_paired_sums` (ecg_metrics_paired_sums) the integer sums of their
 products and the counts of who is right where; `delong_from_sums` and `mcnemar_from_sums` turn those into DeLong's and
 McNemar's tests in Python integers, and `compare_models` is the whole path with a paired bootstrap on request.
+
+Operating points and calibration: `metrics_operating` (ecg_metrics_operating) chooses the cut of every class inside the walk
+along the ranks by four rules (best F1, Youden's J, a target sensitivity, a target specificity), `metrics_confusion`
+(ecg_metrics_confusion) applies per-class thresholds to any rows, `metrics_reliability` (ecg_metrics_reliability) gives the
+calibration table as integers.  `operating_from_points` and `calibration_from_tables` turn them into ratios;
+`operating_points`, `select_thresholds`, `tuned_metrics` and `calibration` are the user calls, with bootstrap bounds on request.
 """
+from fractions import Fraction
+
 import numpy as np
 import torch
 
@@ -37,6 +45,21 @@ def _device_matrix(who, name, t, dtype):
     return t
 
 
+def _pair_checked(who, prob, y, weights):
+    """The checks every counting call makes of prob, y [N, C] and weights [B, N] or None -> (prob, y, weights, B)."""
+    prob = _device_matrix(who, "prob", prob, torch.float32)
+    y = _device_matrix(who, "y", y, torch.float32)
+    if y.shape != prob.shape:
+        raise L.EcgHipError(f"{who}: y {tuple(y.shape)} and prob {tuple(prob.shape)} differ in shape")
+    B = 1
+    if weights is not None:
+        weights = _device_matrix(who, "weights", weights, torch.int32)
+        if weights.shape[1] != prob.shape[0]:
+            raise L.EcgHipError(f"{who}: weights must be [B, N={prob.shape[0]}], got {tuple(weights.shape)}")
+        B = weights.shape[0]
+    return prob, y, weights, B
+
+
 def _workspace(nbytes, device):
     return torch.empty(max(int(nbytes), 4), dtype=torch.uint8, device=device)
 
@@ -58,22 +81,13 @@ def metrics_counts(prob, y, order=None, weights=None, threshold=0.5, curve=False
     below 2^30, or None for one row of ones -> (fields int64 [B, C, 9] in the order of FIELDS, ap float64 [B, C]) and,
     with curve=True, a third tensor int32 [B, C, N, 2] holding tp(r), fp(r) at every rank."""
     who = "metrics_counts"
-    prob = _device_matrix(who, "prob", prob, torch.float32)
-    y = _device_matrix(who, "y", y, torch.float32)
-    if y.shape != prob.shape:
-        raise L.EcgHipError(f"{who}: y {tuple(y.shape)} and prob {tuple(prob.shape)} differ in shape")
+    prob, y, weights, B = _pair_checked(who, prob, y, weights)
     N, C = prob.shape
     if order is None:
         order = metrics_order(prob)[0]
     order = _device_matrix(who, "order", order, torch.int32)
     if tuple(order.shape) != (C, N):
         raise L.EcgHipError(f"{who}: order must be [C={C}, N={N}], got {tuple(order.shape)}")
-    B = 1
-    if weights is not None:
-        weights = _device_matrix(who, "weights", weights, torch.int32)
-        if weights.shape[1] != N:
-            raise L.EcgHipError(f"{who}: weights must be [B, N={N}], got {tuple(weights.shape)}")
-        B = weights.shape[0]
     fields = torch.empty((B, C, len(FIELDS)), dtype=torch.int64, device=prob.device)
     ap = torch.empty((B, C), dtype=torch.float64, device=prob.device)
     cv = torch.empty((B, C, N, 2), dtype=torch.int32, device=prob.device) if curve else None
@@ -125,11 +139,26 @@ def _inputs(y_true, y_prob):
     return y_true.detach().to(torch.float32).contiguous(), y_prob.detach().to(torch.float32).contiguous()
 
 
+def _counts_at(p, y, weights, threshold):
+    """metrics_counts at a float threshold; at a [C] vector of thresholds (tensor or sequence) the TP / FP / FN / TN fields
+    come from metrics_confusion instead, everything else from the same metrics_counts call."""
+    if not torch.is_tensor(threshold) and np.ndim(threshold) == 0:
+        return metrics_counts(p, y, weights=weights, threshold=threshold)
+    thr = torch.as_tensor(threshold, dtype=torch.float32).to(p.device).reshape(-1).contiguous()
+    if thr.numel() != p.shape[1]:
+        raise L.EcgHipError(f"threshold must be a float or one value per class ({p.shape[1]}), got {thr.numel()} values")
+    fields, ap = metrics_counts(p, y, weights=weights)
+    fields[..., TP:TN + 1] = metrics_confusion(p, y, thr.unsqueeze(0), weights=weights)[:, 0]
+    return fields, ap
+
+
 def compute_metrics_device(y_true, y_prob, threshold=0.5):
     """compute_metrics (src/training/metrics.py) on device tensors y_true, y_prob [N, C]: the same three keys as Python
-    floats, plus auroc_per_class / auprc_per_class / f1_per_class as arrays.  Two calls of two launches, one host read."""
+    floats, plus auroc_per_class / auprc_per_class / f1_per_class as arrays.  Two calls of two launches, one host read.
+    `threshold` may be one value per class ([C] tensor or sequence, e.g. select_thresholds' result): F1 is then taken at
+    those, from one more call (metrics_confusion)."""
     y, p = _inputs(y_true, y_prob)
-    s = summarize(*_one_read(*metrics_counts(p, y, threshold=threshold)))
+    s = summarize(*_one_read(*_counts_at(p, y, None, threshold)))
     return {k: (float(v[0]) if k in MACRO_KEYS else v[0]) for k, v in s.items()}
 
 
@@ -153,10 +182,10 @@ def bootstrap_metrics(y_true, y_prob, n_boot=1000, seed=0, threshold=0.5, alpha=
     metrics_counts call with B = n_boot + 1 weight rows (bootstrap_weights; row 0 all ones: the point value).  Returns, per
     key of summarize, {"point", "lo", "hi"} (the alpha/2 and 1 - alpha/2 percentiles over the replicates whose value is not
     NaN; NaN when none is left), "n_nan" (how many replicates were left out, per key) and "replicates" (the n_boot values
-    per key)."""
+    per key).  `threshold` may be one value per class, as for compute_metrics_device."""
     y, p = _inputs(y_true, y_prob)
     w = bootstrap_weights(p.shape[0], int(n_boot), seed, p.device)
-    s = summarize(*_one_read(*metrics_counts(p, y, weights=w, threshold=threshold)))
+    s = summarize(*_one_read(*_counts_at(p, y, w, threshold)))
     out = {"n_nan": {}, "replicates": {}}
     q = (100.0 * alpha / 2, 100.0 * (1 - alpha / 2))
     for k, v in s.items():
@@ -404,6 +433,312 @@ def compare_models(y_true, probs, names=None, threshold=0.5, n_boot=0, seed=0, a
                     d["n_nan"][key] = int(n_nan) if scalar else n_nan
                     d["replicates"][key] = diff[1:]
             out["pairs"][(names[k], names[l])] = d
+    return out
+
+
+# ---- operating points and calibration
+
+RULES = ("f1", "youden", "sensitivity", "specificity")
+(OP_F1, OP_YOUDEN, OP_SENS, OP_SPEC) = range(4)
+(OP_RANK, OP_ROW, OP_TP, OP_FP) = range(4)
+(CF_TP, CF_FP, CF_FN, CF_TN) = range(4)
+(RL_N, RL_POS, RL_SQ) = range(3)
+(RL_SE_HI, RL_SE_LO, RL_OUT, RL_BAD) = range(4)
+MAX_DEN = 1000000
+MAX_THRESHOLD_SETS, MAX_BINS = 16, 64
+
+
+def _target(who, name, value):
+    """(num, den) of a target given as (num, den) integers or as a number: Fraction(str(x)), so 0.9 is 9/10."""
+    if isinstance(value, tuple) and len(value) == 2 and all(isinstance(v, int) for v in value):
+        num, den = value
+    else:
+        try:
+            f = Fraction(str(value))
+        except (ValueError, ZeroDivisionError):
+            raise L.EcgHipError(f"{who}: {name} target {value!r} is no number") from None
+        num, den = f.numerator, f.denominator
+    if not (0 <= num <= den and 1 <= den <= MAX_DEN):
+        raise L.EcgHipError(f"{who}: {name} target {value!r} = {num}/{den} must lie in [0, 1] with a denominator of at most {MAX_DEN}")
+    return int(num), int(den)
+
+
+def metrics_operating(prob, y, order=None, weights=None, sensitivity=(9, 10), specificity=(9, 10)):
+    """prob, y fp32 [N, C]; order int32 [C, N] (metrics_order(prob) when None); weights as for metrics_counts; the two targets
+    as (num, den) or numbers -> (points int64 [B, C, 4, 4]: per rule of RULES the RANK, ROW, TP, FP of the chosen cut, -1, -1,
+    0, 0 where no cut is eligible; totals int64 [B, C, 2]: POS, NEG).  ecg_metrics_operating."""
+    who = "metrics_operating"
+    prob, y, weights, B = _pair_checked(who, prob, y, weights)
+    N, C = prob.shape
+    if order is None:
+        order = metrics_order(prob)[0]
+    order = _device_matrix(who, "order", order, torch.int32)
+    if tuple(order.shape) != (C, N):
+        raise L.EcgHipError(f"{who}: order must be [C={C}, N={N}], got {tuple(order.shape)}")
+    sn, sd = _target(who, "sensitivity", sensitivity)
+    pn, pd = _target(who, "specificity", specificity)
+    points = torch.empty((B, C, len(RULES), 4), dtype=torch.int64, device=prob.device)
+    totals = torch.empty((B, C, 2), dtype=torch.int64, device=prob.device)
+    ws = _workspace(L.query("ecg_metrics_operating_workspace_bytes", N, C, B), prob.device)
+    L.call("ecg_metrics_operating", L.ptr(prob), L.ptr(y), L.ptr(order), L.ptr(weights), L.ptr(points), L.ptr(totals), L.ptr(ws),
+           N, C, B, sn, sd, pn, pd, L.stream())
+    return points, totals
+
+
+def metrics_confusion(prob, y, thresholds, weights=None):
+    """prob, y fp32 [N, C]; thresholds fp32 [T, C] (or [C]: T = 1), T <= 16 sets of per-class thresholds; weights as for
+    metrics_counts -> int64 [B, T, C, 4]: TP, FP, FN, TN with predicted <=> prob >= threshold in fp32.  ecg_metrics_confusion."""
+    who = "metrics_confusion"
+    prob, y, weights, B = _pair_checked(who, prob, y, weights)
+    N, C = prob.shape
+    if torch.is_tensor(thresholds) and thresholds.dim() == 1:
+        thresholds = thresholds.unsqueeze(0)
+    thresholds = _device_matrix(who, "thresholds", thresholds, torch.float32)
+    T = thresholds.shape[0]
+    if thresholds.shape[1] != C:
+        raise L.EcgHipError(f"{who}: thresholds must be [T, C={C}], got {tuple(thresholds.shape)}")
+    out = torch.empty((B, T, C, 4), dtype=torch.int64, device=prob.device)
+    ws = _workspace(L.query("ecg_metrics_confusion_workspace_bytes", N, C, B, T), prob.device)
+    L.call("ecg_metrics_confusion", L.ptr(prob), L.ptr(y), L.ptr(weights), L.ptr(thresholds), L.ptr(out), L.ptr(ws), N, C, B, T,
+           L.stream())
+    return out
+
+
+def metrics_reliability(prob, y, n_bins=10, weights=None):
+    """prob, y fp32 [N, C]; n_bins <= 64 equal-width bins; weights as for metrics_counts -> (bins int64 [B, C, n_bins, 3]: N,
+    POS, SQ per bin; tot int64 [B, C, 4]: SE_HI, SE_LO, OUT, BAD).  ecg_metrics_reliability."""
+    who = "metrics_reliability"
+    prob, y, weights, B = _pair_checked(who, prob, y, weights)
+    N, C = prob.shape
+    M = int(n_bins)
+    bins = torch.empty((B, C, max(M, 0), 3), dtype=torch.int64, device=prob.device)
+    tot = torch.empty((B, C, 4), dtype=torch.int64, device=prob.device)
+    ws = _workspace(L.query("ecg_metrics_reliability_workspace_bytes", N, C, B, M), prob.device)
+    L.call("ecg_metrics_reliability", L.ptr(prob), L.ptr(y), L.ptr(weights), L.ptr(bins), L.ptr(tot), L.ptr(ws), N, C, B, M,
+           L.stream())
+    return bins, tot
+
+
+def _ratios(num, den):
+    """Elementwise _ratio of two integer arrays (int64 or Python integers as objects), NaN where den == 0.  Integers below
+    2^53 are doubles already and numpy's division is the correctly rounded one; anything larger goes through Python integers."""
+    num, den = np.asarray(num), np.asarray(den)
+    num, den = np.broadcast_arrays(num, den)
+    out = np.full(num.shape, np.nan, np.float64)
+    small = num.dtype != object and den.dtype != object and (num.size == 0 or (
+        int(np.abs(num).max()) < (1 << 53) and int(np.abs(den).max()) < (1 << 53)))
+    if small:
+        np.divide(num.astype(np.float64), den.astype(np.float64), out=out, where=den != 0)
+        return out
+    flat = out.reshape(-1)
+    for i, (a, b) in enumerate(zip(num.reshape(-1).tolist(), den.reshape(-1).tolist())):
+        if b != 0:
+            flat[i] = _ratio(int(a), int(b))
+    return flat.reshape(num.shape)
+
+
+def _nanmean_defined(v, defined):
+    """Mean along the last axis over the entries where `defined`; NaN where there is none."""
+    cnt = defined.sum(-1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(cnt > 0, np.where(defined, v, 0.0).sum(-1) / cnt, np.nan)
+
+
+def calibration_from_tables(bins, tot):
+    """bins int [..., C, M, 3], tot int [..., C, 4] (arrays or tensors, as metrics_reliability gives them) -> a dict of
+    float64 arrays.  With W = sum_m N_m and D_m = |2^24 POS_m - SQ_m|, each value ONE integer ratio, one division:
+        "ece"   [..., C]  sum_m D_m / (2^24 W)            "mce"  [..., C]  max over the bins with N_m > 0 of D_m / (2^24 N_m)
+        "brier" [..., C]  (2^24 SE_HI + SE_LO) / (2^48 W)
+        "frac_pos", "mean_prob" [..., C, M]  POS_m / N_m and SQ_m / (2^24 N_m), NaN for an empty bin;  "n" [..., C, M] int64
+        "out", "bad" [..., C] int64, the weight left out (a probability outside [0, 1]; a label that is neither 0 nor 1)
+    NaN for a class with W == 0; "ece_macro", "mce_macro", "brier_macro" [...] are means over the classes with W > 0 (NaN
+    if there is none).  (The maximum of correctly rounded ratios is the correctly rounded maximum: rounding is monotone.)"""
+    b, t = _host(bins, np.int64), _host(tot, np.int64)
+    n, pos, sq = b[..., RL_N], b[..., RL_POS], b[..., RL_SQ]
+    W = n.sum(-1)
+    d = np.abs((pos << 24) - sq)                            # <= 2^54
+    per_bin = _ratios(d, n << 24)
+    out = {"ece": _ratios(d.sum(-1), W << 24), "mce": np.where(W > 0, np.nanmax(np.where(n > 0, per_bin, -np.inf), -1), np.nan),
+           "brier": _ratios((t[..., RL_SE_HI].astype(object) << 24) + t[..., RL_SE_LO].astype(object), W.astype(object) << 48),
+           "frac_pos": _ratios(pos, n), "mean_prob": _ratios(sq, n << 24), "n": n, "out": t[..., RL_OUT], "bad": t[..., RL_BAD]}
+    for k in ("ece", "mce", "brier"):
+        out[k + "_macro"] = _nanmean_defined(out[k], W > 0)
+    return out
+
+
+OP_VALUES = ("f1", "sensitivity", "specificity", "youden")
+
+
+def _operating_values(points, totals):
+    """host int64 points [..., C, R, 4], totals [..., C, 2] -> the four values at each cut, float64 [..., C, R]."""
+    tp, fp = points[..., OP_TP], points[..., OP_FP]
+    P, Q = totals[..., 0][..., None], totals[..., 1][..., None]
+    f1 = _ratios(2 * tp, tp + fp + P)
+    return {"f1": np.where(np.isnan(f1), 0.0, f1), "sensitivity": _ratios(tp, np.broadcast_to(P, tp.shape)),
+            "specificity": _ratios(Q - fp, np.broadcast_to(Q, tp.shape)), "youden": _ratios(tp * Q - fp * P, P * Q + 0 * tp)}
+
+
+def _gather_thresholds(points, prob):
+    """fp32 [..., C, R] on prob's device: prob[ROW, c], +inf where ROW is -1 (no finite score is predicted)."""
+    row = points[..., OP_ROW]
+    C = prob.shape[1]
+    col = torch.arange(C, device=prob.device).view((1,) * (row.dim() - 2) + (C, 1)).expand_as(row)
+    thr = prob[row.clamp(min=0), col]
+    return torch.where(row < 0, torch.full_like(thr, float("inf")), thr)
+
+
+def operating_from_points(points, totals, prob):
+    """points int64 [..., C, R, 4] and totals int64 [..., C, 2] as metrics_operating gives them, prob the fp32 [N, C] they were
+    made from (device tensors: one gather, one host read; or host arrays) -> a dict of arrays [..., C, R]: "threshold" fp32 =
+    prob[ROW, c], +inf where no cut was eligible (no finite score is predicted); "rank", "row", "tp", "fp" int64; and at the cut, each
+    one integer ratio: "f1" = 2tp / (tp + fp + POS) (0 where that is 0 / 0), "sensitivity" = tp / POS, "specificity" =
+    (NEG - fp) / NEG, "youden" = (tp NEG - fp POS) / (POS NEG) (NaN where the class has no positives / negatives)."""
+    if torch.is_tensor(points):
+        thr = _gather_thresholds(points, prob)
+        n_p, n_t = points.numel(), totals.numel()
+        host = torch.cat([points.reshape(-1), totals.reshape(-1), thr.reshape(-1).view(torch.int32).to(torch.int64)]).cpu().numpy()
+        pts, tots = host[:n_p].reshape(points.shape), host[n_p:n_p + n_t].reshape(totals.shape)
+        thr = host[n_p + n_t:].astype(np.int32).view(np.float32).reshape(points.shape[:-1])
+    else:
+        pts, tots, pr = np.asarray(points, np.int64), np.asarray(totals, np.int64), np.asarray(prob, np.float32)
+        row = pts[..., OP_ROW]
+        col = np.arange(pr.shape[1]).reshape((1,) * (row.ndim - 2) + (-1, 1))
+        thr = np.where(row < 0, np.float32(np.inf), pr[np.maximum(row, 0), col]).astype(np.float32)
+    out = {"threshold": thr, "rank": pts[..., OP_RANK], "row": pts[..., OP_ROW], "tp": pts[..., OP_TP], "fp": pts[..., OP_FP]}
+    out.update(_operating_values(pts, tots))
+    return out
+
+
+def _with_bounds(values, alpha, n_boot):
+    """values: dict of arrays whose axis 0 is the weight row -> row 0 as the point values; with n_boot > 0 also "bootstrap"
+    {key: {"lo", "hi"}}, "n_nan" and "replicates" per key, by bootstrap_metrics' percentile rule."""
+    out = {k: v[0] for k, v in values.items()}
+    if n_boot > 0:
+        out["bootstrap"], out["n_nan"], out["replicates"] = {}, {}, {}
+        for k, v in values.items():
+            if v.dtype.kind != "f":
+                continue
+            reps = v[1:].astype(np.float64)
+            if np.isnan(reps).any():
+                lo, hi, n_nan = _percentiles(reps, alpha)
+            else:                                           # nothing to leave out: every column in one call
+                with np.errstate(invalid="ignore"):         # a threshold of +inf among the replicates
+                    lo, hi = np.percentile(reps, (100.0 * alpha / 2, 100.0 * (1 - alpha / 2)), axis=0)
+                n_nan = np.zeros(reps.shape[1:], np.int64)
+            out["bootstrap"][k], out["n_nan"][k], out["replicates"][k] = {"lo": lo, "hi": hi}, n_nan, reps
+    return out
+
+
+def calibration(y_true, y_prob, n_bins=10, n_boot=0, seed=0, alpha=0.05):
+    """Is a probability what it says?  y_true, y_prob [N, C] device tensors -> calibration_from_tables' keys for the rows as
+    they are (ece, mce, brier per class and macro, the reliability table frac_pos / mean_prob / n per bin, out, bad), after
+    one metrics_reliability call and one host read.  With n_boot > 0 the same call takes bootstrap_weights' n_boot + 1 rows
+    (row 0 is the point value) and "bootstrap" holds {"lo", "hi"} per key (percentiles alpha/2 and 1 - alpha/2 over the
+    replicates that are not NaN), with "n_nan" and "replicates" beside it."""
+    y, p = _inputs(y_true, y_prob)
+    n_boot = max(int(n_boot), 0)
+    w = bootstrap_weights(p.shape[0], n_boot, seed, p.device) if n_boot > 0 else None
+    bins, tot = metrics_reliability(p, y, n_bins=n_bins, weights=w)
+    host = torch.cat([bins.reshape(-1), tot.reshape(-1)]).cpu().numpy()     # the one read
+    out = _with_bounds(calibration_from_tables(host[:bins.numel()].reshape(bins.shape), host[bins.numel():].reshape(tot.shape)),
+                       alpha, n_boot)
+    out["n_bins"] = int(n_bins)
+    return out
+
+
+def _rule(who, rule):
+    """A rule as given by the user -> (index into RULES, its name in the results, target or None)."""
+    if isinstance(rule, str) and rule in RULES[:2]:
+        return RULES.index(rule), rule, None
+    if isinstance(rule, (tuple, list)) and len(rule) == 2 and rule[0] in RULES[2:]:
+        _target(who, rule[0], rule[1])
+        return RULES.index(rule[0]), f"{rule[0]}@{rule[1]}", rule[1]
+    raise L.EcgHipError(f'{who}: a rule is "f1", "youden", ("sensitivity", target) or ("specificity", target), got {rule!r}')
+
+
+def _operating_calls(who, p, y, rules, w):
+    """The metrics_operating calls that cover `rules` (one call serves one sensitivity and one specificity target) ->
+    (names, [(call, rule index)], [(points, totals)])."""
+    parsed = [_rule(who, r) for r in rules]
+    if not parsed:
+        raise L.EcgHipError(f"{who}: no rule given")
+    targets = {OP_SENS: [], OP_SPEC: []}
+    where = []
+    for idx, _, target in parsed:
+        call = 0
+        if target is not None:
+            if target not in targets[idx]:
+                targets[idx].append(target)
+            call = targets[idx].index(target)
+        where.append((call, idx))
+    order = metrics_order(p)[0]
+    calls = []
+    for i in range(max(1, len(targets[OP_SENS]), len(targets[OP_SPEC]))):
+        calls.append(metrics_operating(p, y, order=order, weights=w,
+                                       sensitivity=targets[OP_SENS][i] if i < len(targets[OP_SENS]) else (9, 10),
+                                       specificity=targets[OP_SPEC][i] if i < len(targets[OP_SPEC]) else (9, 10)))
+    return [name for _, name, _ in parsed], where, calls
+
+
+def operating_points(y_true, y_prob, rules=("f1", "youden", ("sensitivity", 0.9), ("specificity", 0.9)), n_boot=0, seed=0,
+                     alpha=0.05):
+    """Where to cut each class.  y_true, y_prob [N, C] device tensors; every rule is "f1" (the best F1), "youden" (the best
+    sensitivity + specificity - 1), ("sensitivity", t) (the first cut whose sensitivity reaches t) or ("specificity", t) (the
+    best sensitivity among the cuts whose specificity is at least t); a target is a number read as Fraction(str(t)) and must
+    have a denominator of at most 1 000 000.  Returns {name: operating_from_points' keys as arrays [C]}, the names being
+    "f1", "youden", "sensitivity@0.9", ...: predicted means prob >= threshold.  One metrics_order, one metrics_operating per
+    distinct pair of targets, one host read.  With n_boot > 0 the calls take bootstrap_weights' rows (row 0 is the point
+    value: the cut is chosen anew in every replicate) and each name also holds "bootstrap" {key: {"lo", "hi"}}, "n_nan" and
+    "replicates" for threshold, f1, sensitivity, specificity and youden."""
+    who = "operating_points"
+    y, p = _inputs(y_true, y_prob)
+    n_boot = max(int(n_boot), 0)
+    w = bootstrap_weights(p.shape[0], n_boot, seed, p.device) if n_boot > 0 else None
+    names, where, calls = _operating_calls(who, p, y, rules, w)
+    res = operating_from_points(torch.stack([c[0] for c in calls]), torch.stack([c[1] for c in calls]), p)   # [calls, B, C, 4]
+    return {name: _with_bounds({k: v[call][..., idx] for k, v in res.items()}, alpha, n_boot)
+            for name, (call, idx) in zip(names, where)}
+
+
+def select_thresholds(y_true, y_prob, rule="f1"):
+    """The thresholds of one rule of operating_points, chosen on these rows, as a fp32 [C] DEVICE tensor (no host read): what
+    tuned_metrics, metrics_confusion and the threshold= of compute_metrics_device / bootstrap_metrics take.  +inf for a class
+    in which no cut is eligible."""
+    y, p = _inputs(y_true, y_prob)
+    _, where, calls = _operating_calls("select_thresholds", p, y, (rule,), None)
+    return _gather_thresholds(calls[0][0], p)[0, :, where[0][1]].contiguous()
+
+
+def tuned_from_confusion(conf):
+    """conf int64 [..., C, 4] (TP, FP, FN, TN) -> "f1_per_class" = 2TP / (2TP + FP + FN) (0 where that is 0 / 0, summarize's
+    rule), "sensitivity_per_class" = TP / (TP + FN), "specificity_per_class" = TN / (TN + FP) (NaN without positives /
+    negatives), and "f1_macro", "sensitivity_macro", "specificity_macro": the means over the classes, NaN if any class is."""
+    c = _host(conf, np.int64)
+    tp, fp, fn, tn = (c[..., i] for i in range(4))
+    f1 = _ratios(2 * tp, 2 * tp + fp + fn)
+    out = {"f1_per_class": np.where(np.isnan(f1), 0.0, f1), "sensitivity_per_class": _ratios(tp, tp + fn),
+           "specificity_per_class": _ratios(tn, tn + fp)}
+    for k in ("f1", "sensitivity", "specificity"):
+        out[k + "_macro"] = out[k + "_per_class"].mean(-1)
+    return out
+
+
+def tuned_metrics(y_val, p_val, y_test, p_test, rule="f1", n_boot=0, seed=0, alpha=0.05):
+    """Thresholds chosen on the validation rows (select_thresholds(y_val, p_val, rule)), applied to the test rows: returns
+    "thresholds" fp32 [C], "confusion" int64 [C, 4] (TP, FP, FN, TN on the test rows) and tuned_from_confusion's keys.  The
+    thresholds never see the test rows.  One host read.  With n_boot > 0 the draws are over the TEST rows (the thresholds
+    stay): "bootstrap" {key: {"lo", "hi"}}, "n_nan" and "replicates"."""
+    thr = select_thresholds(y_val, p_val, rule)
+    y, p = _inputs(y_test, p_test)
+    if p.shape[1] != thr.numel():
+        raise L.EcgHipError(f"tuned_metrics: the validation rows have {thr.numel()} classes, the test rows {p.shape[1]}")
+    n_boot = max(int(n_boot), 0)
+    w = bootstrap_weights(p.shape[0], n_boot, seed, p.device) if n_boot > 0 else None
+    conf = metrics_confusion(p, y, thr.unsqueeze(0), weights=w)[:, 0]                      # [B, C, 4]
+    host = torch.cat([conf.reshape(-1), thr.view(torch.int32).to(torch.int64)]).cpu().numpy()  # the one read
+    c = host[:conf.numel()].reshape(conf.shape)
+    out = _with_bounds(tuned_from_confusion(c), alpha, n_boot)
+    out["thresholds"], out["confusion"] = host[conf.numel():].astype(np.int32).view(np.float32), c[0]
     return out
 
 

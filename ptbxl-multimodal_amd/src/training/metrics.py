@@ -1,11 +1,14 @@
 """Macro AUROC / AUPRC / F1 for multi-label predictions (reference src/training/metrics.py:5-42).
 Epoch-end, host-side, O(N*C) on a few thousand rows: stays on sklearn.
 compute_metrics_device (ecg_hip/metrics.py, re-exported here) gives the same three numbers from device tensors, and
-compare_models beside it says whether two models scored on the same rows differ (DeLong, McNemar, paired bootstrap)."""
+compare_models beside it says whether two models scored on the same rows differ (DeLong, McNemar, paired bootstrap);
+select_thresholds / tuned_metrics choose per-class thresholds on the validation rows and report the test rows at them, and
+calibration says whether a probability means what it says (reliability table, ECE, MCE, Brier)."""
 import numpy as np
 from sklearn import metrics as skm
 
-from ecg_hip.metrics import compare_models, compute_metrics_device  # noqa: F401
+from ecg_hip.metrics import (calibration, compare_models, compute_metrics_device, select_thresholds,  # noqa: F401
+                             tuned_metrics)
 
 
 def _nan_on_value_error(fn, *args, **kw):

@@ -1,7 +1,7 @@
 """Epoch-end metrics: the device path (ecg_hip.metrics) against what it replaces.
 
     python tools/bench_metrics.py [--sizes 2198 21799] [--classes 5] [--n-boot 1000] [--host-reps 50] [--out profiles/metrics_bench.json]
-                                  [--legs metrics compare]
+                                  [--legs metrics compare operating]
 
 Per (N, C), on seeded synthetic predictions of a PTB-XL fold's shape, one JSON line with:
   compute_metrics_device   device tensors -> the three macro numbers on the host (two calls of two launches, one read), against
@@ -14,6 +14,15 @@ Per (N, C), on seeded synthetic predictions of a PTB-XL fold's shape, one JSON l
 of the same rows at n_boot = 0 and at --n-boot, against
   host_numpy_delong        the copy of both models to the host plus DeLong's test by fp64 midranks in numpy and McNemar's counts, and
   torch_device_ops         the same integers (placements by sort + searchsorted, the paired sums) from torch ops, one read.
+--legs operating adds (or, alone, refreshes) an "operating" entry per size: operating_points (four rules) and calibration
+(10 bins) at n_boot = 0, each against
+  host_sklearn             the copy to the host plus precision_recall_curve / roc_curve and an argmax per class, resp.
+                           calibration_curve and brier_score_loss per class, and
+  torch_device_ops         the same integers from torch ops on the device (argsort, cumsum, argmax; bincount), one read;
+and at --n-boot against the only route the tree had before ecg_metrics_operating: metrics_counts(curve=True) over the same
+weight rows plus a torch argmax of F1 and J over the curve (two of the four rules, and no ratios or percentiles after the
+read), at the largest B whose curve fits in 1 GiB, SCALED per replicate; "metrics_operating_and_read" is the like-for-like
+counterpart of that route, the new call and one read of its points at the same B.
 The baselines are those paths, never the code under test.  Whole-call times are host clocks around work that ends in a device
 read; the legs of a comparison run alternately in one process and the minimum of the rounds is kept; each leg is primed by
 time first.  Values are checked too: the device numbers against sklearn's within N * 2^-50.
@@ -206,6 +215,176 @@ def bench_compare(a):
     return out
 
 
+def host_sklearn_operating(y, p, sens=0.9, spec=0.9):
+    """Per class: the best F1 and J and the two target cuts from scikit-learn's curves."""
+    from sklearn import metrics as skm
+    out = []
+    for c in range(y.shape[1]):
+        prec, rec, thr_pr = skm.precision_recall_curve(y[:, c], p[:, c])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            f1 = np.where(prec + rec > 0, 2 * prec * rec / (prec + rec), 0.0)[:-1]
+        fpr, tpr, thr_roc = skm.roc_curve(y[:, c], p[:, c], drop_intermediate=False)
+        i, j = int(np.argmax(f1[::-1])), int(np.argmax(tpr - fpr))
+        s = int(np.argmax(tpr >= sens - 1e-12))
+        ok = np.flatnonzero(fpr <= 1.0 - spec + 1e-12)
+        out.append({"f1": float(f1[::-1][i]), "f1_threshold": float(thr_pr[::-1][i]), "youden": float(tpr[j] - fpr[j]),
+                    "sens_fpr": float(fpr[s]), "spec_tpr": float(tpr[ok].max())})
+    return out
+
+
+def host_sklearn_calibration(y, p, n_bins=10):
+    from sklearn.calibration import calibration_curve
+    from sklearn.metrics import brier_score_loss
+    out = []
+    for c in range(y.shape[1]):
+        frac, mean = calibration_curve(y[:, c], p[:, c], n_bins=n_bins, strategy="uniform")
+        cnt = np.bincount(np.searchsorted(np.linspace(0.0, 1.0, n_bins + 1)[1:-1], p[:, c]), minlength=n_bins)
+        cnt = cnt[cnt > 0]
+        gap = np.abs(frac - mean)
+        out.append({"ece": float((gap * cnt).sum() / cnt.sum()), "mce": float(gap.max()), "brier": float(brier_score_loss(y[:, c], p[:, c]))})
+    return out
+
+
+def _torch_walk(y, p):
+    pt, yt = p.t().contiguous(), y.t().contiguous()
+    order = torch.argsort(pt, dim=1, stable=True, descending=True)
+    ps, ys = torch.gather(pt, 1, order), torch.gather(yt, 1, order)
+    tp, fp = torch.cumsum(ys == 1.0, 1), torch.cumsum(ys == 0.0, 1)
+    end = torch.ones_like(ps, dtype=torch.bool)
+    end[:, :-1] = ps[:, 1:] != ps[:, :-1]
+    return ps, tp, fp, end
+
+
+def torch_device_operating(y, p, sens=(9, 10), spec=(9, 10)):
+    """The four cuts from stock torch ops on the device (finite scores, labels 0 / 1): J, the eligibility tests and the target
+    objectives in int64, F1 as an fp64 ratio; argmax per class, one read."""
+    ps, tp, fp, end = _torch_walk(y, p)
+    P, Q = tp[:, -1:], fp[:, -1:]
+    low = torch.iinfo(torch.int64).min
+    f1 = torch.where(end, (2 * tp).double() / (tp + fp + P).double(), -1.0)
+    j = torch.where(end, tp * Q - fp * P, low)
+    s = torch.where(end & (tp * sens[1] >= sens[0] * P), -fp, low)
+    t = torch.where(end & ((Q - fp) * spec[1] >= spec[0] * Q), tp, low)
+    at = torch.stack([torch.argmax(f1, 1), torch.argmax(j, 1), torch.argmax(s, 1), torch.argmax(t, 1)], 1)      # [C, 4]
+    host = torch.cat([torch.gather(tp, 1, at).reshape(-1), torch.gather(fp, 1, at).reshape(-1), P.reshape(-1), Q.reshape(-1),
+                      torch.gather(ps, 1, at).reshape(-1).view(torch.int32).to(torch.int64)]).cpu().numpy()
+    return host
+
+
+def torch_device_calibration(y, p, n_bins=10):
+    """The reliability table's integers from stock torch ops on the device (scores in [0, 1], labels 0 / 1), one read."""
+    N, C = p.shape
+    q = torch.floor(p * 16777216.0).to(torch.int64)
+    m = torch.clamp((q * n_bins) >> 24, max=n_bins - 1) + n_bins * torch.arange(C, device=p.device)[None, :]
+    pos = (y == 1.0).to(torch.int64)
+    e = torch.abs(q - (pos << 24))
+    flat = m.reshape(-1)
+    table = torch.stack([torch.zeros(C * n_bins, dtype=torch.int64, device=p.device).scatter_add_(0, flat, v.reshape(-1))
+                         for v in (torch.ones_like(q), pos, q)], 1)
+    s = e * e
+    return torch.cat([table.reshape(-1), (s >> 24).sum(0), (s & 0xffffff).sum(0)]).cpu().numpy()
+
+
+def curve_route_operating(M, y, p, order, w, end):
+    """What the tree could do before ecg_metrics_operating: the whole curve of every weight row, then an argmax of F1 and of J
+    over it with torch ops (fp64 F1, int64 J), one read."""
+    fields, _, cv = M.metrics_counts(p, y, order=order, weights=w, curve=True)
+    tp, fp = cv[..., 0].to(torch.int64), cv[..., 1].to(torch.int64)
+    P, Q = fields[..., M.POS].unsqueeze(-1), fields[..., M.NEG].unsqueeze(-1)
+    f1 = torch.where(end, (2 * tp).double() / (tp + fp + P).double(), -1.0)
+    j = torch.where(end, tp * Q - fp * P, torch.iinfo(torch.int64).min)
+    at = torch.stack([torch.argmax(f1, -1), torch.argmax(j, -1)], -1)
+    return torch.cat([torch.gather(tp, -1, at).reshape(-1), torch.gather(fp, -1, at).reshape(-1)]).cpu().numpy()
+
+
+def bench_operating(a):
+    """{N: the "operating" entry}: operating_points and calibration against their counterparts."""
+    from ecg_hip import _lib, metrics as M
+    _lib.call("ecg_check_device")
+    warnings.simplefilter("ignore")
+    dev, out = torch.device("cuda"), {}
+    for N in a.sizes:
+        C = a.classes
+        rng = np.random.default_rng(N)
+        y = (rng.random((N, C)) < 0.25).astype(np.float32)
+        p = (1.0 / (1.0 + np.exp(-(rng.standard_normal((N, C)) + 1.5 * y - 1.0)))).astype(np.float32)
+        yd, pd = torch.from_numpy(y).to(dev), torch.from_numpy(p).to(dev)
+        op_legs = {"operating_points": lambda: M.operating_points(yd, pd),
+                   "host_sklearn": lambda: host_sklearn_operating(yd.cpu().numpy(), pd.cpu().numpy()),
+                   "torch_device_ops": lambda: torch_device_operating(yd, pd)}
+        cal_legs = {"calibration": lambda: M.calibration(yd, pd),
+                    "host_sklearn": lambda: host_sklearn_calibration(yd.cpu().numpy(), pd.cpu().numpy()),
+                    "torch_device_ops": lambda: torch_device_calibration(yd, pd)}
+        got, ref, th = op_legs["operating_points"](), op_legs["host_sklearn"](), op_legs["torch_device_ops"]()
+        worst_op = max(max(abs(got["f1"]["f1"][c] - ref[c]["f1"]), abs(got["youden"]["youden"][c] - ref[c]["youden"]),
+                           abs((1.0 - got["sensitivity@0.9"]["specificity"][c]) - ref[c]["sens_fpr"]),
+                           abs(got["specificity@0.9"]["sensitivity"][c] - ref[c]["spec_tpr"])) for c in range(C))
+        assert worst_op <= 1e-12, worst_op
+        names = ("f1", "youden", "sensitivity@0.9", "specificity@0.9")
+        assert np.array_equal(th[:4 * C].reshape(C, 4), np.stack([got[n]["tp"] for n in names], 1))
+        assert np.array_equal(th[4 * C:8 * C].reshape(C, 4), np.stack([got[n]["fp"] for n in names], 1))
+        cal, cref, cth = cal_legs["calibration"](), cal_legs["host_sklearn"](), cal_legs["torch_device_ops"]()
+        worst_cal = max(max(abs(cal[k][c] - cref[c][k]) for k in ("ece", "mce", "brier")) for c in range(C))
+        q = np.floor(p * np.float32(16777216.0)).astype(np.int64)
+        edge_rows = int(np.isin(q, [(j << 24) // 10 for j in range(1, 10)]).sum())     # (lo, hi] and [lo, hi) may differ there
+        assert edge_rows > 0 or worst_cal <= 2.0 ** -22, worst_cal                      # otherwise: the quantisation
+        bins, tot = M.metrics_reliability(pd, yd)
+        assert np.array_equal(cth[:C * 30].reshape(C, 10, 3), bins[0].cpu().numpy())
+        assert np.array_equal(cth[C * 30:].reshape(2, C).T, tot[0, :, :2].cpu().numpy())
+        iters = {"operating_points": 50, "calibration": 50, "host_sklearn": 5, "torch_device_ops": 20}
+        op_ms, cal_ms = alternately(op_legs, iters, wall_ms), alternately(cal_legs, iters, wall_ms)
+        with _lib.kernel_timing() as kt:
+            for _ in range(10):
+                M.operating_points(yd, pd), M.calibration(yd, pd)
+        entry_ms = {n: float(np.mean(v)) for (n, _), v in kt.result.items()}
+
+        w = M.bootstrap_weights(N, a.n_boot, 0, dev)
+        order = M.metrics_order(pd)[0]
+        Bc = int(min(a.n_boot + 1, (1 << 30) // (C * N * 8)))   # the largest B whose curve fits in 1 GiB
+        wc = w[:Bc].contiguous()
+        ps = torch.gather(pd.t().contiguous(), 1, order.long())
+        end = torch.ones_like(ps, dtype=torch.bool)
+        end[:, :-1] = ps[:, 1:] != ps[:, :-1]
+        pts, _ = M.metrics_operating(pd, yd, order=order, weights=wc)
+        cr = curve_route_operating(M, yd, pd, order, wc, end)
+        assert np.array_equal(cr[:cr.size // 2].reshape(Bc, C, 2), pts[:, :, :2, M.OP_TP].cpu().numpy())      # the same cuts
+        assert np.array_equal(cr[cr.size // 2:].reshape(Bc, C, 2), pts[:, :, :2, M.OP_FP].cpu().numpy())
+        boot_ms = alternately({"operating_points": lambda: M.operating_points(yd, pd, n_boot=a.n_boot, seed=0),
+                               "calibration": lambda: M.calibration(yd, pd, n_boot=a.n_boot, seed=0),
+                               "metrics_operating_and_read": lambda: M.metrics_operating(pd, yd, order=order, weights=wc)[0].cpu(),
+                               "curve_route": lambda: curve_route_operating(M, yd, pd, order, wc, end)},
+                              {"operating_points": 3, "calibration": 3, "metrics_operating_and_read": 5, "curve_route": 2}, wall_ms,
+                              rounds=2)
+        kern_ms = {"metrics_operating_ms_at_B": event_ms(lambda: M.metrics_operating(pd, yd, order=order, weights=w), 5, 0.3),
+                   "metrics_reliability_ms_at_B": event_ms(lambda: M.metrics_reliability(pd, yd, weights=w), 5, 0.3),
+                   "metrics_confusion_ms_at_B": event_ms(lambda: M.metrics_confusion(pd, yd, torch.full((1, C), 0.5, device=dev), weights=w), 5, 0.3)}
+        curve_scaled = boot_ms["curve_route"] * (a.n_boot + 1) / Bc
+        line = {"config": {"workload": f"operating points and calibration of {N} x {C} fp32 predictions on one MI355X", "N": N, "C": C},
+                "operating_points_ms": {k: round(v, 4) for k, v in op_ms.items()},
+                "calibration_ms": {k: round(v, 4) for k, v in cal_ms.items()},
+                "host_sklearn_over_operating_points": round(op_ms["host_sklearn"] / op_ms["operating_points"], 2),
+                "torch_device_ops_over_operating_points": round(op_ms["torch_device_ops"] / op_ms["operating_points"], 2),
+                "host_sklearn_over_calibration": round(cal_ms["host_sklearn"] / cal_ms["calibration"], 2),
+                "torch_device_ops_over_calibration": round(cal_ms["torch_device_ops"] / cal_ms["calibration"], 2),
+                "entry_point_ms": {k: round(v, 4) for k, v in entry_ms.items()},
+                "max_abs_diff_to_sklearn": {"operating_points": worst_op, "calibration": worst_cal, "rows_on_a_bin_edge": edge_rows},
+                "bootstrap": {"n_boot": a.n_boot, "operating_points_ms": round(boot_ms["operating_points"], 3),
+                              "calibration_ms": round(boot_ms["calibration"], 3),
+                              **{k: round(v, 3) for k, v in kern_ms.items()},
+                              "curve_route_ms": round(curve_scaled, 3), "curve_route_scaled": Bc != a.n_boot + 1,
+                              "curve_route_B_timed": Bc, "curve_route_rules": ["f1", "youden"],
+                              "metrics_operating_and_read_ms_at_curve_B": round(boot_ms["metrics_operating_and_read"], 3),
+                              "curve_route_over_metrics_operating_and_read": round(boot_ms["curve_route"] / boot_ms["metrics_operating_and_read"], 2),
+                              "curve_route_over_operating_points": round(curve_scaled / boot_ms["operating_points"], 2),
+                              "points_bytes_per_call": (a.n_boot + 1) * C * 16 * 8, "curve_bytes_per_call": (a.n_boot + 1) * C * N * 8},
+                "thresholds": {n: got[n]["threshold"].tolist() for n in names},
+                "ece": cal["ece"].tolist(), "mce": cal["mce"].tolist(), "brier": cal["brier"].tolist()}
+        print(json.dumps({"metric": "operating_points_ms", "value": line["operating_points_ms"]["operating_points"], "unit": "ms", **line}),
+              flush=True)
+        out[N] = line
+    return out
+
+
 def bench(a):
     from ecg_hip import _lib, metrics as M
     from src.training.metrics import compute_metrics
@@ -279,21 +458,23 @@ def main():
     ap.add_argument("--n-boot", type=int, default=1000)
     ap.add_argument("--host-reps", type=int, default=50)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "metrics_bench.json"))
-    ap.add_argument("--legs", nargs="+", choices=("metrics", "compare"), default=["metrics"])
+    ap.add_argument("--legs", nargs="+", choices=("metrics", "compare", "operating"), default=["metrics"])
     a = ap.parse_args()
     if "metrics" in a.legs:
         res = bench(a)
-    else:                                                   # refresh "compare" in the entries the file already has
+    else:                                                   # refresh the other legs in the entries the file already has
         with open(a.out) as f:
             res = json.load(f)
-    if "compare" in a.legs:
-        for N, entry in bench_compare(a).items():
+    for leg, fn in (("compare", bench_compare), ("operating", bench_operating)):
+        if leg not in a.legs:
+            continue
+        for N, entry in fn(a).items():
             for line in res:
                 if line["config"]["N"] == N and line["config"]["C"] == a.classes:
-                    line["compare"] = entry
+                    line[leg] = entry
                     break
             else:
-                res.append({"config": entry["config"], "compare": entry})
+                res.append({"config": entry["config"], leg: entry})
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
