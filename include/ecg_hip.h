@@ -23,6 +23,21 @@
  *     backward on torch's autograd engine thread.
  *   - Conv1d support envelope: stride 1, dilation 1, groups 1, 1 <= K <= 31,
  *     0 <= pad < K (the reference uses K=15, pad=7 only: src/models/ecg_cnn.py:13).
+ *   - Alignment.  The bf16, recording, beats, template and metrics entry points state theirs where they are declared.
+ *     For the fp32 entry points (Conv1d, BatchNorm / ReLU / MaxPool, Grad-CAM, tail, fused tail, the fp32 input step) the
+ *     rule is: a float tensor needs the 4-byte alignment of its element and nothing more — x, y, dy, dx, dp, p, g, weights
+ *     in state_dict layout, bias, gamma, beta, mean, invstd, running statistics, every gradient destination (dw, db,
+ *     dgamma, dbeta, the tail's), workspaces `ws`, cam / raw / alpha — so parameters and gradient sinks that sit back to
+ *     back in one flat buffer, and views such as x[1:], are served as they are.  Where a kernel has a wider form (8-byte
+ *     pooling pairs, 16-byte rows, 16-byte slab sums, dY by LDS-DMA) the host takes it only when EVERY pointer the wide
+ *     access touches is aligned for it and runs the 4-byte form otherwise: same values (same bits where the entry point
+ *     says so).  Four kinds of argument are buffers only the caller of this ABI allocates and a wide access cannot do
+ *     without; they are refused (ECG_EINVAL naming the argument, nothing launched) when misaligned: the packed weights
+ *     w_fwd / w_bwd where the matrix-core kernels apply (16 bytes: streamed by 16-byte LDS-DMA), stat_partials (8 bytes:
+ *     one (sum, sum of squares) pair per load), num_batches_tracked (8 bytes: int64) and the one-launch BatchNorm
+ *     backward's counters (8 bytes).  Each entry point repeats what applies to it; DESIGN.md section 13 has the table
+ *     with the source lines, ecg_conv1d_bwd_weight_forms / ecg_bn_relu_pool_pair_forms / ecg_rows_vec4 report the form a
+ *     call takes.
  *   - Non-finite values (NaN, +-Inf) are ordinary data (tests/test_gpu_values.py):
  *     PROPAGATION  MaxPool1d(2) returns NaN when either element of the pair is NaN (otherwise the first element wins a
  *       tie), ReLU clips only what compares <= 0 (a NaN passes, forward and as the mask of the backward, where the pool
@@ -74,7 +89,10 @@ int ecg_check_device(void);
 /* Packed weights: w [C_out][C_in][K] (state_dict layout) ->
  *   w_fwd [K][C_in][C_out]            (forward operand)
  *   w_bwd [K][C_out][C_in], tap-flipped: w_bwd[k][co][ci] = w[co][ci][K-1-k]  (input-grad operand)
- * Either output may be NULL.  Each holds C_out*C_in*K floats. */
+ * Either output may be NULL.  Each holds C_out*C_in*K floats.
+ * Alignment: w (a parameter) 4 bytes; the pack itself writes 4 bytes at a time, but the matrix-core kernels that READ
+ * w_fwd / w_bwd need them 16-byte aligned (see ecg_conv1d_fwd): allocate them so.  The same holds per problem for the
+ * two grouped packs below. */
 int ecg_conv1d_pack_weights(const float *w, float *w_fwd, float *w_bwd,
                             int C_out, int C_in, int K, ecg_stream_t stream);
 
@@ -102,7 +120,11 @@ int ecg_conv1d_fwd_stat_partials(int N, int C_in, int C_out, int L, int K, int p
  * x [N][C_in][L], w_fwd packed as above, bias [C_out] or NULL, y [N][C_out][Lo],
  * Lo = L + 2*pad - K + 1.
  * stat_partials (nullable): [C_out][P][2] per-producer (sum y, sum y^2) over the producer's
- * outputs, consumed by ecg_bn_finalize (train-mode BatchNorm statistics fused in the epilogue). */
+ * outputs, consumed by ecg_bn_finalize (train-mode BatchNorm statistics fused in the epilogue).
+ * Alignment: x, bias, y, stat_partials 4 bytes (stat_partials' READERS need 8: ecg_bn_finalize).  w_fwd 16 bytes where the
+ * matrix-core kernel applies (K == 15, C_in % 4 == 0, C_out % 32 == 0: it streams the weights by 16-byte LDS-DMA) —
+ * refused otherwise, before the launch; 4 bytes on the direct kernel's shapes.  The same holds for w_bwd of
+ * ecg_conv1d_bwd_data[_ld] and ecg_conv1d_bwd_weight_data_ld (roles of C_in / C_out swapped) with dy, dx at 4 bytes. */
 int ecg_conv1d_fwd(const float *x, const float *w_fwd, const float *bias, float *y,
                    float *stat_partials, int N, int C_in, int C_out, int L, int K, int pad,
                    ecg_stream_t stream);
@@ -145,11 +167,31 @@ int ecg_conv1d_bwd_weight_data_ld(const float *dy, int ldy, const float *x, cons
                                   float *dw, float *db, float *dx, float *ws, int N, int C_in,
                                   int C_out, int L, int K, int pad, ecg_stream_t stream);
 
+/* Which kernels ecg_conv1d_bwd_weight_bias_ld and ecg_conv1d_bwd_weight_data_ld run for exactly these ADDRESSES (device
+ * pointers as integers; db may be 0) and this shape.  A pure host query: it launches nothing and answers from the functions
+ * the launch itself decides with.  form[0..5] =
+ *   [0] slab kernel: ECG_WGRAD_SLABS_FAST_FIR / _DMA (dY streamed by LDS-DMA: needs dy 16-byte aligned and the row stride of
+ *       ecg_conv1d_dy_row_stride) / _REGISTER (4-byte loads: dense rows or any other base) / _DIRECT (shapes without MFMA kernel)
+ *   [1] channel tile (128 / 64 / 32; 0: direct)      [2] time steps per DMA stage (64 / 128; 0: not a DMA form)
+ *   [3] slabs S written to ws
+ *   [4] reduce: ECG_WGRAD_REDUCE_FLOAT4 (16-byte loads and stores: needs ws, dw and db 16-byte aligned, slab and C_out multiples
+ *       of 4, >= 1024 groups) / _GROUPED (4-byte; any base) / _FAST_FIR (4-byte; behind the fast-FIR slab kernel)
+ *   [5] G, the waves that share a 64-output group in the grouped reduce (1 otherwise).
+ * The rider workgroups of ecg_conv1d_bwd_weight_data_ld run the reduce this reports.  Tests use it to know which form ran. */
+enum { ECG_WGRAD_SLABS_FAST_FIR = 0, ECG_WGRAD_SLABS_DMA = 1, ECG_WGRAD_SLABS_REGISTER = 2, ECG_WGRAD_SLABS_DIRECT = 3 };
+enum { ECG_WGRAD_REDUCE_GROUPED = 0, ECG_WGRAD_REDUCE_FLOAT4 = 1, ECG_WGRAD_REDUCE_FAST_FIR = 2 };
+int ecg_conv1d_bwd_weight_forms(uintptr_t dy, int ldy, uintptr_t dw, uintptr_t db, uintptr_t ws, int N, int C_in,
+                                int C_out, int L, int K, int pad, int form[6]);
+
 /* Workspace (floats) for ecg_conv1d_bwd_weight_bias. */
 size_t ecg_conv1d_bwd_weight_ws_floats(int N, int C_in, int C_out, int L, int K, int pad);
 /* dw[co,ci,k] = sum_n sum_t dy[n,co,t]*x[n,ci,t+k-pad] (state_dict layout [C_out][C_in][K]);
  * db[co] = sum_n sum_t dy[n,co,t] (nullable).  Deterministic: split partial slabs in ws are
- * summed in a fixed order, no float atomics. */
+ * summed in a fixed order, no float atomics.
+ * Alignment (all weight-gradient entry points): dy, x, dw, db, ws 4 bytes.  A 16-byte aligned dy with the row stride of
+ * ecg_conv1d_dy_row_stride is streamed by LDS-DMA, any other dy through registers; ws, dw and db all 16-byte aligned (and
+ * a large enough slab) take the float4 reduce, anything else the grouped one.  The slab kernels differ in summation order
+ * (both within the bounds of tests/test_gpu_ops.py); both reduces sum the slabs in double, in a fixed order. */
 int ecg_conv1d_bwd_weight_bias(const float *dy, const float *x, float *dw, float *db, float *ws,
                                int N, int C_in, int C_out, int L, int K, int pad,
                                ecg_stream_t stream);
@@ -250,7 +292,9 @@ int ecg_bn_stat_partials(const float *y, float *stat_partials, int N, int C, int
 
 /* Train-mode statistics from partials (summed in double, fixed order):
  * mean, biased var -> invstd = 1/sqrt(var+eps);  running_mean/var (nullable) updated with
- * `momentum` and the UNBIASED variance;  *num_batches_tracked (nullable, device int64) += 1. */
+ * `momentum` and the UNBIASED variance;  *num_batches_tracked (nullable, device int64) += 1.
+ * Alignment: stat_partials and num_batches_tracked 8 bytes (refused otherwise: a partial is read as one 8-byte pair);
+ * mean, invstd, running statistics 4.  The same holds for ecg_bn_stats_relu_pool_fwd and the two bf16-row forms. */
 int ecg_bn_finalize(const float *stat_partials, int P, long long count,
                     float *mean, float *invstd, float *running_mean, float *running_var,
                     long long *num_batches_tracked, int C, float momentum, float eps,
@@ -259,7 +303,11 @@ int ecg_bn_finalize(const float *stat_partials, int P, long long count,
 /* invstd[c] = 1/sqrt(var[c] + eps)  (eval mode: from running_var) */
 int ecg_bn_invstd(const float *var, float *invstd, int C, float eps, ecg_stream_t stream);
 
-/* p[n,c,j] = relu(max(a[2j], a[2j+1])),  a = (y-mean)*(invstd*gamma)+beta,  Lp = L/2; NaN if either a is NaN */
+/* p[n,c,j] = relu(max(a[2j], a[2j+1])),  a = (y-mean)*(invstd*gamma)+beta,  Lp = L/2; NaN if either a is NaN
+ * Alignment (this pass, ecg_bn_stats_relu_pool_fwd mode 0 and the two-pass backward ecg_bn_relu_pool[_gap]_bwd[_ld]): every
+ * pointer 4 bytes.  An 8-byte aligned y with even L is read one pooling pair per 8-byte load, any other y by two 4-byte
+ * loads: same arithmetic in the same order, same bits.  p, dp, dy and the per-channel vectors are accessed 4 bytes at a
+ * time (the _gap_ forward reads y that way too). */
 int ecg_bn_relu_pool_fwd(const float *y, const float *gamma, const float *beta,
                          const float *mean, const float *invstd, float *p,
                          int N, int C, int L, ecg_stream_t stream);
@@ -293,13 +341,21 @@ int ecg_bn_stats_relu_pool_fwd(const float *stat_partials, int P, long long coun
  *   communication kernel waiting for a late peer) costs time, never correctness.  Use the two-pass form while collectives
  *   run on the device during backward (ecg_hip.functional.declare_backward_collectives).
  *   gap != 0: dp is dg [N][C] (the global-average-pool form).  The two forms associate the partial sums differently
- *   (both deterministic). */
+ *   (both deterministic).
+ *   Alignment: counters 8 bytes (refused otherwise); everything else 4.  y 8-byte aligned with even L: 8-byte pair loads;
+ *   then, and when dy is 8-byte aligned with even ldy as well, 8-byte pair stores into dy — decided from dy's own
+ *   address.  Same bits in every combination. */
 int ecg_bn_relu_pool_bwd_one_launch_splits(int N, int C, int L, int ldy);
 size_t ecg_bn_relu_pool_bwd_one_launch_counter_uints(int N, int C, int L, int ldy);
 int ecg_bn_relu_pool_bwd_one_launch(const float *y, const float *dp, const float *gamma, const float *beta,
                                     const float *mean, const float *invstd, float *dy, int ldy,
                                     float *dgamma, float *dbeta, uint32_t *counters, int N, int C, int L,
                                     int train, int gap, int spin_polls, ecg_stream_t stream);
+/* Pure host query (nothing is launched) of the pair decisions of the BatchNorm passes for the given ADDRESSES (device
+ * pointers as integers; dy may be 0), answered by the predicates the launches decide with: form[0] = 1 when y's pooling
+ * pairs are loaded 8 bytes at a time (forward pool pass, two-pass backward, one-launch backward), form[1] = 1 when the
+ * one-launch backward stores dy pairs 8 bytes at a time.  Tests use it to know which form ran. */
+int ecg_bn_relu_pool_pair_forms(uintptr_t y, uintptr_t dy, int L, int ldy, int form[2]);
 
 size_t ecg_bn_relu_pool_bwd_ws_floats(int N, int C, int L);
 /* Backward of the fused tail: dp [N][C][L/2] -> dy [N][C][L], dgamma[C], dbeta[C].
@@ -320,7 +376,8 @@ int ecg_bn_relu_pool_bwd_ld(const float *y, const float *dp, const float *gamma,
 /* Inference: a whole ConvBlock in ONE launch — Conv1d, eval-mode BatchNorm1d (running statistics)
  * folded into the epilogue, ReLU and MaxPool1d(2); only the pooled activation p [N][C_out][Lo/2]
  * is written (reference test path scripts/06_ecg_baseline_test.py:69-106).  Covered shapes:
- * ecg_conv1d_bn_relu_pool_eval_supported() != 0 (K = 15, C_in % 4 == 0, C_out % 32 == 0). */
+ * ecg_conv1d_bn_relu_pool_eval_supported() != 0 (K = 15, C_in % 4 == 0, C_out % 32 == 0).
+ * Alignment (both eval blocks): w_fwd 16 bytes (refused otherwise); x, bias, gamma, beta, running statistics, p / g 4. */
 int ecg_conv1d_bn_relu_pool_eval_supported(int C_in, int C_out, int K, int pad);
 int ecg_conv1d_bn_relu_pool_eval_fwd(const float *x, const float *w_fwd, const float *bias,
                                      const float *gamma, const float *beta,
@@ -406,6 +463,8 @@ int ecg_bn_relu_pool_gap_bwd_ld(const float *y, const float *dg, const float *ga
  * Covered (ecg_gradcam_supported): C % 32 == 0, 32 <= C <= 256, 2 <= Lo <= 5792, 1 <= K <= 8,
  * S >= 1; odd Lo drops its last position from the pool as MaxPool1d(2) does.  Fixed summation
  * order, no atomics: the result of a sample does not depend on N, on its position in the batch or on K.
+ * Alignment: every pointer 4 bytes.  cam rows are stored 16 bytes at a time when S % 4 == 0 and cam is 16-byte aligned
+ * (ecg_rows_vec4(cam, 0, S)), one float at a time otherwise: same values, same bits.
  * ---------------------------------------------------------------------------------- */
 int ecg_gradcam_supported(int C, int Lo, int K, int S);
 size_t ecg_gradcam_ws_floats(int N, int C, int Lo, int K, int S);
@@ -428,6 +487,9 @@ int ecg_maxpool2_bwd(const float *x, const float *dp, float *dx, int rows, int L
 
 /* ------------------------------------------------------------------------------------
  * Tail — AdaptiveAvgPool1d(1), Linear, FiLM, BCE-with-logits.
+ * Alignment (this section and the fused tail below, ecg_transpose and ecg_linear_wgrad_grouped included): every float
+ * pointer 4 bytes — all accesses are 4 bytes wide, so weights, biases and gradient destinations may sit anywhere in a
+ * flat parameter / gradient buffer; running_sum (double) 8.
  * ---------------------------------------------------------------------------------- */
 
 /* g[r] = mean_t p[r][t], r in [0, rows)  — src/models/ecg_cnn.py:46,62 */
@@ -535,7 +597,13 @@ int ecg_wfdb16_physical(const int16_t *d, const double *gain, const int *baselin
 int ecg_wfdb16_zscore(const int16_t *d, const double *gain, const int *baseline, float *out,
                       float *stats, int B, int T, int leads, ecg_stream_t stream);
 /* Per-lead z-score, (x-mean)/(std+1e-6) with population std.  x [rows][T] -> out [rows][T] (in place
- * allowed); stats [rows][2] receives (mean, std + 1e-6) per row. */
+ * allowed); stats [rows][2] receives (mean, std + 1e-6) per row.
+ * Alignment (the fp32 side of the input step: out of ecg_wfdb16_physical / _zscore / _windows[_resampled], x and out here):
+ * 4 bytes.  Rows are walked 16 bytes at a time when T % 4 == 0 and the pointers the walk touches are 16-byte aligned — the
+ * statistics pass asks that of x, the apply pass of x and out, the fused int16 kernel of out — and one float at a time
+ * otherwise, with the same left-to-right chains: same bits.  ecg_rows_vec4(a, b, n) is that predicate as a pure host query
+ * (addresses as integers, b = 0 when one pointer is walked): 1 = the 16-byte walk. */
+int ecg_rows_vec4(uintptr_t a, uintptr_t b, int n);
 int ecg_zscore_rows(const float *x, float *out, float *stats, int rows, int T, ecg_stream_t stream);
 /* The same step for CONTINUOUS recordings d [R][Ttot][leads], read in place: window w of recording r starts at sample
  * first + w*hop — or at last_start when last_start >= 0 and w == W-1 (the "shifted tail" window that ends with the

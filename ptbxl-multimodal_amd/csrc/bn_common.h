@@ -104,12 +104,20 @@ __device__ __forceinline__ void bn_finalize_block(const BnFin &f, int c, bool wr
     mu_out = res[0]; is_out = res[1];
 }
 
+// bn_finalize_block reads a channel's (sum, sum of squares) partial as ONE 8-byte word and the batch counter is an int64:
+// both are buffers the caller allocates (never parameters), refused when they are not 8-byte aligned
+inline int check_fin_aligned(const char *who, const float *partials, const long long *nbt) {
+    ECG_REQUIRE((reinterpret_cast<uintptr_t>(partials) & 7) == 0, "%s: stat_partials must be 8-byte aligned", who);
+    ECG_REQUIRE((reinterpret_cast<uintptr_t>(nbt) & 7) == 0, "%s: num_batches_tracked must be 8-byte aligned", who);
+    return ECG_OK;
+}
+
 inline int check_fin(const char *who, const BnFin &f, int C) {
     ECG_REQUIRE(f.partials && f.mean && f.invstd, "%s: null pointer", who);
     ECG_REQUIRE(f.P > 0 && C > 0 && f.count > 0, "%s: P=%d C=%d count=%g", who, f.P, C, f.count);
     ECG_REQUIRE((f.running_mean == nullptr) == (f.running_var == nullptr),
                 "%s: running_mean/var must both be given or both NULL", who);
-    return ECG_OK;
+    return check_fin_aligned(who, f.partials, f.nbt);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -337,7 +337,9 @@ __device__ __forceinline__ unsigned long long res_word(float v) {      // {value
     return (1ull << 32) | (unsigned long long)__float_as_uint(v);
 }
 
-template <bool AL8>
+// AL8: 8-byte pair loads of y (host: pairs_aligned); ST8: 8-byte pair stores into dy (host: resident_pair_stores) — two
+// tensors, two addresses, two decisions.
+template <bool AL8, bool ST8>
 __global__ __launch_bounds__(kResThreads) void bn_bwd_resident_kernel(
     const float *__restrict__ y, const float *__restrict__ g, const float *__restrict__ gamma,
     const float *__restrict__ beta, const float *__restrict__ mean, const float *__restrict__ invstd,
@@ -505,7 +507,7 @@ __global__ __launch_bounds__(kResThreads) void bn_bwd_resident_kernel(
         const float o0 = train ? gi * (da0 - k1 - (y0[i] - mu) * is * k2) : gi * da0;   // (eval: no 0 * xhat of a non-finite y)
         if (has1) {
             const float o1 = train ? gi * (da1 - k1 - (y1[i] - mu) * is * k2) : gi * da1;
-            if (AL8 && (ldy & 1) == 0) *reinterpret_cast<float2 *>(dr + t) = make_float2(o0, o1);
+            if (ST8) *reinterpret_cast<float2 *>(dr + t) = make_float2(o0, o1);
             else { dr[t] = o0; dr[t + 1] = o1; }
         } else dr[t] = o0;
     }
@@ -562,6 +564,11 @@ using namespace ecg;
 
 // every pooling pair (2j, 2j+1) of every row is 8-byte aligned: even rows from an 8-byte aligned base
 static bool pairs_aligned(const float *y, int L) { return (L & 1) == 0 && (reinterpret_cast<uintptr_t>(y) & 7) == 0; }
+// the one-launch backward writes the pair (dy[2j], dy[2j+1]) as ONE 8-byte store where it loaded the y pair as one: that
+// takes even dy rows from an 8-byte aligned dy base as well — dy's own address, not y's
+static bool resident_pair_stores(const float *y, const float *dy, int L, int ldy) {
+    return pairs_aligned(y, L) && (ldy & 1) == 0 && (reinterpret_cast<uintptr_t>(dy) & 7) == 0;
+}
 
 static int check_ncl(const char *who, int N, int C, int L) {
     ECG_REQUIRE(N > 0 && C > 0 && L > 0, "%s: N=%d C=%d L=%d must be > 0", who, N, C, L);
@@ -590,6 +597,8 @@ ECG_API int ecg_bn_finalize(const float *stat_partials, int P, long long count, 
     ECG_REQUIRE(P > 0 && C > 0 && count > 0, "bn_finalize: P=%d C=%d count=%lld", P, C, count);
     ECG_REQUIRE((running_mean == nullptr) == (running_var == nullptr),
                 "bn_finalize: running_mean/var must both be given or both NULL");
+    int rc = check_fin_aligned("bn_finalize", stat_partials, num_batches_tracked);
+    if (rc) return rc;
     const BnFin f{stat_partials, P, (double)count, mean, invstd, running_mean, running_var, num_batches_tracked,
                   momentum, eps};
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, as_stream(stream), f);
@@ -759,6 +768,14 @@ ECG_API int ecg_bn_relu_pool_bwd_one_launch_splits(int N, int C, int L, int ldy)
     return resident_splits(N, C, L, ldy);
 }
 
+// Which pair accesses the BatchNorm passes take for exactly these addresses: the predicates the launches decide with.
+ECG_API int ecg_bn_relu_pool_pair_forms(uintptr_t y, uintptr_t dy, int L, int ldy, int form[2]) {
+    ECG_REQUIRE(form && L > 0 && ldy >= L, "bn_relu_pool_pair_forms: L=%d ldy=%d", L, ldy);
+    form[0] = pairs_aligned(reinterpret_cast<const float *>(y), L) ? 1 : 0;
+    form[1] = resident_pair_stores(reinterpret_cast<const float *>(y), reinterpret_cast<const float *>(dy), L, ldy) ? 1 : 0;
+    return ECG_OK;
+}
+
 ECG_API size_t ecg_bn_relu_pool_bwd_one_launch_counter_uints(int N, int C, int L, int ldy) {
     const int S = ecg_bn_relu_pool_bwd_one_launch_splits(N, C, L, ldy);
     return S > 1 ? (size_t)C * (4 * (size_t)S + 1) : 0;      // 2 S 64-bit words per channel + one leave count per channel
@@ -783,12 +800,13 @@ ECG_API int ecg_bn_relu_pool_bwd_one_launch(const float *y, const float *dp, con
     const float bcast = gap ? 1.0f / (float)(L / 2) : 0.f;
     ECG_REQUIRE(!gap || L >= 2, "bn_relu_pool_bwd_one_launch: L=%d leaves an empty pooled row", L);
     hipStream_t st = as_stream(stream);
-    if (pairs_aligned(y, L))
-        hipLaunchKernelGGL((bn_bwd_resident_kernel<true>), dim3(C, S), dim3(kResThreads), 0, st, y, dp, gamma, beta, mean,
-                           invstd, S, (double)N * L, dgamma, dbeta, dy, N, C, L, ldy, bcast, train, words, left, spin);
-    else
-        hipLaunchKernelGGL((bn_bwd_resident_kernel<false>), dim3(C, S), dim3(kResThreads), 0, st, y, dp, gamma, beta, mean,
-                           invstd, S, (double)N * L, dgamma, dbeta, dy, N, C, L, ldy, bcast, train, words, left, spin);
+#define ECG_RES(AL8, ST8) hipLaunchKernelGGL((bn_bwd_resident_kernel<AL8, ST8>), dim3(C, S), dim3(kResThreads), 0, st, y, dp, gamma, \
+                                             beta, mean, invstd, S, (double)N * L, dgamma, dbeta, dy, N, C, L, ldy, bcast, train, \
+                                             words, left, spin)
+    if (!pairs_aligned(y, L)) ECG_RES(false, false);
+    else if (resident_pair_stores(y, dy, L, ldy)) ECG_RES(true, true);
+    else ECG_RES(true, false);
+#undef ECG_RES
     return check_launch("bn_bwd_resident_kernel");
 }
 

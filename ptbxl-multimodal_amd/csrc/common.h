@@ -29,6 +29,13 @@ inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 #define ECG_REQUIRE(cond, ...) \
     do { if (!(cond)) return ::ecg::fail(ECG_EINVAL, __VA_ARGS__); } while (0)
 
+// Rows of n floats behind a (and b, NULL = not part of the walk) can be walked as float4: whole float4s per row and
+// 16-byte aligned bases, so every row starts on a 16-byte boundary.  THE predicate of the input step's and Grad-CAM's
+// float4 / scalar walks, on the host and inside the kernels; ecg_rows_vec4 reports it.
+__host__ __device__ inline bool rows_vec4(const void *a, const void *b, int n) {
+    return (n & 3) == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
+}
+
 // ---- device helpers ----------------------------------------------------------------
 // Lane reductions: the first four butterfly levels are DPP row operations (fused into
 // v_add_f32_dpp, ~1 issue slot each); only the 16- and 32-lane levels need the LDS crossbar

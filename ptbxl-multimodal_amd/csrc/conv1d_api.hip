@@ -35,6 +35,11 @@ int mfma_wgrad(const float *dy, int ldy, const float *x, float *dw, float *db, f
 int mfma_wgrad_slabs(const float *dy, int ldy, const float *x, float *dw, float *db, float *ws, int N,
                      int Cin, int Cout, int L, int K, int pad, hipStream_t st, WgradReduce *red);
 int mfma_wgrad_reduce(const WgradReduce &red, hipStream_t st);
+void mfma_wgrad_form(const float *dy, int ldy, int N, int Cin, int Cout, int L, int K, int pad, int form[4], size_t *slab_floats);
+int direct_wgrad_splits(int N, int Cin, int Cout, int K);
+WgradReduce wgrad_reduce_describe(const float *ws, float *dw, float *db, size_t wslab, int Cin, int Cout, int S);
+static_assert(WGR_GROUPED == ECG_WGRAD_REDUCE_GROUPED && WGR_FLOAT4 == ECG_WGRAD_REDUCE_FLOAT4 && WGR_FFA == ECG_WGRAD_REDUCE_FAST_FIR,
+              "the reduce forms are reported as they are numbered");
 int mfma_fwd_rider(const float *x, int ldx, const float *wp, float *y, int N, int Cin, int Cout, int L, int K, int pad,
                    WgradReduce red, hipStream_t st);
 
@@ -57,6 +62,16 @@ static int check_conv_grad(const char *who, bool ptrs, int ldy, bool strided, in
     ECG_REQUIRE(ldy >= Lo, "%s: dY row stride %d < row length %d", who, ldy, Lo);
     ECG_REQUIRE(strided || ldy == Lo, "%s: this shape needs dense dY rows (stride %d != %d); "
                 "use the stride ecg_conv1d_dy_row_stride returns", who, ldy, Lo);
+    return ECG_OK;
+}
+
+// The matrix-core kernels stream the packed weights global -> LDS by DMA, 16 bytes per lane (conv1d_mfma.hip: glds16): a
+// packed operand that is only 4-byte aligned is refused before anything is launched.  (The direct kernels read 4 bytes at
+// a time: no requirement there.  Packed weights are buffers the caller allocates for ecg_conv1d_pack_weights, never
+// parameters: nothing a framework hands over ends up here misaligned.)
+static int check_packed(const char *who, const char *arg, const float *wp) {
+    ECG_REQUIRE((reinterpret_cast<uintptr_t>(wp) & 15) == 0, "%s: %s must be 16-byte aligned (the matrix-core kernels "
+                "stream the packed weights by 16-byte LDS-DMA)", who, arg);
     return ECG_OK;
 }
 }  // namespace ecg
@@ -111,8 +126,11 @@ ECG_API int ecg_conv1d_fwd(const float *x, const float *w_fwd, const float *bias
     int rc = check_conv_shape(N, C_in, C_out, L, K, pad);
     if (rc) return rc;
     ECG_REQUIRE(x && w_fwd && y, "conv1d_fwd: null pointer");
-    if (mfma_fwd_supported(C_in, C_out, K, pad))
+    if (mfma_fwd_supported(C_in, C_out, K, pad)) {
+        rc = check_packed("conv1d_fwd", "w_fwd", w_fwd);
+        if (rc) return rc;
         return mfma_fwd(x, L, w_fwd, bias, y, stat_partials, N, C_in, C_out, L, K, pad, as_stream(stream));
+    }
     return direct_fwd(x, w_fwd, bias, y, stat_partials, N, C_in, C_out, L, K, pad, as_stream(stream));
 }
 
@@ -142,6 +160,7 @@ ECG_API int ecg_conv1d_bwd_data_ld(const float *dy, int ldy, const float *w_bwd,
     const bool mfma = mfma_fwd_supported(C_out, C_in, K, padb);
     int rc = check_conv_grad("conv1d_bwd_data", dy && w_bwd && dx, ldy, mfma, N, C_in, C_out, L, K, pad);
     if (rc) return rc;
+    if (mfma && (rc = check_packed("conv1d_bwd_data", "w_bwd", w_bwd))) return rc;
     if (mfma) return mfma_fwd(dy, ldy, w_bwd, nullptr, dx, nullptr, N, C_out, C_in, Lo, K, padb, as_stream(stream));
     return direct_fwd(dy, w_bwd, nullptr, dx, nullptr, N, C_out, C_in, Lo, K, padb, as_stream(stream));
 }
@@ -166,6 +185,27 @@ ECG_API int ecg_conv1d_bwd_weight_bias_ld(const float *dy, int ldy, const float 
     return direct_wgrad(dy, x, dw, db, ws, N, C_in, C_out, L, K, pad, as_stream(stream));
 }
 
+// Which kernels ecg_conv1d_bwd_weight_bias_ld / ecg_conv1d_bwd_weight_data_ld run for exactly these pointers and this shape:
+// the functions the launch itself decides with, nothing launched.
+ECG_API int ecg_conv1d_bwd_weight_forms(uintptr_t dy, int ldy, uintptr_t dw, uintptr_t db, uintptr_t ws, int N, int C_in,
+                                        int C_out, int L, int K, int pad, int form[6]) {
+    int rc = check_conv_shape(N, C_in, C_out, L, K, pad);
+    if (rc) return rc;
+    ECG_REQUIRE(form, "conv1d_bwd_weight_forms: null output");
+    ECG_REQUIRE(ldy >= L + 2 * pad - K + 1, "conv1d_bwd_weight_forms: dY row stride %d < row length %d", ldy, L + 2 * pad - K + 1);
+    size_t wslab = (size_t)C_out * C_in * K;
+    if (mfma_wgrad_supported(C_in, C_out, K)) {
+        mfma_wgrad_form(reinterpret_cast<const float *>(dy), ldy, N, C_in, C_out, L, K, pad, form, &wslab);
+    } else {
+        form[0] = ECG_WGRAD_SLABS_DIRECT; form[1] = 0; form[2] = 0; form[3] = direct_wgrad_splits(N, C_in, C_out, K);
+    }
+    if (form[0] == ECG_WGRAD_SLABS_FAST_FIR) { form[4] = ECG_WGRAD_REDUCE_FAST_FIR; form[5] = 1; return ECG_OK; }
+    const WgradReduce r = wgrad_reduce_describe(reinterpret_cast<const float *>(ws), reinterpret_cast<float *>(dw),
+                                                reinterpret_cast<float *>(db), wslab, C_in, C_out, form[3]);
+    form[4] = r.form; form[5] = r.G;
+    return ECG_OK;
+}
+
 ECG_API int ecg_conv1d_bwd_weight_bias(const float *dy, const float *x, float *dw, float *db,
                                        float *ws, int N, int C_in, int C_out, int L, int K, int pad,
                                        ecg_stream_t stream) {
@@ -184,6 +224,7 @@ ECG_API int ecg_conv1d_bwd_weight_data_ld(const float *dy, int ldy, const float 
     int rc = check_conv_grad("conv1d_bwd_weight_data", dy && x && w_bwd && dw && dx && ws, ldy, wg_mfma && dg_mfma, N, C_in, C_out,
                              L, K, pad);
     if (rc) return rc;
+    if (dg_mfma && (rc = check_packed("conv1d_bwd_weight_data", "w_bwd", w_bwd))) return rc;
     hipStream_t st = as_stream(stream);
     WgradReduce red;
     rc = wg_mfma ? mfma_wgrad_slabs(dy, ldy, x, dw, db, ws, N, C_in, C_out, L, K, pad, st, &red)
@@ -214,6 +255,8 @@ ECG_API int ecg_conv1d_bn_relu_pool_eval_fwd(const float *x, const float *w_fwd,
     const int Lo = L + 2 * pad - K + 1;
     if (Lo / 2 == 0) return ECG_OK;
     ECG_REQUIRE(p, "conv1d_bn_relu_pool_eval_fwd: null output");
+    rc = check_packed("conv1d_bn_relu_pool_eval_fwd", "w_fwd", w_fwd);
+    if (rc) return rc;
     return mfma_fwd_eval_pool(x, w_fwd, bias, gamma, beta, running_mean, running_var, eps, p, N,
                               C_in, C_out, L, K, pad, as_stream(stream), 0);
 }
@@ -234,6 +277,8 @@ ECG_API int ecg_conv1d_bn_relu_pool_gap_eval_fwd(const float *x, const float *w_
     ECG_REQUIRE(mfma_fwd_eval_gap_supported(C_in, C_out, L, K, pad),
                 "conv1d_bn_relu_pool_gap_eval_fwd: shape not covered (the conv output row must fit one time tile; "
                 "query ecg_conv1d_bn_relu_pool_gap_eval_supported)");
+    rc = check_packed("conv1d_bn_relu_pool_gap_eval_fwd", "w_fwd", w_fwd);
+    if (rc) return rc;
     return mfma_fwd_eval_pool(x, w_fwd, bias, gamma, beta, running_mean, running_var, eps, g, N,
                               C_in, C_out, L, K, pad, as_stream(stream), 1);
 }

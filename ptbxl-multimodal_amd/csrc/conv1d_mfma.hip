@@ -1411,12 +1411,28 @@ size_t mfma_wgrad_ws_floats(int N, int Cin, int Cout, int L, int K, int pad) {
     return need;
 }
 
+// The plan of ONE call: the LDS-DMA forms stream 16 bytes per lane from dy + a multiple of the row stride, so they need rows
+// the stages tile (wgrad_dma_rows) AND a 16-byte aligned base; anything else takes the register-staged kernel (4-byte loads).
+// 128-float stages are a DMA form too: never without `dma` (wgrad_dma_rows(.., 128) implies wgrad_dma_rows(.., 64), so the
+// base is what decides).
+static WgPlan wgrad_plan_for(const float *dy, int ldy, int N, int Cin, int Cout, int Lo, int K) {
+    const bool dma = wgrad_dma_rows(ldy, Lo, 64) && (reinterpret_cast<uintptr_t>(dy) & 15) == 0;
+    return wgrad_plan(N, Cin, Cout, Lo, K, dma, dma && wgrad_dma_rows(ldy, Lo, 128));
+}
+
+// what ecg_conv1d_bwd_weight_forms reports: {slab kernel, channel tile, steps per stage (0: not a DMA form), slabs}, floats per slab
+void mfma_wgrad_form(const float *dy, int ldy, int N, int Cin, int Cout, int L, int K, int pad, int form[4], size_t *slab_floats) {
+    const WgPlan p = wgrad_plan_for(dy, ldy, N, Cin, Cout, L + 2 * pad - K + 1, K);
+    form[0] = p.form == WG_FFA ? ECG_WGRAD_SLABS_FAST_FIR : p.form == WG_DMA ? ECG_WGRAD_SLABS_DMA : ECG_WGRAD_SLABS_REGISTER;
+    form[1] = p.m_t; form[2] = p.form == WG_REG ? 0 : p.tt; form[3] = p.splits;
+    *slab_floats = p.slab_floats;
+}
+
 // launches the slab kernel and describes the reduce that has to follow it
 int mfma_wgrad_slabs(const float *dy, int ldy, const float *x, float *dw, float *db, float *ws, int N,
                      int Cin, int Cout, int L, int K, int pad, hipStream_t st, WgradReduce *red) {
     const int Lo = L + 2 * pad - K + 1;
-    const bool dma = wgrad_dma_rows(ldy, Lo, 64) && (reinterpret_cast<uintptr_t>(dy) & 15) == 0;
-    const WgPlan p = wgrad_plan(N, Cin, Cout, Lo, K, dma, wgrad_dma_rows(ldy, Lo, 128));
+    const WgPlan p = wgrad_plan_for(dy, ldy, N, Cin, Cout, Lo, K);
     dim3 grid((unsigned)(p.tiles * p.splits)), block(256);
 #define ECG_WG(KERNEL) \
     hipLaunchKernelGGL(KERNEL, grid, block, 0, st, dy, x, ws, N, Cin, Cout, L, Lo, ldy, pad, p.splits)

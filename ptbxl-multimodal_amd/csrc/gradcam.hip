@@ -201,7 +201,7 @@ __global__ __launch_bounds__(kThreads) void gradcam_kernel(
             sub = mn;
             div = __fadd_rn(__fsub_rn(mx, mn), 1e-8f);
         }
-        const bool vec = (S & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+        const bool vec = rows_vec4(out, nullptr, S);
         for (int j4 = tid * 4; j4 < S; j4 += kThreads * 4) {
             float v[4];
 #pragma unroll

@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256) void wfdb16_zscore_fused_kernel(
         stats[2 * ((size_t)b * leads + l0 + tid) + 1] = sd;
     }
     __syncthreads();
-    const bool vec = ((T & 3) == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
+    const bool vec = rows_vec4(out, nullptr, T);        // (the source rows are in LDS, 16-byte aligned by Tpad)
     for (int l = 0; l < nl; ++l) {
         const float mean = st[2 * l], sd = st[2 * l + 1];
         const float *row = phys + (size_t)l * Tpad;
@@ -293,7 +293,7 @@ __global__ __launch_bounds__(64) void zscore_stats_kernel(const float *__restric
     if (lane >= LANES || row >= rows) return;
     const float *r = x + (size_t)row * T;
     // float4 walk needs 16-byte aligned rows: T % 4 == 0 and an aligned base
-    const bool vec = ((T & 3) == 0) && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
+    const bool vec = rows_vec4(x, nullptr, T);
     float mean, sd;
     if (vec) {
         row_stats_vec(r, T, mean, sd);
@@ -372,6 +372,12 @@ __global__ __launch_bounds__(256) void windows_overlap_mean_kernel(const float *
 
 using namespace ecg;
 
+// The float4 / scalar decision of the row walks (rows_vec4, common.h) for these addresses: ecg_zscore_rows' statistics pass
+// asks it of (x, 0), its apply pass of (x, out), the fused int16 kernel of (out, 0), Grad-CAM's store of (cam row, 0) with n = S.
+ECG_API int ecg_rows_vec4(uintptr_t a, uintptr_t b, int n) {
+    return n > 0 && rows_vec4(reinterpret_cast<const void *>(a), reinterpret_cast<const void *>(b), n) ? 1 : 0;
+}
+
 ECG_API int ecg_zscore_rows(const float *x, float *out, float *stats, int rows, int T,
                             ecg_stream_t stream) {
     ECG_REQUIRE(x && out && stats, "zscore_rows: null pointer");
@@ -384,7 +390,7 @@ ECG_API int ecg_zscore_rows(const float *x, float *out, float *stats, int rows, 
         hipLaunchKernelGGL((zscore_stats_kernel<16>), dim3(cdiv(rows, 16)), dim3(64), 0, st, x, stats, rows, T);
     int rc = check_launch("zscore_stats_kernel");
     if (rc) return rc;
-    const bool vec = (T % 4 == 0) && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) % 16 == 0);
+    const bool vec = rows_vec4(x, out, T);
     const int T4 = vec ? T / 4 : 0;
     hipLaunchKernelGGL(zscore_apply_kernel, dim3(cdiv(vec ? T4 : T, 256), rows), dim3(256), 0, st, x, stats,
                        out, T, T4);

@@ -39,6 +39,9 @@ SIGNATURES = {
     "ecg_conv1d_bwd_data_ld": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "ecg_conv1d_bwd_weight_bias_ld": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "ecg_conv1d_bwd_weight_data_ld": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "ecg_conv1d_bwd_weight_forms": (_i, [_sz, _i, _sz, _sz, _sz] + [_i] * 6 + [_vp]),
+    "ecg_bn_relu_pool_pair_forms": (_i, [_sz, _sz, _i, _i, _vp]),
+    "ecg_rows_vec4": (_i, [_sz, _sz, _i]),
     "ecg_conv1d_bf16_supported": (_i, [_i, _i, _i, _i]),
     "ecg_conv1d_bf16_packed_elems": (_sz, [_i, _i, _i]),
     "ecg_conv1d_pack_weights_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
