@@ -23,7 +23,9 @@
  *     backward on torch's autograd engine thread.
  *   - Conv1d support envelope: stride 1, dilation 1, groups 1, 1 <= K <= 31,
  *     0 <= pad < K (the reference uses K=15, pad=7 only: src/models/ecg_cnn.py:13).
- *   - Alignment.  The bf16, recording, beats, template and metrics entry points state theirs where they are declared.
+ *   - Alignment.  The recording, beats, template and metrics entry points state theirs where they are declared; the bf16
+ *     entry points in the table "bf16 operand contract" in front of them (base alignment, row stride and the rule for
+ *     the pad [L, ld) of every row; DESIGN.md section 14 has the same table with the source lines).
  *     For the fp32 entry points (Conv1d, BatchNorm / ReLU / MaxPool, Grad-CAM, tail, fused tail, the fp32 input step) the
  *     rule is: a float tensor needs the 4-byte alignment of its element and nothing more — x, y, dy, dx, dp, p, g, weights
  *     in state_dict layout, bias, gamma, beta, mean, invstd, running statistics, every gradient destination (dw, db,
@@ -216,7 +218,48 @@ int ecg_conv1d_bwd_weight_bias(const float *dy, const float *x, float *dw, float
  * (tap-flipped), ecg_conv1d_bf16_packed_elems(C_reduce, C_result, K) 2-byte elements each.
  * K must be 15; forward needs C_in % 4 == 0 and C_out % 32 == 0, the input-grad the same with the roles swapped, the weight
  * gradient K == 15, pad == 7, C_out % 32 == 0.  ecg_conv1d_bf16_supported returns a bit mask: 1 = forward, 2 = input-grad,
- * 4 = weight-grad.  Same reference call sites as the fp32 entry points: src/models/ecg_cnn.py:13-16 and their autograd. */
+ * 4 = weight-grad.  Same reference call sites as the fp32 entry points: src/models/ecg_cnn.py:13-16 and their autograd.
+ *
+ * bf16 operand contract.  Rows are [N][C][ld]; the PAD of a row is [L, ld).  Pad rules: ZERO = the caller / producer provides
+ * zeros and the kernel relies on them; FREE = may hold any bits, NaN included, and no bit of any output depends on them;
+ * ZEROED = this call writes +0 there; UNTOUCHED = this call writes nothing there.  "refused" = ECG_EINVAL before any launch.
+ * The conv families are those ecg_conv1d_bf16_conv_forms reports.  fp32 vectors not listed need 4 bytes; stat_partials and
+ * num_batches_tracked 8 (refused otherwise).
+ *   entry point / operand                   base                          stride                  pad
+ *   ecg_conv1d_fwd_bf16_yh
+ *     x bf16                                4, refused                    even, >= L              ZERO
+ *     x fp32                                round 2: 4; ring: 8, refused  = L                     -
+ *     wb_fwd                                16, refused (both families)   -                       -
+ *     y                                     round 2: 4; ring: 16, refused even, >= Lo (ring: % 8) round 2 UNTOUCHED; ring ZEROED
+ *                                                                                                 as far as its tiles reach
+ *   ecg_conv1d_bwd_data_bf16hh
+ *     dy_bf16                               4, refused                    even, >= Lo             ZERO
+ *     wb_bwd                                16, refused (both families)   -                       -
+ *     dx_bf16                               as y above                    even, >= L              as y above: FREE for readers
+ *   ecg_conv1d_bwd_weight_bias_bf16_ncl
+ *     dy_bf16                               16, refused                   .._tk_dy_stride(Lo)     ZERO (to the % 128 stride)
+ *     x bf16 / fp32                         16, refused                   % 8 / % 4 (L % 8 == 0)  ZERO / not read
+ *     dw, db, ws                            4                             -                       dw, db written whole
+ *   ecg_bn_stats_relu_pool_fwd_h
+ *     y_bf16                                16, refused                   % 8, >= L               FREE
+ *     p_bf16                                16, refused                   % 8, >= L/2             ZEROED
+ *   ecg_bn_stats_relu_pool_gap_fwd_yh
+ *     y_bf16                                4, refused                    even, >= L              FREE
+ *   ecg_bn_relu_pool_bwd_h
+ *     y_bf16                                16, refused                   % 8, >= L               FREE
+ *     dp, dp_kind 0 (bf16 rows)             8, refused                    % 4, >= ceil4(L/2)      FREE
+ *     dp, dp_kind 1 (fp32 [N][C]) / 2 (rows) 4                            - / >= L/2              - / FREE
+ *     dy_bf16                               16, refused                   % 8, >= L               ZEROED
+ *   ecg_conv1d_bn_relu_pool[_gap]_eval_fwd_bf16
+ *     x bf16 / fp32                         4 / 8, refused                even, >= L / = L, even  ZERO / -
+ *     wb_fwd                                16, refused                   -                       -
+ *     p bf16                                16, refused                   % 8, >= Lo/2            ZEROED
+ *   ecg_conv1d_pack_weights_bf16, the bf16 half of ecg_pack_weights_grouped_mixed
+ *     w                                     4                             -                       -
+ *     wb_fwd, wb_bwd                        2 to pack; READERS refuse < 16 -                      written whole (zeros past
+ *                                                                                                 the channel count)
+ * So y[.., Lo:ldy) and dp[.., L/2:ldp) are FREE for every reader (their producers differ by family), x[.., L:ldx) and
+ * dY[.., Lo:ldy) are ZERO for every reader and ZEROED by the pass that produces them. */
 int ecg_conv1d_bf16_supported(int C_in, int C_out, int K, int pad);
 size_t ecg_conv1d_bf16_packed_elems(int C_reduce, int C_result, int K);
 int ecg_conv1d_pack_weights_bf16(const float *w, void *wb_fwd, void *wb_bwd, int C_out, int C_in,
@@ -238,6 +281,23 @@ int ecg_conv1d_fwd_bf16_yh_stat_partials(int N, int C_in, int C_out, int L, int 
  * C_res = C_out, pad; ecg_conv1d_bwd_data_bf16hh: C_red = C_out, C_res = C_in, pad = K-1-pad): the ring kernel's time
  * steps per workgroup tile (640 / 1280), or 0 = the round-2 kernel of conv1d_mfma_bf16.hip.  Tests and profiles. */
 int ecg_conv1d_bf16_ring_tile(int N, int C_red, int C_res, int L_out, int K, int pad, int ld_in, int ld_out);
+/* The form a bf16 conv takes — pure host queries answered by the functions the launch itself decides with (no device, no
+ * pointers: the bf16 forms are chosen by shape and row stride alone).  Tests use them to know which form ran.
+ * ecg_conv1d_bf16_conv_forms: ecg_conv1d_fwd_bf16_yh (C_red = C_in, C_res = C_out, L_out = Lo, pad, x_bf16, ld_in = ldx
+ * (ignored for an fp32 x: give L), ld_out = ldy, stats = 1) or ecg_conv1d_bwd_data_bf16hh (C_red = C_out, C_res = C_in,
+ * L_out = L, pad = K-1-pad, x_bf16 = 1, ld_in = ldy, ld_out = ldx, stats = 0):
+ *   [0] family ECG_BF16_CONV_ROUND2 (csrc/conv1d_mfma_bf16.hip) / ECG_BF16_CONV_RING (csrc/conv1d_bf16_ring.hip)
+ *   [1] channel tile, [2] time tile: one of ECG_BF16_ROUND2_TILES / ECG_BF16_RING_TILES
+ *   [3] resident 16-channel weight chunks: round 2: 2 (both LDS images hold the whole slice: statistics forms with
+ *       C_red <= 32) or 0 (streamed); ring: 1 / 2 / 4 resident, 0 = streamed through the ring
+ *   [4] workgroups per channel tile = the statistics partials per channel (ecg_conv1d_fwd_bf16_yh_stat_partials)
+ *   [5] whether statistics are taken (= stats). */
+enum { ECG_BF16_CONV_ROUND2 = 0, ECG_BF16_CONV_RING = 1 };
+/* every (channel tile, time tile[, resident chunks]) the plans can return */
+#define ECG_BF16_ROUND2_TILES {{32, 256}, {64, 128}, {64, 256}, {128, 256}}
+#define ECG_BF16_RING_TILES {{128, 640, 0}, {64, 1280, 2}, {64, 1280, 0}, {32, 1280, 4}, {32, 512, 1}}
+int ecg_conv1d_bf16_conv_forms(int N, int C_red, int C_res, int L_out, int K, int pad, int x_bf16, int ld_in, int ld_out,
+                               int stats, int form[6]);
 /* The BatchNorm passes on bf16 [N][C][ld] tensors (csrc/bn_relu_pool_h.hip; 16 bytes per lane in and out):
  *   ecg_bn_stats_relu_pool_fwd_h: statistics combine + BN + ReLU + MaxPool(2): y_bf16 [N][C][ldy] -> p_bf16 [N][C][ldp], rows
  *     zero-filled from L/2 to ldp (ldy, ldp multiples of 8); mean / invstd are outputs, running statistics and the counter
@@ -264,6 +324,12 @@ int ecg_bn_relu_pool_bwd_h(const void *y_bf16, int ldyy, const void *dp, int dp_
  * block's ecg_bn_relu_pool_bwd_h reads. */
 int ecg_conv1d_bwd_data_bf16hh(const void *dy_bf16, int ldy, const void *wb_bwd, void *dx_bf16, int ldx, int N,
                                int C_in, int C_out, int L, int K, int pad, ecg_stream_t stream);
+/* The forms of the bf16 row passes (pure host query, the launches' own plans): chunks in flight per thread U (one of
+ * ECG_BN_H_U_MIN .. ECG_BN_H_U_MAX) and workgroups per channel of each launch, for ecg_bn_stats_relu_pool_fwd_h with this ldp
+ * and ecg_bn_relu_pool_bwd_h with this dY stride ldy: [0] forward U, [1] forward splits, [2] backward reduce U, [3] its
+ * splits, [4] backward dY-pass U, [5] its splits, [6] splits of ecg_bn_stats_relu_pool_gap_fwd_yh (no U: a wave per row). */
+enum { ECG_BN_H_U_MIN = 3, ECG_BN_H_U_MAX = 6 };
+int ecg_bn_relu_pool_h_forms(int N, int C, int L, int ldp, int ldy, int form[7]);
 /* Weight + bias gradient on the bf16 tensors the other two convs read — TIME on the MFMA's K axis (round 4,
  * csrc/conv1d_wgrad_bf16_tk.hip): dy_bf16 [N][C_out][ldy] with ldy = ecg_conv1d_bf16_tk_dy_stride(Lo) (rows zero-filled to a
  * multiple of 128), x either bf16 [N][C_in][ldx] (x_is_bf16 != 0: ldx % 8 == 0, rows zero-filled past L — the previous
@@ -274,6 +340,11 @@ int ecg_conv1d_bwd_data_bf16hh(const void *dy_bf16, int ldy, const void *wb_bwd,
  * reference call site as ecg_conv1d_bwd_weight_bias. */
 int ecg_conv1d_bf16_tk_supported(int C_in, int C_out, int K, int pad);
 int ecg_conv1d_bf16_tk_min_len(void);
+/* The form ecg_conv1d_bwd_weight_bias_bf16_ncl takes (pure host query, the launch's own plan): [0] output channels per tile
+ * m_t, [1] columns (input channel x tap, 16 per channel) per tile r_t: one of ECG_BF16_TK_TILES, [2] 128-step stages per row,
+ * [3] splits (slabs written to ws), [4] 1 = fp32 x (rounded while staged), 0 = bf16 x. */
+#define ECG_BF16_TK_TILES {{128, 512}, {64, 512}, {32, 192}}
+int ecg_conv1d_bwd_weight_bf16_ncl_forms(int N, int C_in, int C_out, int L, int K, int pad, int x_is_bf16, int form[5]);
 int ecg_conv1d_bf16_tk_dy_stride(int Lo);
 size_t ecg_conv1d_bwd_weight_bf16_ncl_ws_floats(int N, int C_in, int C_out, int L, int K, int pad);
 int ecg_conv1d_bwd_weight_bias_bf16_ncl(const void *dy_bf16, int ldy, const void *x, int x_is_bf16, int ldx,
@@ -415,6 +486,14 @@ int ecg_conv1d_bn_relu_pool_gap_eval_fwd(const float *x, const float *w_fwd, con
  * output sums over (chunk, tap) in a fixed order and nothing reduces across samples or workgroups: a sample's result is
  * bitwise independent of N and of its position in the batch.  Multiplies per output pair: those of the bf16 forward. */
 int ecg_conv1d_bn_relu_pool_eval_bf16_supported(int C_in, int C_out, int L, int K, int pad, int gap);
+/* The form an eval block takes (pure host query, the launch's own plan; ECG_EINVAL where the geometry is not covered):
+ * [0] channel tile, [1] time tile, [2] resident weight chunks (0 = ring): one of ECG_BF16_EVAL_CANDIDATES, [3] workgroups per
+ * channel tile, [4] epilogue ECG_BF16_EVAL_P_BF16 / _P_FP32 / _GAP. */
+enum { ECG_BF16_EVAL_P_BF16 = 1, ECG_BF16_EVAL_P_FP32 = 2, ECG_BF16_EVAL_GAP = 3 };
+#define ECG_BF16_EVAL_CANDIDATES \
+    {{128, 640, 0}, {128, 256, 0}, {128, 128, 0}, {64, 1280, 2}, {64, 512, 2}, {64, 1280, 0}, {32, 1280, 4}, {32, 512, 1}}
+int ecg_conv1d_bn_relu_pool_eval_bf16_forms(int N, int C_in, int C_out, int L, int K, int pad, int x_bf16, int p_bf16, int gap,
+                                            int form[5]);
 int ecg_conv1d_bn_relu_pool_eval_fwd_bf16(const void *x, int x_bf16, int ldx, const void *wb_fwd, const float *bias,
                                           const float *gamma, const float *beta, const float *running_mean,
                                           const float *running_var, float eps, void *p, int p_bf16, int ldp, int N,

@@ -26,6 +26,8 @@ inline int stream_splits(int C, int units) {
 // (6 bytes per position: the number of loads in flight per thread, the per-position instruction count and the walk order
 // were all varied without effect), and twice the workgroups took 4-11 us off every backward call of 12x5000 (config-5 step
 // 1.449 -> 1.415 ms); 4096 adds nothing.
+// splits per channel of the global-average forward (four rows, one per wave, in flight per workgroup)
+inline int gap_fwd_splits(int C, int N) { return stream_splits(C, cdiv(N, 4)); }
 inline int stat_splits(int N, int C, bool wide = false) {
     int s = cdiv(wide ? 2048 : 1024, C);
     if (s > N) s = N;

@@ -639,7 +639,7 @@ static int pool_gap_fwd_impl(const BnFin *fin, const float *y, const float *gamm
     if (rc) return rc;
     ECG_REQUIRE(y && gamma && beta && mean && invstd && g, "bn_relu_pool_gap_fwd: null pointer");
     ECG_REQUIRE(L >= 2, "bn_relu_pool_gap_fwd: L=%d leaves an empty pooled row", L);
-    const int S2 = stream_splits(C, cdiv(N, 4));          // four rows (one per wave) in flight per workgroup
+    const int S2 = gap_fwd_splits(C, N);
     if (yh)         // bf16 activation storage (train mode: always with the statistics combine)
         hipLaunchKernelGGL((bn_relu_pool_gap_fwd_kernel<true, true>), dim3(C, S2), dim3(kBlock), 0, st, y, gamma, beta,
                            mean, invstd, g, N, C, L, L / 2, S2, *fin, ldy);

@@ -233,6 +233,20 @@ static int pick_u(long long items) {
     }
     return best;
 }
+// (U, splits) of the three launches of this file, decided ONCE: the entry points and ecg_bn_relu_pool_h_forms read these
+struct RowPlan { int u, splits; };
+static RowPlan fwd_h_plan(int N, int C, int ldp) {
+    const int S2 = stream_splits(C, N);
+    return {pick_u((long long)cdiv(N, S2) * (ldp / 8)), S2};
+}
+static RowPlan bwd_h_reduce_plan(int N, int C, int L) {
+    const int S = stat_splits(N, C, true);      // (ecg_bn_relu_pool_bwd_ws_floats sizes `ws` from the same call)
+    return {pick_u((long long)cdiv(N, S) * ((L / 2 + 3) / 4)), S};
+}
+static RowPlan bwd_h_dx_plan(int N, int C, int ldy) {
+    const int S2 = stream_splits(C, N);
+    return {pick_u((long long)cdiv(N, S2) * (ldy / 8)), S2};
+}
 #define ECG_PICK_U(U_, ...) \
     do { switch (U_) { case 3: { constexpr int UU = 3; __VA_ARGS__; } break; case 5: { constexpr int UU = 5; __VA_ARGS__; } break; \
                        case 6: { constexpr int UU = 6; __VA_ARGS__; } break; default: { constexpr int UU = 4; __VA_ARGS__; } } } while (0)
@@ -252,9 +266,9 @@ ECG_API int ecg_bn_stats_relu_pool_fwd_h(const float *stat_partials, int P, long
                 "bn_stats_relu_pool_fwd_h: row strides must be multiples of 8 (ldy=%d >= L, ldp=%d >= L/2)", ldy, ldp);
     ECG_REQUIRE(((reinterpret_cast<uintptr_t>(y_bf16) | reinterpret_cast<uintptr_t>(p_bf16)) & 15) == 0,
                 "bn_stats_relu_pool_fwd_h: tensors must be 16-byte aligned");
-    const int S2 = stream_splits(C, N);
-    const int u = pick_u((long long)cdiv(N, S2) * (ldp / 8));
-    ECG_PICK_U(u, hipLaunchKernelGGL(bn_relu_pool_fwd_h_kernel<UU>, dim3(C, S2), dim3(kBlock), 0, as_stream(stream),
+    const RowPlan fp = fwd_h_plan(N, C, ldp);
+    const int S2 = fp.splits;
+    ECG_PICK_U(fp.u, hipLaunchKernelGGL(bn_relu_pool_fwd_h_kernel<UU>, dim3(C, S2), dim3(kBlock), 0, as_stream(stream),
                                      static_cast<const u16h *>(y_bf16), gamma, beta, static_cast<u16h *>(p_bf16), N, C, L / 2,
                                      ldy, ldp, S2, f));
     return check_launch("bn_relu_pool_fwd_h_kernel");
@@ -274,22 +288,32 @@ ECG_API int ecg_bn_relu_pool_bwd_h(const void *y_bf16, int ldyy, const void *dp,
     ECG_REQUIRE(((reinterpret_cast<uintptr_t>(y_bf16) | reinterpret_cast<uintptr_t>(dy_bf16)) & 15) == 0 &&
                 (dp_kind != 0 || (reinterpret_cast<uintptr_t>(dp) & 7) == 0), "bn_relu_pool_bwd_h: tensors must be 16-byte aligned");
     hipStream_t st = as_stream(stream);
-    const int S = stat_splits(N, C, true);      // (ecg_bn_relu_pool_bwd_ws_floats sizes `ws` from the same call)
+    const RowPlan rp = bwd_h_reduce_plan(N, C, L), dp_ = bwd_h_dx_plan(N, C, ldy);
+    const int S = rp.splits;
     const float bcast = dp_kind == 1 ? 1.0f / (float)(L / 2) : 0.f;
     const u16h *y = static_cast<const u16h *>(y_bf16);
-    const int ur = pick_u((long long)cdiv(N, S) * ((L / 2 + 3) / 4));
+    const int ur = rp.u;
 #define ECG_RED(DK) ECG_PICK_U(ur, hipLaunchKernelGGL((bn_bwd_reduce_h_kernel<DK, UU>), dim3(C, S), dim3(kBlock), 0, st, y, dp, gamma, \
                                                       beta, mean, invstd, ws, N, C, L, S, bcast, ldyy, ldp))
     if (dp_kind == 1) ECG_RED(1); else if (dp_kind == 2) ECG_RED(2); else ECG_RED(0);
 #undef ECG_RED
     int rc = check_launch("bn_bwd_reduce_h_kernel");
     if (rc) return rc;
-    const int S2 = stream_splits(C, N);
-    const int ud = pick_u((long long)cdiv(N, S2) * (ldy / 8));
+    const int S2 = dp_.splits, ud = dp_.u;
 #define ECG_DX(DK) ECG_PICK_U(ud, hipLaunchKernelGGL((bn_bwd_dx_h_kernel<DK, UU>), dim3(C, S2), dim3(kBlock), 0, st, y, dp, gamma, beta, \
                                                      mean, invstd, ws, S, (double)N * L, dgamma, dbeta, static_cast<u16h *>(dy_bf16), \
                                                      ldy, N, C, L, S2, bcast, train, ldyy, ldp))
     if (dp_kind == 1) ECG_DX(1); else if (dp_kind == 2) ECG_DX(2); else ECG_DX(0);
 #undef ECG_DX
     return check_launch("bn_bwd_dx_h_kernel");
+}
+
+// The forms the row passes take (include/ecg_hip.h): answered by the plan functions the launches above decide with.
+ECG_API int ecg_bn_relu_pool_h_forms(int N, int C, int L, int ldp, int ldy, int form[7]) {
+    ECG_REQUIRE(form && N > 0 && C > 0 && L >= 2 && ldp >= 0 && ldp % 8 == 0 && ldy >= L && ldy % 8 == 0,
+                "bn_relu_pool_h_forms: bad argument");
+    const RowPlan f = fwd_h_plan(N, C, ldp), r = bwd_h_reduce_plan(N, C, L), d = bwd_h_dx_plan(N, C, ldy);
+    form[0] = f.u; form[1] = f.splits; form[2] = r.u; form[3] = r.splits; form[4] = d.u; form[5] = d.splits;
+    form[6] = gap_fwd_splits(C, N);
+    return ECG_OK;
 }

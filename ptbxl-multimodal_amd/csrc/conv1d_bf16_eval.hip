@@ -73,6 +73,8 @@ RingPlan bf16_eval_plan(int N, int Cin, int Cout, int Lo, int K, int pad, bool x
     return p;
 }
 
+int eval_epi(int gap, int p_bf16) { return gap ? kEpiGAP : (p_bf16 ? kEpiPH : kEpiPF); }
+
 int eval_fwd(const char *who, const void *x, int x_bf16, int ldx, const void *wb, const float *bias, const float *gamma,
              const float *beta, const float *mean, const float *var, float eps, void *pb, int p_bf16, int ldp, float *out,
              int gap, int N, int Cin, int Cout, int L, int K, int pad, hipStream_t st) {
@@ -96,7 +98,7 @@ int eval_fwd(const char *who, const void *x, int x_bf16, int ldx, const void *wb
                     "%s: a bf16 p needs a row stride >= Lo/2 that is a multiple of 8 and a 16-byte aligned base", who);
     else
         ECG_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, "%s: the output must be 4-byte aligned", who);
-    const int epi = gap ? kEpiGAP : (p_bf16 ? kEpiPH : kEpiPF);
+    const int epi = eval_epi(gap, p_bf16);
     return bf16_eval_launch(rp, epi, x, x_bf16 ? ldx : L, wb, gamma, beta, mean, var, eps, bias, p_bf16 ? pb : nullptr,
                             p_bf16 ? ldp : 0, p_bf16 ? nullptr : out, N, Cin, Cout, L, Lo, pad, st);
 }
@@ -111,6 +113,16 @@ ECG_API int ecg_conv1d_bn_relu_pool_eval_bf16_supported(int C_in, int C_out, int
     if (L <= 0 || Lo < 2) return 0;
     return (bf16_eval_plan(1, C_in, C_out, Lo, K, pad, false, gap != 0).ok ? 1 : 0) |
            (L % 2 == 0 && bf16_eval_plan(1, C_in, C_out, Lo, K, pad, true, gap != 0).ok ? 2 : 0);
+}
+
+// The form an eval block takes (include/ecg_hip.h): bf16_eval_plan and eval_epi, as eval_fwd launches them
+ECG_API int ecg_conv1d_bn_relu_pool_eval_bf16_forms(int N, int C_in, int C_out, int L, int K, int pad, int x_bf16, int p_bf16,
+                                                    int gap, int form[5]) {
+    ECG_REQUIRE(form && N > 0 && L > 0, "conv1d_bn_relu_pool_eval_bf16_forms: bad argument");
+    const RingPlan rp = bf16_eval_plan(N, C_in, C_out, L + 2 * pad - K + 1, K, pad, !x_bf16, gap != 0);
+    ECG_REQUIRE(rp.ok && (x_bf16 || L % 2 == 0), "conv1d_bn_relu_pool_eval_bf16_forms: geometry not covered");
+    form[0] = rp.co_t; form[1] = rp.t_t; form[2] = rp.res_ch; form[3] = rp.G; form[4] = eval_epi(gap, p_bf16);
+    return ECG_OK;
 }
 
 ECG_API int ecg_conv1d_bn_relu_pool_eval_fwd_bf16(const void *x, int x_bf16, int ldx, const void *wb_fwd, const float *bias,

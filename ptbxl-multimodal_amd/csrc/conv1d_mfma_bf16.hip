@@ -446,8 +446,11 @@ size_t bf16_packed_elems(int Cred, int Cout, int K) {       // reduction channel
     return (size_t)((Cred + kCB - 1) / kCB) * K * Cout * kCB;
 }
 
+// WRES (the whole weight slice resident): the statistics forms of layers with at most two 16-channel chunks
+static bool bf16_wres(int Cin, bool stats) { return stats && Cin <= 2 * kCB; }
+
 template <int CO_T, int T_T, int WCO, int WT>
-static void launch_bf16(const void *x, int ldx, bool xh, const u16 *wb, const float *bias, u16 *y, int ldyo,
+static void launch_bf16(const void *x, int ldx, bool xh, bool wres, const u16 *wb, const float *bias, u16 *y, int ldyo,
                         float *partials, int N, int Cin, int Cout, int L, int Lo, int pad, int G, hipStream_t st) {
     const int tiles_t = cdiv(Lo, T_T);
     dim3 grid((unsigned)((size_t)(Cout / CO_T) * G)), block(64 * WCO * WT);
@@ -459,10 +462,10 @@ static void launch_bf16(const void *x, int ldx, bool xh, const u16 *wb, const fl
     // activation / this block's bf16 dY (xh), or the fp32 network input of the first block
     if (xh) { // bf16 in, bf16 out: the train-mode forward of an inner block (statistics), or its input gradient (none)
         if (!partials) ECG_BF(false, true, false);
-        else if (Cin <= 2 * kCB) ECG_BF(true, true, true);
+        else if (wres) ECG_BF(true, true, true);
         else ECG_BF(true, true, false);
     } else { // fp32 network input (train-mode forward: always with statistics)
-        if (Cin <= 2 * kCB) ECG_BF(true, false, true);
+        if (wres) ECG_BF(true, false, true);
         else ECG_BF(true, false, false);
     }
 #undef ECG_BF
@@ -474,27 +477,42 @@ RingPlan bf16_ring_plan(int N, int Cin, int Cout, int Lo, int K, int pad, int ld
 int bf16_ring_launch(const RingPlan &p, const void *x, int ldx, const void *wb, const float *bias, void *y, int ldyo,
                      float *partials, int P_stride, int N, int Cin, int Cout, int L, int Lo, int pad, hipStream_t st);
 
+// The form of one conv of this file's two entry points, decided ONCE: the launch (bf16_fwd_any) and the host queries
+// (ecg_conv1d_bf16_conv_forms, ecg_conv1d_fwd_bf16_yh_stat_partials, ecg_conv1d_bf16_ring_tile) all read this.
+// Chosen by SHAPE and row strides only, so that a query (which sees no pointers) always agrees with the launch.
+struct Bf16Form { bool ring; int co_t, t_t, res, G; };
+static Bf16Form bf16_form(int N, int Cin, int Cout, int Lo, int K, int pad, int ldx, int ldyo, bool xh, bool stats) {
+    const RingPlan rp = bf16_ring_plan(N, Cin, Cout, Lo, K, pad, ldx, ldyo, !xh);
+    if (rp.ok) return {true, rp.co_t, rp.t_t, rp.res_ch, rp.G};
+    const Bf16Cfg c = bf16_cfg(N, Cout, Lo);
+    return {false, c.co_t, c.t_t, bf16_wres(Cin, stats) ? 2 : 0, c.G};
+}
+
 // x: fp32 [N][Cin][L] (xh false, ldx ignored) or bf16 [N][Cin][ldx] with rows zero-filled past L (xh true);
 // y: bf16 [N][Cout][ldyo]
-static int bf16_fwd_any(const void *x, int ldx, bool xh, const void *wb, const float *bias, u16 *y, int ldyo,
-                        float *partials, int N, int Cin, int Cout, int L, int K, int pad, hipStream_t st) {
+static int bf16_fwd_any(const char *who, const void *x, int ldx, bool xh, const void *wb, const float *bias, u16 *y,
+                        int ldyo, float *partials, int N, int Cin, int Cout, int L, int K, int pad, hipStream_t st) {
     const int Lo = L + 2 * pad - K + 1;
     const u16 *w = static_cast<const u16 *>(wb);
-    const RingPlan rp = bf16_ring_plan(N, Cin, Cout, Lo, K, pad, ldx, ldyo, !xh);
-    // The kernel is chosen by SHAPE only, so that ecg_conv1d_fwd_bf16_yh_stat_partials (which sees no pointers) always
-    // agrees with the launch about the number of partials; operands the chosen kernel cannot address are refused.
-    // (fp32 input: the rows are [L] floats read as aligned pairs; torch allocations and whole-sample slices satisfy both)
-    if (rp.ok) {
-        ECG_REQUIRE(((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(wb)) & 15) == 0 &&
-                        (reinterpret_cast<uintptr_t>(x) & (xh ? 3 : 7)) == 0,
-                    "conv1d bf16 (long rows): y / packed weights must be 16-byte aligned, x %d-byte aligned", xh ? 4 : 8);
+    const Bf16Form f = bf16_form(N, Cin, Cout, Lo, K, pad, ldx, ldyo, xh, partials != nullptr);
+    // Operands the chosen kernel cannot address are refused, never rerouted (the partials count would change).
+    // The packed weights are a buffer only the caller of the ABI allocates, streamed by 16-byte LDS-DMA in BOTH kernels.
+    ECG_REQUIRE((reinterpret_cast<uintptr_t>(wb) & 15) == 0, "%s: packed weights must be 16-byte aligned", who);
+    if (f.ring) {
+        // ring: y rows are stored 16 bytes at a time; an fp32 x is read as aligned pairs, a bf16 x as aligned dwords
+        ECG_REQUIRE((reinterpret_cast<uintptr_t>(y) & 15) == 0 && (reinterpret_cast<uintptr_t>(x) & (xh ? 3 : 7)) == 0,
+                    "%s (long rows): y must be 16-byte aligned, x %d-byte aligned", who, xh ? 4 : 8);
+        const RingPlan rp{true, f.co_t, f.t_t, f.res, f.G, !xh};
         return bf16_ring_launch(rp, x, ldx, wb, bias, y, ldyo, partials, rp.G, N, Cin, Cout, L, Lo, pad, st);
     }
-    const Bf16Cfg c = bf16_cfg(N, Cout, Lo);
-    if (c.co_t == 128) launch_bf16<128, 256, 2, 4>(x, ldx, xh, w, bias, y, ldyo, partials, N, Cin, Cout, L, Lo, pad, c.G, st);
-    else if (c.co_t == 64 && c.t_t == 256) launch_bf16<64, 256, 1, 4>(x, ldx, xh, w, bias, y, ldyo, partials, N, Cin, Cout, L, Lo, pad, c.G, st);
-    else if (c.co_t == 64) launch_bf16<64, 128, 2, 2>(x, ldx, xh, w, bias, y, ldyo, partials, N, Cin, Cout, L, Lo, pad, c.G, st);
-    else launch_bf16<32, 256, 1, 4>(x, ldx, xh, w, bias, y, ldyo, partials, N, Cin, Cout, L, Lo, pad, c.G, st);
+    // round 2: an fp32 x is read one float at a time, a bf16 x as aligned dwords (checked by the entry points), y one
+    // element at a time
+    ECG_REQUIRE((reinterpret_cast<uintptr_t>(x) & 3) == 0, "%s: x must be 4-byte aligned", who);
+    const bool wres = f.res != 0;
+    if (f.co_t == 128) launch_bf16<128, 256, 2, 4>(x, ldx, xh, wres, w, bias, y, ldyo, partials, N, Cin, Cout, L, Lo, pad, f.G, st);
+    else if (f.co_t == 64 && f.t_t == 256) launch_bf16<64, 256, 1, 4>(x, ldx, xh, wres, w, bias, y, ldyo, partials, N, Cin, Cout, L, Lo, pad, f.G, st);
+    else if (f.co_t == 64) launch_bf16<64, 128, 2, 2>(x, ldx, xh, wres, w, bias, y, ldyo, partials, N, Cin, Cout, L, Lo, pad, f.G, st);
+    else launch_bf16<32, 256, 1, 4>(x, ldx, xh, wres, w, bias, y, ldyo, partials, N, Cin, Cout, L, Lo, pad, f.G, st);
     return check_launch("conv1d_mfma_bf16_fwd_kernel");
 }
 
@@ -543,19 +561,26 @@ ECG_API int ecg_conv1d_pack_weights_bf16(const float *w, void *wb_fwd, void *wb_
 // types and row strides too)
 ECG_API int ecg_conv1d_fwd_bf16_yh_stat_partials(int N, int C_in, int C_out, int L, int K, int pad, int x_bf16, int ldx,
                                                  int ldy) {
-    const int Lo = L + 2 * pad - K + 1;
-    {
-        const RingPlan rp = bf16_ring_plan(N, C_in, C_out, Lo, K, pad, x_bf16 ? ldx : L, ldy, !x_bf16);
-        if (rp.ok) return rp.G;
-    }
-    return bf16_fwd_stat_partials(N, C_out, Lo);
+    return bf16_form(N, C_in, C_out, L + 2 * pad - K + 1, K, pad, x_bf16 ? ldx : L, ldy, x_bf16 != 0, true).G;
+}
+
+// The form a conv of this file takes (include/ecg_hip.h): what bf16_fwd_any launches for the same arguments.
+ECG_API int ecg_conv1d_bf16_conv_forms(int N, int C_red, int C_res, int L_out, int K, int pad, int x_bf16, int ld_in,
+                                       int ld_out, int stats, int form[6]) {
+    ECG_REQUIRE(form && N > 0 && C_red > 0 && C_res > 0 && L_out > 0 && K == kKB && pad >= 0 && pad < K,
+                "conv1d_bf16_conv_forms: bad argument");
+    ECG_REQUIRE(bf16_fwd_supported(C_red, C_res, K, pad), "conv1d_bf16_conv_forms: needs C_red %% 4 == 0, C_res %% 32 == 0");
+    const Bf16Form f = bf16_form(N, C_red, C_res, L_out, K, pad, ld_in, ld_out, x_bf16 != 0, stats != 0);
+    form[0] = f.ring ? ECG_BF16_CONV_RING : ECG_BF16_CONV_ROUND2;
+    form[1] = f.co_t; form[2] = f.t_t; form[3] = f.res; form[4] = f.G; form[5] = stats != 0;
+    return ECG_OK;
 }
 
 // time steps per workgroup tile of the ring kernel when a conv with bf16 tensors on both sides (C_red reduction channels,
 // C_res result channels, L_out result positions, `pad` as the kernel sees it) takes it, 0 when the round-2 kernel runs
 ECG_API int ecg_conv1d_bf16_ring_tile(int N, int C_red, int C_res, int L_out, int K, int pad, int ld_in, int ld_out) {
-    const RingPlan rp = bf16_ring_plan(N, C_red, C_res, L_out, K, pad, ld_in, ld_out);
-    return rp.ok ? rp.t_t : 0;
+    const Bf16Form f = bf16_form(N, C_red, C_res, L_out, K, pad, ld_in, ld_out, true, false);
+    return f.ring ? f.t_t : 0;
 }
 
 // Train-mode forward with bf16 ACTIVATION STORAGE: y is written as bf16 [N][C_out][ldy] (ldy >= Lo, even), the
@@ -575,7 +600,7 @@ ECG_API int ecg_conv1d_fwd_bf16_yh(const void *x, int x_bf16, int ldx, const voi
                 "conv1d_fwd_bf16_yh: needs an even row stride >= Lo and a 4-byte aligned y");
     ECG_REQUIRE(!x_bf16 || (ldx >= L && ldx % 2 == 0 && (pad & 1) == 1 && (reinterpret_cast<uintptr_t>(x) & 3) == 0),
                 "conv1d_fwd_bf16_yh: a bf16 x needs an even row stride >= L, odd pad and a 4-byte aligned base");
-    return bf16_fwd_any(x, x_bf16 ? ldx : L, x_bf16 != 0, wb_fwd, bias, static_cast<u16 *>(y_bf16), ldy,
+    return bf16_fwd_any("conv1d_fwd_bf16_yh", x, x_bf16 ? ldx : L, x_bf16 != 0, wb_fwd, bias, static_cast<u16 *>(y_bf16), ldy,
                         stat_partials, N, C_in, C_out, L, K, pad, as_stream(stream));
 }
 
@@ -593,7 +618,7 @@ ECG_API int ecg_conv1d_bwd_data_bf16hh(const void *dy_bf16, int ldy, const void 
                 "conv1d_bwd_data_bf16hh: needs an even row stride >= Lo, odd K-1-pad and a 4-byte aligned dY");
     ECG_REQUIRE(ldx >= L && ldx % 2 == 0 && (reinterpret_cast<uintptr_t>(dx_bf16) & 3) == 0,
                 "conv1d_bwd_data_bf16hh: needs an even dx row stride >= L and a 4-byte aligned dx");
-    return bf16_fwd_any(dy_bf16, ldy, true, wb_bwd, nullptr, static_cast<u16 *>(dx_bf16), ldx, nullptr, N, C_out,
+    return bf16_fwd_any("conv1d_bwd_data_bf16hh", dy_bf16, ldy, true, wb_bwd, nullptr, static_cast<u16 *>(dx_bf16), ldx, nullptr, N, C_out,
                         C_in, Lo, K, padb, as_stream(stream));
 }
 

@@ -478,6 +478,16 @@ ECG_API int ecg_conv1d_bf16_tk_supported(int C_in, int C_out, int K, int pad) {
     return wgrad_bf16_tk_supported(C_in, C_out, K, pad) ? 1 : 0;
 }
 
+// The form the time-on-K weight gradient takes (include/ecg_hip.h): tk_plan, as wgrad_bf16_tk launches it
+ECG_API int ecg_conv1d_bwd_weight_bf16_ncl_forms(int N, int C_in, int C_out, int L, int K, int pad, int x_is_bf16,
+                                                 int form[5]) {
+    ECG_REQUIRE(form && N > 0 && C_in > 0 && C_out > 0 && L + 2 * pad - K + 1 > 0 && wgrad_bf16_tk_supported(C_in, C_out, K, pad),
+                "conv1d_bwd_weight_bf16_ncl_forms: bad argument");
+    const TkPlan p = tk_plan(N, C_in, C_out, L + 2 * pad - K + 1);
+    form[0] = p.m_t; form[1] = p.r_t; form[2] = p.ntt; form[3] = p.splits; form[4] = x_is_bf16 ? 0 : 1;
+    return ECG_OK;
+}
+
 ECG_API int ecg_conv1d_bf16_tk_min_len(void) { return TK_MIN_L; }
 
 ECG_API int ecg_conv1d_bf16_tk_dy_stride(int Lo) { return Lo > 0 ? wgrad_bf16_tk_dy_stride(Lo) : 0; }

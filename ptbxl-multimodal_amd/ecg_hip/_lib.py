@@ -48,6 +48,10 @@ SIGNATURES = {
     "ecg_conv1d_fwd_bf16_yh": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp] + [_i] * 6 + [_vp]),
     "ecg_conv1d_fwd_bf16_yh_stat_partials": (_i, [_i] * 9),
     "ecg_conv1d_bf16_ring_tile": (_i, [_i] * 8),
+    "ecg_conv1d_bf16_conv_forms": (_i, [_i] * 10 + [_vp]),
+    "ecg_conv1d_bwd_weight_bf16_ncl_forms": (_i, [_i] * 7 + [_vp]),
+    "ecg_bn_relu_pool_h_forms": (_i, [_i] * 5 + [_vp]),
+    "ecg_conv1d_bn_relu_pool_eval_bf16_forms": (_i, [_i] * 9 + [_vp]),
     "ecg_bn_stats_relu_pool_fwd_h": (_i, [_vp, _i, _ll, _vp, _vp, _vp, _f, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "ecg_bn_relu_pool_bwd_h": (_i, [_vp, _i, _vp, _i, _i] + [_vp] * 5 + [_i] + [_vp] * 3 + [_i] * 4 + [_vp]),
     "ecg_conv1d_bwd_data_bf16hh": (_i, [_vp, _i, _vp, _vp, _i] + [_i] * 6 + [_vp]),
