@@ -1,47 +1,11 @@
 // conv1d_api.hip — C-ABI entry points for Conv1d and the shape dispatch between the
-// MFMA implicit-GEMM kernels (conv1d_mfma.hip) and the direct VALU kernels (conv1d_direct.hip).
-#include "common.h"
-#include "wgrad_reduce.h"
+// MFMA implicit-GEMM kernels (conv1d_mfma.hip) and the direct VALU kernels (conv1d_direct.hip); what it calls in those
+// files is declared in conv1d_internal.h.
+#include "conv1d_internal.h"
 
 namespace ecg {
-// conv1d_direct.hip
-int direct_fwd_stat_partials(int N, int Lo);
-int direct_fwd(const float *x, const float *wp, const float *bias, float *y, float *partials,
-               int N, int Cin, int Cout, int L, int K, int pad, hipStream_t st);
-size_t direct_wgrad_ws_floats(int N, int Cin, int Cout, int K);
-int direct_wgrad(const float *dy, const float *x, float *dw, float *db, float *ws, int N, int Cin,
-                 int Cout, int L, int K, int pad, hipStream_t st);
-int direct_wgrad_slabs(const float *dy, const float *x, float *dw, float *db, float *ws, int N, int Cin,
-                       int Cout, int L, int K, int pad, hipStream_t st, WgradReduce *red);
-int pack_weights(const float *w, float *w_fwd, float *w_bwd, int Co, int Ci, int K,
-                 hipStream_t st);
-int pack_weights_grouped(const float *const *w, float *const *w_fwd, float *const *w_bwd, void *const *wb_fwd,
-                         void *const *wb_bwd, const int *Co, const int *Ci, const int *K, int count, hipStream_t st);
-// conv1d_mfma.hip
-bool mfma_fwd_supported(int Cin, int Cout, int K, int pad);
-int mfma_fwd_stat_partials(int N, int Cin, int Cout, int Lo);
-int mfma_fwd(const float *x, int ldx, const float *wp, const float *bias, float *y, float *partials,
-             int N, int Cin, int Cout, int L, int K, int pad, hipStream_t st);
-int mfma_fwd_eval_pool(const float *x, const float *wp, const float *bias, const float *gamma,
-                       const float *beta, const float *mean, const float *var, float eps, float *p,
-                       int N, int Cin, int Cout, int L, int K, int pad, hipStream_t st, int gap);
-bool mfma_fwd_eval_gap_supported(int Cin, int Cout, int L, int K, int pad);
-bool mfma_wgrad_supported(int Cin, int Cout, int K);
-size_t mfma_wgrad_ws_floats(int N, int Cin, int Cout, int L, int K, int pad);
-int mfma_wgrad_dma_stride(int Lo, int tt);
-int mfma_multiplies_per_pair(int op, int Cin, int Cout, int K, int pad);
-int mfma_wgrad(const float *dy, int ldy, const float *x, float *dw, float *db, float *ws, int N,
-               int Cin, int Cout, int L, int K, int pad, hipStream_t st);
-int mfma_wgrad_slabs(const float *dy, int ldy, const float *x, float *dw, float *db, float *ws, int N,
-                     int Cin, int Cout, int L, int K, int pad, hipStream_t st, WgradReduce *red);
-int mfma_wgrad_reduce(const WgradReduce &red, hipStream_t st);
-void mfma_wgrad_form(const float *dy, int ldy, int N, int Cin, int Cout, int L, int K, int pad, int form[4], size_t *slab_floats);
-int direct_wgrad_splits(int N, int Cin, int Cout, int K);
-WgradReduce wgrad_reduce_describe(const float *ws, float *dw, float *db, size_t wslab, int Cin, int Cout, int S);
 static_assert(WGR_GROUPED == ECG_WGRAD_REDUCE_GROUPED && WGR_FLOAT4 == ECG_WGRAD_REDUCE_FLOAT4 && WGR_FFA == ECG_WGRAD_REDUCE_FAST_FIR,
               "the reduce forms are reported as they are numbered");
-int mfma_fwd_rider(const float *x, int ldx, const float *wp, float *y, int N, int Cin, int Cout, int L, int K, int pad,
-                   WgradReduce red, hipStream_t st);
 
 static int check_conv_shape(int N, int Cin, int Cout, int L, int K, int pad) {
     ECG_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && L > 0, "conv1d: N=%d C_in=%d C_out=%d L=%d must be > 0",

@@ -11,18 +11,11 @@
 // samples or workgroups, so a sample's output does not depend on N or on its place in the batch.
 // Replaces the eval forward of ConvBlock (reference src/models/ecg_cnn.py:12-17) under inference_precision("bf16").
 // Parity: tests/test_gpu_bf16_inference.py.
-#include "common.h"
+#include "conv1d_internal.h"
 
 namespace ecg {
 
-struct RingPlan { bool ok; int co_t, t_t, res_ch, G; bool xf32; };
-int bf16_eval_launch(const RingPlan &p, int epi, const void *x, int ldx, const void *wb, const float *gamma,
-                     const float *beta, const float *mean, const float *var, float eps, const float *bias, void *p_bf16,
-                     int ldp, float *out, int N, int Cin, int Cout, int L, int Lo, int pad, hipStream_t st);
-
 namespace {
-constexpr int kEpiPH = 1, kEpiPF = 2, kEpiGAP = 3;     // = ring::EPI_PH / EPI_PF / EPI_GAP
-
 // Configurations conv1d_bf16_ring.hip instantiates with an eval epilogue (bf16_eval_launch):
 //   co_t  t_t   res_ch   per_cu   needs
 //   32    512   1 (x fp32)  2     the fp32 network input, C_in <= 16
@@ -64,16 +57,12 @@ RingPlan bf16_eval_plan(int N, int Cin, int Cout, int Lo, int K, int pad, bool x
     p.co_t = cand[best].co_t; p.t_t = cand[best].t_t; p.res_ch = cand[best].res_ch;
     const int CT = Cout / p.co_t;
     const long long ntiles = (long long)N * cdiv(Lo, p.t_t);
-    long long G = 256LL * cand[best].per_cu / CT;
-    if (G < 1) G = 1;
-    if (G > ntiles) G = ntiles;
-    const long long per = (ntiles + G - 1) / G;
-    p.G = (int)((ntiles + per - 1) / per);
+    p.G = persistent_groups(256LL * cand[best].per_cu / CT, ntiles);
     p.ok = true;
     return p;
 }
 
-int eval_epi(int gap, int p_bf16) { return gap ? kEpiGAP : (p_bf16 ? kEpiPH : kEpiPF); }
+ring::Epilogue eval_epi(int gap, int p_bf16) { return gap ? ring::EPI_GAP : (p_bf16 ? ring::EPI_PH : ring::EPI_PF); }
 
 int eval_fwd(const char *who, const void *x, int x_bf16, int ldx, const void *wb, const float *bias, const float *gamma,
              const float *beta, const float *mean, const float *var, float eps, void *pb, int p_bf16, int ldp, float *out,
@@ -98,9 +87,8 @@ int eval_fwd(const char *who, const void *x, int x_bf16, int ldx, const void *wb
                     "%s: a bf16 p needs a row stride >= Lo/2 that is a multiple of 8 and a 16-byte aligned base", who);
     else
         ECG_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3) == 0, "%s: the output must be 4-byte aligned", who);
-    const int epi = eval_epi(gap, p_bf16);
-    return bf16_eval_launch(rp, epi, x, x_bf16 ? ldx : L, wb, gamma, beta, mean, var, eps, bias, p_bf16 ? pb : nullptr,
-                            p_bf16 ? ldp : 0, p_bf16 ? nullptr : out, N, Cin, Cout, L, Lo, pad, st);
+    return bf16_eval_launch(rp, eval_epi(gap, p_bf16), x, x_bf16 ? ldx : L, wb, gamma, beta, mean, var, eps, bias,
+                            p_bf16 ? pb : nullptr, p_bf16 ? ldp : 0, p_bf16 ? nullptr : out, N, Cin, Cout, L, Lo, pad, st);
 }
 }  // namespace
 

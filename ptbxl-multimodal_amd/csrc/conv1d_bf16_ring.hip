@@ -26,6 +26,7 @@
 // rows; both weight modes), test_bf16_conv_full_size_config5_*.
 // Replaces the ATen work behind ConvBlock.net[0] (reference src/models/ecg_cnn.py:13) and its input gradient.
 #include "mfma_util.h"
+#include "conv1d_internal.h"
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
@@ -47,18 +48,6 @@ constexpr int NT = 64 * NW;
 constexpr int NSLOT = 5;         // ring slots of 8 KB
 constexpr int LA = 4;            // groups in flight ahead of the one being computed
 constexpr int SLOTB = 8192;
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
-    __builtin_amdgcn_s_waitcnt(((N >> 4) << 14) | 0x0F70 | (N & 15));
-}
-__device__ __forceinline__ void wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xC07F); }
-template <int N>
-__device__ __forceinline__ void wait_lgkm() {           // lgkmcnt(N), vmcnt / expcnt left at "no wait"
-    static_assert(N >= 0 && N < 16, "lgkmcnt is a 4-bit counter");
-    __builtin_amdgcn_s_waitcnt(0xC07F | (N << 8));
-}
 
 // (The timing-only 16x16x32 what-if variant of this step — profiles/r03_mfma_shape_whatif.txt — lived here in round 3;
 // it was removed from the product source once measured: 3-7 % at best against a certain spill.)
@@ -101,12 +90,12 @@ constexpr int commit_tap(int cb, int GT) {
 // tile is 75 MFMAs per wave against an epilogue of comparable length, and two independent workgroups fill each other's
 // epilogues (in-kernel stamps with one 1280-step workgroup per CU: taps 5.4 us, epilogue 2.9 us per tile, matrix pipe
 // idle in the latter).
-// EPI: what the epilogue writes.  EPI_Y = the train-mode conv output y (bf16 [N][Cout][ldyo], + statistics with STATS);
+// EPI: what the epilogue writes (ring::Epilogue, conv1d_internal.h).  EPI_Y = the train-mode conv output y (bf16
+// [N][Cout][ldyo], + statistics with STATS);
 // the eval forms fold eval BatchNorm (scale / shift from the running statistics and the bias, computed in the prologue:
 // one lane = one channel), ReLU and MaxPool(2) into it — a pool pair is two neighbouring accumulator registers of a lane —
 // and write only the pooled row: EPI_PH bf16 [N][Cout][ldyo] zero-filled from Lo/2 to ldyo, EPI_PF fp32 [N][Cout][Lo/2]
 // (ev.out), EPI_GAP the global average of the pooled row, fp32 [N][Cout] (ev.out; a row is ONE tile: tiles_t == 1).
-enum { EPI_Y = 0, EPI_PH = 1, EPI_PF = 2, EPI_GAP = 3 };
 struct EvalArgs { const float *gamma, *beta, *mean, *var; float eps; float *out; };
 
 template <int CO_T, int WCO, int WT, int MT, bool STATS, int RES_CH, bool XF32 = false, int EPI = EPI_Y>
@@ -530,7 +519,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 4 
                     }
                     if constexpr (RES && k == 0) __builtin_amdgcn_s_barrier();   // everybody has left the previous chunk's x image
                     if constexpr (k == 13) {             // the commits of taps KC0..12 become visible before tap 14 prefetches
-                        wait_lgkm0();
+                        wait_lgkm<0>();
                         __builtin_amdgcn_s_barrier();
                     }
                     __builtin_amdgcn_sched_barrier(0);   // one tap = one scheduling region
@@ -646,8 +635,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MT == 2 ? 4 
 // ---------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------
-struct RingPlan { bool ok; int co_t, t_t, res_ch, G; bool xf32; };
-
 // Which shapes the ring kernel takes: bf16 in and out (x_bf16 / y_bf16 of the callers), K = 15, odd pad, even ldx,
 // ldy % 4 == 0, and rows long enough that 640-step tiles waste no more than the 256-step tiles of the old kernel.
 // xf32: the input is the fp32 network input (one 16-channel chunk: C_in <= 16), rounded to bf16 while it is staged.
@@ -670,11 +657,7 @@ RingPlan bf16_ring_plan(int N, int Cin, int Cout, int Lo, int K, int pad, int ld
     if (new_pad > old_pad + old_pad / 50) return p;
     const int CT = Cout / p.co_t;
     const long long ntiles = (long long)N * cdiv(Lo, p.t_t);
-    long long G = (xf32 ? 512 : 256) / CT;                // (the fp32-input variant runs two workgroups per CU)
-    if (G < 1) G = 1;
-    if (G > ntiles) G = ntiles;
-    const long long per = (ntiles + G - 1) / G;
-    p.G = (int)((ntiles + per - 1) / per);
+    p.G = persistent_groups((xf32 ? 512 : 256) / CT, ntiles);     // (the fp32-input variant runs two workgroups per CU)
     p.ok = true;
     return p;
 }
@@ -708,9 +691,10 @@ int bf16_ring_launch(const RingPlan &p, const void *x, int ldx, const void *wb, 
 // ---- eval ConvBlock (conv1d_bf16_eval.hip: plan and entry points) ------------------------------------------------------
 // The same kernel with an eval epilogue.  Configurations (CO_T, WCO, WT, MT, RES_CH) by tile length T_T = WT * MT * 32; the
 // plan picks, among those the channel counts allow, the tile that pads the row least (12x1000 rows are 125-1000 long).
-int bf16_eval_launch(const RingPlan &p, int epi, const void *x, int ldx, const void *wb, const float *gamma,
-                     const float *beta, const float *mean, const float *var, float eps, const float *bias, void *p_bf16,
-                     int ldp, float *out, int N, int Cin, int Cout, int L, int Lo, int pad, hipStream_t st) {
+int bf16_eval_launch(const RingPlan &p, ring::Epilogue epi, const void *x, int ldx, const void *wb,
+                     const float *gamma, const float *beta, const float *mean, const float *var, float eps,
+                     const float *bias, void *p_bf16, int ldp, float *out, int N, int Cin, int Cout, int L, int Lo, int pad,
+                     hipStream_t st) {
     using namespace ring;
     const int tiles_t = cdiv(Lo, p.t_t);
     dim3 grid((unsigned)((Cout / p.co_t) * p.G)), block(NT);

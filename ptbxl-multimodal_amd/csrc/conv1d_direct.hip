@@ -12,7 +12,7 @@
 // workgroup needs are contiguous and wave-uniform, so they arrive through the scalar cache
 // (s_load_dwordx8/x16) and feed v_fma_f32 as SGPR operands — one LDS read of x feeds CO_T FMAs.
 #include "bf16_util.h"
-#include "wgrad_reduce.h"
+#include "conv1d_internal.h"
 #include <cstdlib>
 
 namespace ecg {
@@ -390,8 +390,6 @@ int direct_wgrad(const float *dy, const float *x, float *dw, float *db, float *w
     if (rc) return rc;
     return wgrad_reduce_launch(red, st);
 }
-
-int pack_weights(const float *w, float *w_fwd, float *w_bwd, int Co, int Ci, int K, hipStream_t st);
 
 // All weight packs of a model in ONE launch (a Linear transpose is the K = 1 case).
 // A workgroup moves one tile of 16 output channels x up to 16 input channels x K taps through LDS: the source

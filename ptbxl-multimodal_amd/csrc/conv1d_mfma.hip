@@ -19,7 +19,7 @@
 // Replaces the ATen work behind ConvBlock.net[0] (reference src/models/ecg_cnn.py:13) and its
 // backward (src/training/loop.py:33).
 #include "mfma_util.h"
-#include "wgrad_reduce.h"
+#include "conv1d_internal.h"
 #include <cstdlib>
 #include <tuple>
 #include <type_traits>
@@ -35,21 +35,6 @@ __device__ unsigned long long *g_stamps = nullptr;
 
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
-
-// s_waitcnt lgkmcnt(n), vmcnt / expcnt left at "no wait" (n is a compile-time constant after unrolling).  hipcc's own
-// placement drains lgkmcnt(0) on every second step of the fragment double-buffering below — i.e. it waits for the LDS
-// reads just issued for the NEXT step in front of MFMAs that only need the previous ones; an explicit counted wait
-// placed before the MFMAs tells its scoreboard the operands are complete (a count larger than the reads really in
-// flight is harmless: the compiler still adds whatever wait correctness needs).
-__device__ __forceinline__ void wait_lgkm_f(int n) {
-    switch (n) {
-        case 1: __builtin_amdgcn_s_waitcnt(0xC17F); break;
-        case 2: __builtin_amdgcn_s_waitcnt(0xC27F); break;
-        case 3: __builtin_amdgcn_s_waitcnt(0xC37F); break;
-        case 4: __builtin_amdgcn_s_waitcnt(0xC47F); break;
-        default: break;
-    }
 }
 
 // =======================================================================================
@@ -284,7 +269,7 @@ __global__ __launch_bounds__(256, ECG_FFA_MINB) void conv1d_mfma_ffa_kernel(
         for (int st = 0; st < NST; ++st) {
             const int j = st / (CI_C / 2), cp = st % (CI_C / 2);
             ld(st + 1 < NST ? st + 1 : 0, wa_n, wb_n, xq_n);
-            wait_lgkm_f(3);
+            wait_lgkm<3>();
             if (st < XLOADS) {
                 if (do_next) commit_x(st, nxt);
             } else if (st < XLOADS + DPW) {
@@ -1325,10 +1310,6 @@ __global__ __launch_bounds__(64) void wgrad_ffa_reduce_kernel(const float *__res
                                                               float *__restrict__ db, int Cin, int Cout, int S) {
     wgrad_ffa_reduce_lane(slab, dw, db, Cin, Cout, S, (size_t)blockIdx.x * 64 + threadIdx.x);
 }
-
-// conv1d_direct.hip: dw[i] = sum_s slab[s][i] in fixed order — which form sums a slab set, and its standalone launch
-WgradReduce wgrad_reduce_describe(const float *ws, float *dw, float *db, size_t wslab, int Cin, int Cout, int S);
-int wgrad_reduce_launch(const WgradReduce &r, hipStream_t st);
 
 // Development knobs are COMPILE-TIME (A/B libraries: make VARIANT=x EXTRA="-DECG_WG_SLOTS=768"): the product library reads no
 // environment variable.

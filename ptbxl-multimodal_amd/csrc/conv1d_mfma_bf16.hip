@@ -2,7 +2,8 @@
 // gfx950 matrix cores (v_mfma_f32_32x32x16_bf16, fp32 accumulate), fp32 activations in HBM.
 // This is the opt-in path of BASELINE.json config 5 ("AF binary, 12x5000, bf16 mixed precision");
 // the fp32 MFMA kernels of conv1d_mfma.hip remain the default and the parity path.  The weight
-// gradient of this mode is in conv1d_wgrad_bf16.hip.
+// gradient of this mode is in conv1d_wgrad_bf16_tk.hip; long rows with bf16 on both sides take the
+// kernel of conv1d_bf16_ring.hip (bf16_ring_plan / bf16_ring_launch, declared in conv1d_internal.h).
 //
 // Same im2col-free structure as the fp32 kernel, with a 16-channel reduction block per MFMA:
 //   D[co][t] += sum_{ci in chunk of 16} W[tap][co][ci] * X[t + tap][ci]       (one MFMA per tap)
@@ -15,6 +16,7 @@
 // Replaces the ATen work behind ConvBlock.net[0] (reference src/models/ecg_cnn.py:13); the
 // reference itself has no mixed precision (`amp: true` in its YAML is a dead key).
 #include "mfma_util.h"
+#include "conv1d_internal.h"
 
 namespace ecg {
 
@@ -25,29 +27,6 @@ __device__ unsigned long long *g_stamps_b = nullptr;
 
 constexpr int kKB = 15;      // kernel size staged by this path
 constexpr int kCB = 16;      // input channels per MFMA (its K dimension)
-
-// s_waitcnt vmcnt(N) with lgkmcnt / expcnt left at "no wait"
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
-    __builtin_amdgcn_s_waitcnt(((N >> 4) << 14) | 0x0F70 | (N & 15));
-}
-
-// s_waitcnt lgkmcnt(n) with vmcnt / expcnt left at "no wait" (n is a compile-time constant after unrolling)
-__device__ __forceinline__ void wait_lgkm(int n) {
-    switch (n) {
-        case 0: __builtin_amdgcn_s_waitcnt(0xC07F); break;
-        case 1: __builtin_amdgcn_s_waitcnt(0xC17F); break;
-        case 2: __builtin_amdgcn_s_waitcnt(0xC27F); break;
-        case 3: __builtin_amdgcn_s_waitcnt(0xC37F); break;
-        case 4: __builtin_amdgcn_s_waitcnt(0xC47F); break;
-        case 5: __builtin_amdgcn_s_waitcnt(0xC57F); break;
-        case 6: __builtin_amdgcn_s_waitcnt(0xC67F); break;
-        case 7: __builtin_amdgcn_s_waitcnt(0xC77F); break;
-        case 8: __builtin_amdgcn_s_waitcnt(0xC87F); break;
-        default: break;                                   // more than the counter is worth tracking: let the compiler decide
-    }
-}
 
 // w [Co][Ci][K] fp32 -> wb_fwd [ceil(Ci/16)][K][Co][16] and wb_bwd [ceil(Co/16)][K][Ci][16]
 // (tap-flipped, roles of the channel axes swapped), zero-filled past the channel count.
@@ -334,7 +313,7 @@ __global__ __launch_bounds__(64 * WCO * WT) __attribute__((amdgpu_waves_per_eu(2
             // Left alone, hipcc waits lgkmcnt(0) on every second step and after every LDS-DMA issue — the full LDS
             // latency of the reads just issued, in front of MFMAs that do not need them.  The explicit counted wait
             // sits BEFORE the staging operation so that the compiler sees the operands complete at that point.
-            wait_lgkm(MC + MT);
+            wait_lgkm<MC + MT>();
 #pragma unroll
             for (int o = k * OPS; o < (k + 1) * OPS; ++o) {      // weight DMA pieces first (longest latency), x commits, x loads;
                 if (o < DPW) { if (!WRES) dma_w(o, wnext, nxt); }   // all UNCONDITIONAL: stages past the end restage valid data
@@ -414,7 +393,7 @@ __global__ __launch_bounds__(64 * WCO * WT) __attribute__((amdgpu_waves_per_eu(2
     ECG_STAMP_AT(g_stamps_b, 4);
 }
 
-bool bf16_fwd_supported(int Cin, int Cout, int K, int pad) {
+static bool bf16_fwd_supported(int Cin, int Cout, int K, int pad) {
     (void)pad;
     return K == kKB && Cin % 4 == 0 && Cout % 32 == 0;
 }
@@ -431,18 +410,11 @@ static Bf16Cfg bf16_cfg(int N, int Cout, int Lo) {
     else if (Cout % 64 == 0) { c = {64, wide ? 256 : 128, 0}; per_cu = 2; }
     else { c = {32, 256, 0}; per_cu = 2; }            // (VGPRs allow two 4-wave workgroups per CU)
     const int CT = Cout / c.co_t;
-    const long long ntiles = (long long)N * cdiv(Lo, c.t_t);
-    long long G = (256LL * per_cu) / CT;
-    if (G > ntiles) G = ntiles;
-    if (G < 1) G = 1;
-    const long long per = (ntiles + G - 1) / G;       // tiles of the busiest workgroup
-    c.G = (int)((ntiles + per - 1) / per);            // fewest workgroups with that maximum
+    c.G = persistent_groups((256LL * per_cu) / CT, (long long)N * cdiv(Lo, c.t_t));
     return c;
 }
 
-int bf16_fwd_stat_partials(int N, int Cout, int Lo) { return bf16_cfg(N, Cout, Lo).G; }
-
-size_t bf16_packed_elems(int Cred, int Cout, int K) {       // reduction channels padded to 16
+static size_t bf16_packed_elems(int Cred, int Cout, int K) {       // reduction channels padded to 16
     return (size_t)((Cred + kCB - 1) / kCB) * K * Cout * kCB;
 }
 
@@ -470,12 +442,6 @@ static void launch_bf16(const void *x, int ldx, bool xh, bool wres, const u16 *w
     }
 #undef ECG_BF
 }
-
-// conv1d_bf16_ring.hip: the round-3 kernel for long rows with bf16 activations on both sides
-struct RingPlan { bool ok; int co_t, t_t, res_ch, G; bool xf32; };
-RingPlan bf16_ring_plan(int N, int Cin, int Cout, int Lo, int K, int pad, int ldx, int ldyo, bool xf32 = false);
-int bf16_ring_launch(const RingPlan &p, const void *x, int ldx, const void *wb, const float *bias, void *y, int ldyo,
-                     float *partials, int P_stride, int N, int Cin, int Cout, int L, int Lo, int pad, hipStream_t st);
 
 // The form of one conv of this file's two entry points, decided ONCE: the launch (bf16_fwd_any) and the host queries
 // (ecg_conv1d_bf16_conv_forms, ecg_conv1d_fwd_bf16_yh_stat_partials, ecg_conv1d_bf16_ring_tile) all read this.
@@ -516,7 +482,7 @@ static int bf16_fwd_any(const char *who, const void *x, int ldx, bool xh, const 
     return check_launch("conv1d_mfma_bf16_fwd_kernel");
 }
 
-int bf16_pack(const float *w, void *wb_fwd, void *wb_bwd, int Co, int Ci, int K, hipStream_t st) {
+static int bf16_pack(const float *w, void *wb_fwd, void *wb_bwd, int Co, int Ci, int K, hipStream_t st) {
     const size_t n = bf16_packed_elems(Ci, Co, K), m = bf16_packed_elems(Co, Ci, K);
     const size_t total = n > m ? n : m;
     hipLaunchKernelGGL(pack_weights_bf16_kernel, dim3(cdiv((long long)total, 256)), dim3(256), 0, st, w,
@@ -533,10 +499,6 @@ static int check_bf16_shape(const char *who, int N, int Cin, int Cout, int L, in
     ECG_REQUIRE(K == kKB && pad >= 0 && pad < K && L + 2 * pad - K + 1 > 0, "%s: kernel size must be 15", who);
     return ECG_OK;
 }
-
-namespace ecg {
-bool wgrad_bf16_tk_supported(int Cin, int Cout, int K, int pad);      // conv1d_wgrad_bf16_tk.hip
-}  // namespace ecg
 
 ECG_API int ecg_conv1d_bf16_supported(int C_in, int C_out, int K, int pad) {
     // bit 0: forward (C_in % 4 == 0, C_out % 32 == 0); bit 1: input-grad (roles swapped);

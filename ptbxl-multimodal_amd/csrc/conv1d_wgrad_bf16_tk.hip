@@ -29,6 +29,7 @@
 // Exact on bf16-rounded operands up to fp32 accumulation order (tests/test_gpu_ops.py::test_bf16_tk_*).
 // Replaces autograd's conv weight-gradient (reference src/models/ecg_cnn.py:13 via loss.backward()).
 #include "mfma_util.h"
+#include "conv1d_internal.h"
 
 namespace ecg {
 
@@ -407,9 +408,6 @@ __global__ __launch_bounds__(512) void conv1d_wgrad_bf16_tk_kernel(
 
 }  // namespace tk
 
-// conv1d_direct.hip: dw[i] = sum_s slab[s][i] in fixed order
-int wgrad_reduce(const float *ws, float *dw, float *db, size_t wslab, int Cout, int S, hipStream_t st);
-
 #ifndef ECG_TK_RT128
 #define ECG_TK_RT128 512         // column-tile width of the 128-channel plan (A/B knob: 256 halves the slab bytes per layer)
 #endif
@@ -440,18 +438,18 @@ bool wgrad_bf16_tk_supported(int Cin, int Cout, int K, int pad) {
     return K == tk::KK && pad == tk::PAD && Cout % 32 == 0;
 }
 
-int wgrad_bf16_tk_dy_stride(int Lo) { return cdiv(Lo, tk::TT) * tk::TT; }
+static int wgrad_bf16_tk_dy_stride(int Lo) { return cdiv(Lo, tk::TT) * tk::TT; }
 
 // the shortest input row the entry point takes (its ECG_REQUIRE below); callers that choose between this form and the
 // fp32 one ask ecg_conv1d_bf16_tk_min_len instead of carrying the number
 constexpr int TK_MIN_L = 16;
 
-size_t wgrad_bf16_tk_ws_floats(int N, int Cin, int Cout, int L, int K, int pad) {
+static size_t wgrad_bf16_tk_ws_floats(int N, int Cin, int Cout, int L, int K, int pad) {
     return tk_plan(N, Cin, Cout, L + 2 * pad - K + 1).slab_floats + 16;
 }
 
-int wgrad_bf16_tk(const void *dy_bf16, int ldy, const void *x, int x_is_bf16, int ldx, float *dw, float *db,
-                  float *ws, int N, int Cin, int Cout, int L, int K, int pad, hipStream_t st) {
+static int wgrad_bf16_tk(const void *dy_bf16, int ldy, const void *x, int x_is_bf16, int ldx, float *dw, float *db,
+                         float *ws, int N, int Cin, int Cout, int L, int K, int pad, hipStream_t st) {
     const int Lo = L + 2 * pad - K + 1;
     const TkPlan p = tk_plan(N, Cin, Cout, Lo);
     if (!p.m_t) return fail(ECG_EINVAL, "conv1d_bwd_weight_bias_bf16_ncl: C_out=%d is not a multiple of 32", Cout);

@@ -1,6 +1,8 @@
 // mfma_util.h — device-only leaf helpers shared by the matrix-core convolution kernels (conv1d_mfma.hip,
-// conv1d_mfma_bf16.hip, conv1d_bf16_ring.hip, conv1d_wgrad_bf16_tk.hip).  Nothing here keeps state: the per-file stamp
-// buffers stay in their translation units (the library is built without relocatable device code).
+// conv1d_mfma_bf16.hip, conv1d_bf16_ring.hip, conv1d_wgrad_bf16_tk.hip): the operand vector types, the in-kernel stamp
+// macro, the LDS-DMA piece (glds16), the counted waits (wait_vm, wait_lgkm), the accumulator row map and the XCD block
+// order.  Nothing here keeps state: the per-file stamp buffers stay in their translation units (the library is built
+// without relocatable device code).  What the same files share on the HOST is in conv1d_internal.h.
 #pragma once
 #include "bf16_util.h"      // the bf16 pair of a packed dword: bf16_lo, bf16_hi, pack2_bf16
 
@@ -40,6 +42,22 @@ __device__ __forceinline__ void glds16(const void *base_in, unsigned voff, unsig
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(voff), "s"(base), "s"(dst) : "memory");
+}
+
+// Counted waits: s_waitcnt on ONE counter, the others left at "no wait".  hipcc's own placement drains lgkmcnt(0) on every
+// second step of the kernels' fragment double-buffering — i.e. it waits for the LDS reads just issued for the NEXT step
+// in front of MFMAs that only need the previous ones; an explicit counted wait placed before the MFMAs tells its
+// scoreboard the operands are complete (a count larger than the reads really in flight is harmless: the compiler still
+// adds whatever wait correctness needs).  wait_vm counts what glds16 issued, which the compiler does not see at all.
+template <int N>
+__device__ __forceinline__ void wait_vm() {             // vmcnt(N)
+    static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
+    __builtin_amdgcn_s_waitcnt(((N >> 4) << 14) | 0x0F70 | (N & 15));
+}
+template <int N>
+__device__ __forceinline__ void wait_lgkm() {           // lgkmcnt(N)
+    static_assert(N >= 0 && N < 16, "lgkmcnt is a 4-bit counter");
+    __builtin_amdgcn_s_waitcnt(0xC07F | (N << 8));
 }
 
 // row of element r of a 32x32 accumulator held by this lane: (r&3) + 8*(r>>2) + 4*(lane>>5)
