@@ -42,6 +42,7 @@
 //   bins   workgroup (b, c) adds w, w [y == 1] and w q into the bin of q in LDS (integer atomics, one set of bins per
 //   wave), the two halves of the squared error and OUT, BAD per lane.  Integer sums only: one value in any order.
 #include <cmath>
+#include <initializer_list>
 
 #include "common.h"
 
@@ -73,10 +74,7 @@ __host__ __device__ __forceinline__ bool metrics_key_nonfinite(unsigned k) {
 
 __host__ __device__ __forceinline__ int metrics_padded(int N) { return (N + 3) & ~3; }
 
-// the workspaces hold 16-byte words; the caller owes 4-byte alignment only, the helpers give 16 bytes of slack
-__host__ __forceinline__ unsigned *metrics_ws_base(void *workspace) {
-    return reinterpret_cast<unsigned *>(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
-}
+// the workspaces hold 16-byte words; the caller owes 4-byte alignment only, so 16 bytes of slack (metrics_ws)
 __host__ __forceinline__ size_t metrics_ws_bytes(int N, int C) { return (size_t)C * metrics_padded(N) * 4 + 16; }
 
 __global__ __launch_bounds__(kMtThreads) void metrics_keys_kernel(const float *__restrict__ prob, unsigned *__restrict__ keys,
@@ -172,6 +170,11 @@ __global__ __launch_bounds__(kMtThreads) void metrics_pack_kernel(const float *_
 
 typedef unsigned long long mt_u64;
 
+// THE walk word: tp in the high half, fp in the low one.  Both stay below 2^30, so sums of words never carry across.
+__device__ __forceinline__ mt_u64 mt_word(int tp, int fp) { return (mt_u64)(unsigned)tp << 32 | (mt_u64)(unsigned)fp; }
+__device__ __forceinline__ long long mt_tp(mt_u64 word) { return (long long)(word >> 32); }
+__device__ __forceinline__ long long mt_fp(mt_u64 word) { return (long long)(word & 0xffffffffu); }
+
 // exclusive scan of one value per lane over the workgroup, by + or by max; `total` is the value over all lanes.  wtot: one
 // slot per wave, private to the call site (a slot is rewritten only after a later __syncthreads of the caller's loop).
 template <bool kMax>
@@ -204,6 +207,20 @@ __device__ __forceinline__ int wave_sum_int(int v) {
     return v;
 }
 
+// K order-free totals of the workgroup: every lane's part -> wave sums -> integer atomics on tot_s in LDS, which the
+// caller zeroed beforehand (`if (tid < K) tot_s[tid] = 0`; the first barrier here orders that).  On return every lane
+// sees all of tot_s.  Integers: one value in any order.
+template <int K>
+__device__ __forceinline__ void metrics_block_totals(const int (&tot)[K], int *tot_s) {
+    __syncthreads();
+#pragma unroll
+    for (int f = 0; f < K; ++f) {
+        const int s = wave_sum_int(tot[f]);
+        if ((threadIdx.x & (kWave - 1)) == 0) atomicAdd(&tot_s[f], s);
+    }
+    __syncthreads();
+}
+
 // the four packed words of lane `tid` in the chunk at r0, and their weights (0 for a word that is not valid)
 __device__ __forceinline__ void metrics_load4(const unsigned *__restrict__ pc, const int *__restrict__ wb, int r0, int Np,
                                               unsigned pk[kMtItems], int wt[kMtItems], int lane = (int)threadIdx.x) {
@@ -216,8 +233,8 @@ __device__ __forceinline__ void metrics_load4(const unsigned *__restrict__ pc, c
         wt[k] = (pk[k] & kMtValid) ? (wb ? wb[pk[k] & 0xffffu] : 1) : 0;
 }
 
-// One chunk of the walk along the ranks, the lane's four consecutive items in pk / wt: cum[k] = (tp << 32 | fp) at item k
-// (both stay below 2^30, so the halves never meet) by one block-wide sum scan, and start[k] = the same word at the latest
+// One chunk of the walk along the ranks, the lane's four consecutive items in pk / wt: cum[k] = the walk word (mt_word) at
+// item k by one block-wide sum scan, and start[k] = the same word at the latest
 // group end BEFORE item k (0 if there is none) by one block-wide MAX scan of the word at group ends: tp and fp never
 // decrease, so the latest group end is the largest.  carry / carry_end hold the two across chunks.  The caller's loop has
 // a __syncthreads between two calls (the slots of wsum / wmax).
@@ -227,7 +244,7 @@ __device__ __forceinline__ void metrics_walk4(const unsigned pk[kMtItems], const
     mt_u64 run = 0;
 #pragma unroll
     for (int k = 0; k < kMtItems; ++k) {
-        run += (pk[k] & kMtPos) ? (mt_u64)(unsigned)wt[k] << 32 : (pk[k] & kMtNeg) ? (mt_u64)(unsigned)wt[k] : 0;
+        run += (pk[k] & kMtPos) ? mt_word(wt[k], 0) : (pk[k] & kMtNeg) ? mt_word(0, wt[k]) : 0;
         cum[k] = run;
     }
     mt_u64 total, total_end;
@@ -275,13 +292,7 @@ __global__ __launch_bounds__(kMtThreads) void metrics_scan_kernel(const unsigned
             tot[7] += (!pos && !neg) ? wt[k] : 0;            // wt is 0 for padding
         }
     }
-    __syncthreads();
-#pragma unroll
-    for (int f = 0; f < kMtTotals; ++f) {
-        const int s = wave_sum_int(tot[f]);
-        if ((tid & (kWave - 1)) == 0) atomicAdd(&tot_s[f], s);   // LDS, integers
-    }
-    __syncthreads();
+    metrics_block_totals(tot, tot_s);
     const long long POS = tot_s[0];
     const double dPOS = (double)POS;
 
@@ -297,11 +308,10 @@ __global__ __launch_bounds__(kMtThreads) void metrics_scan_kernel(const unsigned
         const int e0 = kMtItems * tid, r = r0 + e0;
 #pragma unroll
         for (int k = 0; k < kMtItems; ++k) {
-            const long long tp = (long long)(cum[k] >> 32), fp = (long long)(cum[k] & 0xffffffffu);
+            const long long tp = mt_tp(cum[k]), fp = mt_fp(cum[k]);
             double term = 0.0;
             if (pk[k] & kMtEnd) {
-                const mt_u64 pe = start[k];
-                const long long tpp = (long long)(pe >> 32), fpp = (long long)(pe & 0xffffffffu), d = tp - tpp;
+                const long long tpp = mt_tp(start[k]), fpp = mt_fp(start[k]), d = tp - tpp;
                 u2 += (fp - fpp) * (tp + tpp);
                 if (d > 0) term = ((double)d / dPOS) * ((double)tp / (double)(tp + fp));
             }
@@ -360,11 +370,11 @@ __global__ __launch_bounds__(kMtThreads) void metrics_place_kernel(const unsigne
         int h[kMtItems];
 #pragma unroll
         for (int k = 0; k < kMtItems; ++k)
-            h[k] = (pk[k] & kMtPos) ? -(int)(start[k] & 0xffffffffu) : (int)(start[k] >> 32);
+            h[k] = (pk[k] & kMtPos) ? -(int)mt_fp(start[k]) : (int)mt_tp(start[k]);
         if (r < Np) *reinterpret_cast<int4 *>(hc + r) = make_int4(h[0], h[1], h[2], h[3]);   // r and Np are multiples of 4
         __syncthreads();                                     // the scan's slots; after the last chunk, the plane is visible
     }
-    const int POS = (int)(carry >> 32), NEG = (int)(carry & 0xffffffffu);
+    const int POS = (int)mt_tp(carry), NEG = (int)mt_fp(carry);
 
     const int lane = kMtThreads - 1 - tid;
     carry = 0, carry_end = 0;
@@ -389,7 +399,7 @@ __global__ __launch_bounds__(kMtThreads) void metrics_place_kernel(const unsigne
         for (int k = 0; k < kMtItems; ++k) {
             const int i = kMtItems - 1 - k;
             if (!(pk[i] & kMtValid)) continue;
-            const int stp = (int)(start[k] >> 32), sfp = (int)(start[k] & 0xffffffffu);
+            const int stp = (int)mt_tp(start[k]), sfp = (int)mt_fp(start[k]);
             out[pk[i] & 0xffffu] = (pk[i] & kMtPos) ? NEG + h[i] + sfp : (pk[i] & kMtNeg) ? h[i] + POS - stp : -1;   // row < N
         }
         __syncthreads();
@@ -470,8 +480,7 @@ struct OpBest {
 __device__ __forceinline__ bool op_better(int rule, mt_u64 aw, int ar, mt_u64 bw, int br, long long P, long long Q) {
     if (ar < 0) return false;
     if (br < 0) return true;
-    const long long ta = (long long)(aw >> 32), fa = (long long)(aw & 0xffffffffu);
-    const long long tb = (long long)(bw >> 32), fb = (long long)(bw & 0xffffffffu);
+    const long long ta = mt_tp(aw), fa = mt_fp(aw), tb = mt_tp(bw), fb = mt_fp(bw);
     long long oa, ob;
     if (rule == ECG_OP_F1) {
         const long long da = ta + fa + P, db = tb + fb + P;   // a zero denominator counts as 0 / 1
@@ -500,17 +509,14 @@ __global__ __launch_bounds__(kMtThreads) void metrics_operating_kernel(const uns
     unsigned pk[kMtItems];
     int wt[kMtItems];
 
-    int pos = 0, neg = 0;                                    // pass 1: POS and NEG, which the objectives need
+    int tot[2] = {0, 0};                                     // pass 1: POS and NEG, which the objectives need
     if (tid < 2) tot_s[tid] = 0;
     for (int r0 = 0; r0 < N; r0 += kMtChunk) {
         metrics_load4(pc, wb, r0, Np, pk, wt);
 #pragma unroll
-        for (int k = 0; k < kMtItems; ++k) pos += (pk[k] & kMtPos) ? wt[k] : 0, neg += (pk[k] & kMtNeg) ? wt[k] : 0;
+        for (int k = 0; k < kMtItems; ++k) tot[0] += (pk[k] & kMtPos) ? wt[k] : 0, tot[1] += (pk[k] & kMtNeg) ? wt[k] : 0;
     }
-    __syncthreads();
-    pos = wave_sum_int(pos), neg = wave_sum_int(neg);
-    if ((tid & (kWave - 1)) == 0) atomicAdd(&tot_s[0], pos), atomicAdd(&tot_s[1], neg);   // LDS, integers
-    __syncthreads();
+    metrics_block_totals(tot, tot_s);
     const long long P = tot_s[0], Q = tot_s[1];
 
     OpBest best[ECG_OP_RULES];
@@ -525,7 +531,7 @@ __global__ __launch_bounds__(kMtThreads) void metrics_operating_kernel(const uns
 #pragma unroll
         for (int k = 0; k < kMtItems; ++k) {
             if ((pk[k] & (kMtEnd | kMtNan | kMtValid)) != (kMtEnd | kMtValid)) continue;
-            const long long tp = (long long)(cum[k] >> 32), fp = (long long)(cum[k] & 0xffffffffu);
+            const long long tp = mt_tp(cum[k]), fp = mt_fp(cum[k]);
             const bool ok[ECG_OP_RULES] = {true, true, P > 0 && tp * sens_den >= (long long)sens_num * P,
                                            Q > 0 && (Q - fp) * spec_den >= (long long)spec_num * Q};
 #pragma unroll
@@ -553,7 +559,7 @@ __global__ __launch_bounds__(kMtThreads) void metrics_operating_kernel(const uns
             if (op_better(tid, best_w[tid][v], best_r[tid][v], bw, br, P, Q)) bw = best_w[tid][v], br = best_r[tid][v];
         long long *o = points + (((size_t)b * C + c) * ECG_OP_RULES + tid) * ECG_OP_FIELDS;
         o[ECG_OP_RANK] = br, o[ECG_OP_ROW] = br < 0 ? -1 : (long long)(pc[br] & 0xffffu);   // br < N <= Np
-        o[ECG_OP_TP] = br < 0 ? 0 : (long long)(bw >> 32), o[ECG_OP_FP] = br < 0 ? 0 : (long long)(bw & 0xffffffffu);
+        o[ECG_OP_TP] = br < 0 ? 0 : mt_tp(bw), o[ECG_OP_FP] = br < 0 ? 0 : mt_fp(bw);
     }
     if (tid == 0) totals[((size_t)b * C + c) * 2] = P, totals[((size_t)b * C + c) * 2 + 1] = Q;
 }
@@ -589,13 +595,7 @@ __global__ __launch_bounds__(kMtThreads) void metrics_cf_sums_kernel(const unsig
         const bool pred = (v >> t) & 1u;
         acc[0] += pred ? wp : 0, acc[1] += pred ? wn : 0, acc[2] += wp, acc[3] += wn;
     }
-    __syncthreads();
-#pragma unroll
-    for (int f = 0; f < 4; ++f) {
-        const int s = wave_sum_int(acc[f]);
-        if ((tid & (kWave - 1)) == 0) atomicAdd(&sum_s[f], s);   // LDS, integers
-    }
-    __syncthreads();
+    metrics_block_totals(acc, sum_s);
     if (tid == 0) {
         const long long tp = sum_s[0], fp = sum_s[1], P = sum_s[2], Q = sum_s[3];
         long long *o = out + (((size_t)b * T + t) * C + c) * ECG_CF_FIELDS;
@@ -661,8 +661,59 @@ __global__ __launch_bounds__(kMtThreads) void metrics_rl_bins_kernel(const unsig
     }
 }
 
-static bool metrics_sizes_ok(int N, int C) { return N >= 1 && N <= kMtMaxN && C >= 1 && C <= kMtMaxC; }
+// ---- host side.  Every kind of refusal is written once; an entry point calls them in the order of its contract, and
+// ecg_last_error() names the first that fails.  The *_workspace_bytes queries refuse by returning 0 and leave no text.
+#define MT_CHECK(call) do { if (int rc_ = (call)) return rc_; } while (0)
+// one launch of kMtThreads lanes per workgroup and its check_launch under the kernel's name -> ECG_OK or the launch's code
+template <typename... P, typename... A>
+static int metrics_launch(const char *name, void (*kernel)(P...), dim3 grid, ecg_stream_t stream, A... args) {
+    hipLaunchKernelGGL(kernel, grid, dim3(kMtThreads), 0, as_stream(stream), static_cast<P>(args)...);
+    return check_launch(name);
+}
+#define MT_LAUNCH(kernel, ...) metrics_launch(#kernel, kernel, __VA_ARGS__)
+static dim3 metrics_elementwise(int a, int b) { return dim3(cdiv((long long)a * b, kMtThreads)); }   // one lane per element
+
+static bool metrics_in(int v, int max) { return v >= 1 && v <= max; }
+static bool metrics_sizes_ok(int N, int C) { return metrics_in(N, kMtMaxN) && metrics_in(C, kMtMaxC); }
 static bool aligned_to(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+static int metrics_limit(const char *who, const char *name, int v, int max) {
+    ECG_REQUIRE(metrics_in(v, max), "%s: %s=%d outside [1,%d]", who, name, v, max);
+    return ECG_OK;
+}
+static int metrics_sizes(const char *who, int N, int C) {
+    MT_CHECK(metrics_limit(who, "N", N, kMtMaxN));
+    return metrics_limit(who, "C", C, kMtMaxC);
+}
+static int metrics_weight_rows(const char *who, int B, const int *w) {
+    ECG_REQUIRE(w || B == 1, "%s: B=%d weight rows need w (NULL means one row of ones)", who, B);
+    return ECG_OK;
+}
+// eight: the bases that must be 8-byte aligned, `names` their names in the message; four: the other bases that must be
+// there; optional: bases that may be NULL.  Nothing may be missing before any alignment is looked at.
+typedef std::initializer_list<const void *> MtBases;
+static int metrics_bases(const char *who, MtBases eight, const char *names, MtBases four, MtBases optional = {}) {
+    for (MtBases list : {eight, four})
+        for (const void *p : list) ECG_REQUIRE(p, "%s: null pointer", who);
+    for (const void *p : eight) ECG_REQUIRE(aligned_to(p, 8), "%s: %s must be 8-byte aligned", who, names);
+    for (MtBases list : {four, optional})
+        for (const void *p : list) ECG_REQUIRE(aligned_to(p, 4), "%s: a base is not 4-byte aligned", who);
+    return ECG_OK;
+}
+
+// the workspace as the kernels see it: its first 16-byte boundary (the caller owes 4-byte alignment only, the
+// *_workspace_bytes give 16 bytes of slack) and the padded length of a column
+struct MtWorkspace { unsigned *base; int Np; };
+static MtWorkspace metrics_ws(void *workspace, int N) {
+    return {reinterpret_cast<unsigned *>(((uintptr_t)workspace + 15) & ~(uintptr_t)15), metrics_padded(N)};
+}
+
+// the first launch of counts, operating and placements
+static int metrics_pack(const float *prob, const float *y, const int *order, MtWorkspace ws, int N, int C, float threshold,
+                        ecg_stream_t stream) {
+    const dim3 grid(cdiv(ws.Np, kMtThreads), C);
+    return MT_LAUNCH(metrics_pack_kernel, grid, stream, prob, y, order, ws.base, N, C, ws.Np, threshold);
+}
 
 }  // namespace ecg
 
@@ -673,129 +724,89 @@ ECG_API int ecg_metrics_slab(void) { return kMtSlab; }
 ECG_API size_t ecg_metrics_order_workspace_bytes(int N, int C) { return metrics_sizes_ok(N, C) ? metrics_ws_bytes(N, C) : 0; }
 
 ECG_API size_t ecg_metrics_counts_workspace_bytes(int N, int C, int B) {
-    return metrics_sizes_ok(N, C) && B >= 1 && B <= kMtMaxB ? metrics_ws_bytes(N, C) : 0;
+    return metrics_sizes_ok(N, C) && metrics_in(B, kMtMaxB) ? metrics_ws_bytes(N, C) : 0;
 }
 
 ECG_API int ecg_metrics_order(const float *prob, int *order, int *nonfinite, void *workspace, int N, int C,
                               ecg_stream_t stream) {
     const char *who = "metrics_order";
-    ECG_REQUIRE(N >= 1 && N <= kMtMaxN, "%s: N=%d outside [1,%d]", who, N, kMtMaxN);
-    ECG_REQUIRE(C >= 1 && C <= kMtMaxC, "%s: C=%d outside [1,%d]", who, C, kMtMaxC);
-    ECG_REQUIRE(prob && order && nonfinite && workspace, "%s: null pointer", who);
-    ECG_REQUIRE(aligned_to(prob, 4) && aligned_to(order, 4) && aligned_to(nonfinite, 4) && aligned_to(workspace, 4),
-                "%s: a base is not 4-byte aligned", who);
-    unsigned *keys = metrics_ws_base(workspace);
-    const int Np = metrics_padded(N);
-    hipLaunchKernelGGL(metrics_keys_kernel, dim3(cdiv((long long)N * C, kMtThreads)), dim3(kMtThreads), 0, as_stream(stream),
-                       prob, keys, N, C, Np);
-    if (int rc = check_launch("metrics_keys_kernel")) return rc;
-    hipLaunchKernelGGL(metrics_rank_kernel, dim3(cdiv(N, kMtThreads), C), dim3(kMtThreads), 0, as_stream(stream), keys, order,
-                       nonfinite, N, Np);
-    return check_launch("metrics_rank_kernel");
+    MT_CHECK(metrics_sizes(who, N, C));
+    MT_CHECK(metrics_bases(who, {}, "", {prob, order, nonfinite, workspace}));
+    const MtWorkspace keys = metrics_ws(workspace, N);
+    MT_CHECK(MT_LAUNCH(metrics_keys_kernel, metrics_elementwise(N, C), stream, prob, keys.base, N, C, keys.Np));
+    return MT_LAUNCH(metrics_rank_kernel, dim3(cdiv(N, kMtThreads), C), stream, keys.base, order, nonfinite, N, keys.Np);
 }
 
 ECG_API int ecg_metrics_counts(const float *prob, const float *y, const int *order, const int *w, long long *fields, double *ap,
                                int *curve, void *workspace, int N, int C, int B, float threshold, ecg_stream_t stream) {
     const char *who = "metrics_counts";
-    ECG_REQUIRE(N >= 1 && N <= kMtMaxN, "%s: N=%d outside [1,%d]", who, N, kMtMaxN);
-    ECG_REQUIRE(C >= 1 && C <= kMtMaxC, "%s: C=%d outside [1,%d]", who, C, kMtMaxC);
-    ECG_REQUIRE(B >= 1 && B <= kMtMaxB, "%s: B=%d outside [1,%d]", who, B, kMtMaxB);
-    ECG_REQUIRE(w || B == 1, "%s: B=%d weight rows need w (NULL means one row of ones)", who, B);
+    MT_CHECK(metrics_sizes(who, N, C));
+    MT_CHECK(metrics_limit(who, "B", B, kMtMaxB));
+    MT_CHECK(metrics_weight_rows(who, B, w));
     ECG_REQUIRE(threshold == threshold, "%s: threshold is NaN", who);
-    ECG_REQUIRE(prob && y && order && fields && ap && workspace, "%s: null pointer", who);
-    ECG_REQUIRE(aligned_to(fields, 8) && aligned_to(ap, 8), "%s: fields and ap must be 8-byte aligned", who);
-    ECG_REQUIRE(aligned_to(prob, 4) && aligned_to(y, 4) && aligned_to(order, 4) && aligned_to(w, 4) && aligned_to(curve, 4) &&
-                    aligned_to(workspace, 4),
-                "%s: a base is not 4-byte aligned", who);
-    unsigned *packed = metrics_ws_base(workspace);
-    const int Np = metrics_padded(N);
-    hipLaunchKernelGGL(metrics_pack_kernel, dim3(cdiv(Np, kMtThreads), C), dim3(kMtThreads), 0, as_stream(stream), prob, y, order,
-                       packed, N, C, Np, threshold);
-    if (int rc = check_launch("metrics_pack_kernel")) return rc;
-    hipLaunchKernelGGL(metrics_scan_kernel, dim3(B, C), dim3(kMtThreads), 0, as_stream(stream), packed, w, fields, ap, curve, N, C,
-                       Np);
-    return check_launch("metrics_scan_kernel");
+    MT_CHECK(metrics_bases(who, {fields, ap}, "fields and ap", {prob, y, order, workspace}, {w, curve}));
+    const MtWorkspace packed = metrics_ws(workspace, N);
+    MT_CHECK(metrics_pack(prob, y, order, packed, N, C, threshold, stream));
+    return MT_LAUNCH(metrics_scan_kernel, dim3(B, C), stream, packed.base, w, fields, ap, curve, N, C, packed.Np);
 }
 
 constexpr int kOpMaxDen = 1000000;
-static bool metrics_fraction_ok(int num, int den) { return num >= 0 && num <= den && den >= 1 && den <= kOpMaxDen; }
+static int metrics_fraction(const char *who, const char *name, int num, int den) {
+    ECG_REQUIRE(num >= 0 && num <= den && den >= 1 && den <= kOpMaxDen, "%s: %s %d/%d is not 0 <= num <= den, 1 <= den <= %d", who,
+                name, num, den, kOpMaxDen);
+    return ECG_OK;
+}
 
 ECG_API size_t ecg_metrics_operating_workspace_bytes(int N, int C, int B) { return ecg_metrics_counts_workspace_bytes(N, C, B); }
 
 ECG_API size_t ecg_metrics_confusion_workspace_bytes(int N, int C, int B, int T) {
-    return T >= 1 && T <= kCfMaxT ? ecg_metrics_counts_workspace_bytes(N, C, B) : 0;
+    return metrics_in(T, kCfMaxT) ? ecg_metrics_counts_workspace_bytes(N, C, B) : 0;
 }
 
 ECG_API size_t ecg_metrics_reliability_workspace_bytes(int N, int C, int B, int M) {
-    return M >= 1 && M <= kRlMaxM ? ecg_metrics_counts_workspace_bytes(N, C, B) : 0;
+    return metrics_in(M, kRlMaxM) ? ecg_metrics_counts_workspace_bytes(N, C, B) : 0;
 }
 
 ECG_API int ecg_metrics_operating(const float *prob, const float *y, const int *order, const int *w, long long *points,
                                   long long *totals, void *workspace, int N, int C, int B, int sens_num, int sens_den,
                                   int spec_num, int spec_den, ecg_stream_t stream) {
     const char *who = "metrics_operating";
-    ECG_REQUIRE(N >= 1 && N <= kMtMaxN, "%s: N=%d outside [1,%d]", who, N, kMtMaxN);
-    ECG_REQUIRE(C >= 1 && C <= kMtMaxC, "%s: C=%d outside [1,%d]", who, C, kMtMaxC);
-    ECG_REQUIRE(B >= 1 && B <= kMtMaxB, "%s: B=%d outside [1,%d]", who, B, kMtMaxB);
-    ECG_REQUIRE(metrics_fraction_ok(sens_num, sens_den), "%s: sensitivity %d/%d is not 0 <= num <= den, 1 <= den <= %d", who,
-                sens_num, sens_den, kOpMaxDen);
-    ECG_REQUIRE(metrics_fraction_ok(spec_num, spec_den), "%s: specificity %d/%d is not 0 <= num <= den, 1 <= den <= %d", who,
-                spec_num, spec_den, kOpMaxDen);
-    ECG_REQUIRE(w || B == 1, "%s: B=%d weight rows need w (NULL means one row of ones)", who, B);
-    ECG_REQUIRE(prob && y && order && points && totals && workspace, "%s: null pointer", who);
-    ECG_REQUIRE(aligned_to(points, 8) && aligned_to(totals, 8), "%s: points and totals must be 8-byte aligned", who);
-    ECG_REQUIRE(aligned_to(prob, 4) && aligned_to(y, 4) && aligned_to(order, 4) && aligned_to(w, 4) && aligned_to(workspace, 4),
-                "%s: a base is not 4-byte aligned", who);
-    unsigned *packed = metrics_ws_base(workspace);
-    const int Np = metrics_padded(N);
-    hipLaunchKernelGGL(metrics_pack_kernel, dim3(cdiv(Np, kMtThreads), C), dim3(kMtThreads), 0, as_stream(stream), prob, y, order,
-                       packed, N, C, Np, 0.0f);
-    if (int rc = check_launch("metrics_pack_kernel")) return rc;
-    hipLaunchKernelGGL(metrics_operating_kernel, dim3(B, C), dim3(kMtThreads), 0, as_stream(stream), packed, w, points, totals, N,
-                       C, Np, sens_num, sens_den, spec_num, spec_den);
-    return check_launch("metrics_operating_kernel");
+    MT_CHECK(metrics_sizes(who, N, C));
+    MT_CHECK(metrics_limit(who, "B", B, kMtMaxB));
+    MT_CHECK(metrics_fraction(who, "sensitivity", sens_num, sens_den));
+    MT_CHECK(metrics_fraction(who, "specificity", spec_num, spec_den));
+    MT_CHECK(metrics_weight_rows(who, B, w));
+    MT_CHECK(metrics_bases(who, {points, totals}, "points and totals", {prob, y, order, workspace}, {w}));
+    const MtWorkspace packed = metrics_ws(workspace, N);
+    MT_CHECK(metrics_pack(prob, y, order, packed, N, C, 0.0f, stream));
+    return MT_LAUNCH(metrics_operating_kernel, dim3(B, C), stream, packed.base, w, points, totals, N, C, packed.Np, sens_num,
+                     sens_den, spec_num, spec_den);
 }
 
 ECG_API int ecg_metrics_confusion(const float *prob, const float *y, const int *w, const float *thr, long long *out,
                                   void *workspace, int N, int C, int B, int T, ecg_stream_t stream) {
     const char *who = "metrics_confusion";
-    ECG_REQUIRE(N >= 1 && N <= kMtMaxN, "%s: N=%d outside [1,%d]", who, N, kMtMaxN);
-    ECG_REQUIRE(C >= 1 && C <= kMtMaxC, "%s: C=%d outside [1,%d]", who, C, kMtMaxC);
-    ECG_REQUIRE(B >= 1 && B <= kMtMaxB, "%s: B=%d outside [1,%d]", who, B, kMtMaxB);
-    ECG_REQUIRE(T >= 1 && T <= kCfMaxT, "%s: T=%d outside [1,%d]", who, T, kCfMaxT);
-    ECG_REQUIRE(w || B == 1, "%s: B=%d weight rows need w (NULL means one row of ones)", who, B);
-    ECG_REQUIRE(prob && y && thr && out && workspace, "%s: null pointer", who);
-    ECG_REQUIRE(aligned_to(out, 8), "%s: out must be 8-byte aligned", who);
-    ECG_REQUIRE(aligned_to(prob, 4) && aligned_to(y, 4) && aligned_to(w, 4) && aligned_to(thr, 4) && aligned_to(workspace, 4),
-                "%s: a base is not 4-byte aligned", who);
-    unsigned *bits = metrics_ws_base(workspace);
-    const int Np = metrics_padded(N);
-    hipLaunchKernelGGL(metrics_cf_bits_kernel, dim3(cdiv((long long)N * C, kMtThreads)), dim3(kMtThreads), 0, as_stream(stream),
-                       prob, y, thr, bits, N, C, Np, T);
-    if (int rc = check_launch("metrics_cf_bits_kernel")) return rc;
-    hipLaunchKernelGGL(metrics_cf_sums_kernel, dim3(B, C, T), dim3(kMtThreads), 0, as_stream(stream), bits, w, out, N, C, Np);
-    return check_launch("metrics_cf_sums_kernel");
+    MT_CHECK(metrics_sizes(who, N, C));
+    MT_CHECK(metrics_limit(who, "B", B, kMtMaxB));
+    MT_CHECK(metrics_limit(who, "T", T, kCfMaxT));
+    MT_CHECK(metrics_weight_rows(who, B, w));
+    MT_CHECK(metrics_bases(who, {out}, "out", {prob, y, thr, workspace}, {w}));
+    const MtWorkspace bits = metrics_ws(workspace, N);
+    MT_CHECK(MT_LAUNCH(metrics_cf_bits_kernel, metrics_elementwise(N, C), stream, prob, y, thr, bits.base, N, C, bits.Np, T));
+    return MT_LAUNCH(metrics_cf_sums_kernel, dim3(B, C, T), stream, bits.base, w, out, N, C, bits.Np);
 }
 
 ECG_API int ecg_metrics_reliability(const float *prob, const float *y, const int *w, long long *bins, long long *tot,
                                     void *workspace, int N, int C, int B, int M, ecg_stream_t stream) {
     const char *who = "metrics_reliability";
-    ECG_REQUIRE(N >= 1 && N <= kMtMaxN, "%s: N=%d outside [1,%d]", who, N, kMtMaxN);
-    ECG_REQUIRE(C >= 1 && C <= kMtMaxC, "%s: C=%d outside [1,%d]", who, C, kMtMaxC);
-    ECG_REQUIRE(B >= 1 && B <= kMtMaxB, "%s: B=%d outside [1,%d]", who, B, kMtMaxB);
-    ECG_REQUIRE(M >= 1 && M <= kRlMaxM, "%s: M=%d outside [1,%d]", who, M, kRlMaxM);
-    ECG_REQUIRE(w || B == 1, "%s: B=%d weight rows need w (NULL means one row of ones)", who, B);
-    ECG_REQUIRE(prob && y && bins && tot && workspace, "%s: null pointer", who);
-    ECG_REQUIRE(aligned_to(bins, 8) && aligned_to(tot, 8), "%s: bins and tot must be 8-byte aligned", who);
-    ECG_REQUIRE(aligned_to(prob, 4) && aligned_to(y, 4) && aligned_to(w, 4) && aligned_to(workspace, 4),
-                "%s: a base is not 4-byte aligned", who);
-    unsigned *quant = metrics_ws_base(workspace);
-    const int Np = metrics_padded(N);
-    hipLaunchKernelGGL(metrics_rl_quant_kernel, dim3(cdiv((long long)N * C, kMtThreads)), dim3(kMtThreads), 0, as_stream(stream),
-                       prob, y, quant, N, C, Np);
-    if (int rc = check_launch("metrics_rl_quant_kernel")) return rc;
-    hipLaunchKernelGGL(metrics_rl_bins_kernel, dim3(B, C), dim3(kMtThreads), 0, as_stream(stream), quant, w, bins, tot, N, C, Np, M);
-    return check_launch("metrics_rl_bins_kernel");
+    MT_CHECK(metrics_sizes(who, N, C));
+    MT_CHECK(metrics_limit(who, "B", B, kMtMaxB));
+    MT_CHECK(metrics_limit(who, "M", M, kRlMaxM));
+    MT_CHECK(metrics_weight_rows(who, B, w));
+    MT_CHECK(metrics_bases(who, {bins, tot}, "bins and tot", {prob, y, workspace}, {w}));
+    const MtWorkspace quant = metrics_ws(workspace, N);
+    MT_CHECK(MT_LAUNCH(metrics_rl_quant_kernel, metrics_elementwise(N, C), stream, prob, y, quant.base, N, C, quant.Np));
+    return MT_LAUNCH(metrics_rl_bins_kernel, dim3(B, C), stream, quant.base, w, bins, tot, N, C, quant.Np, M);
 }
 
 static size_t metrics_pair_part_count(int N, int C, int M) { return (size_t)C * M * M * metrics_pair_slices(N) * kPsParts; }
@@ -805,44 +816,29 @@ ECG_API size_t ecg_metrics_placements_workspace_bytes(int N, int C) {
 }
 
 ECG_API size_t ecg_metrics_paired_sums_workspace_bytes(int N, int C, int M) {
-    return metrics_sizes_ok(N, C) && M >= 1 && M <= kPsMaxM ? metrics_pair_part_count(N, C, M) * 8 + 16 : 0;
+    return metrics_sizes_ok(N, C) && metrics_in(M, kPsMaxM) ? metrics_pair_part_count(N, C, M) * 8 + 16 : 0;
 }
 
 ECG_API int ecg_metrics_placements(const float *prob, const float *y, const int *order, int *place, void *workspace, int N,
                                    int C, ecg_stream_t stream) {
     const char *who = "metrics_placements";
-    ECG_REQUIRE(N >= 1 && N <= kMtMaxN, "%s: N=%d outside [1,%d]", who, N, kMtMaxN);
-    ECG_REQUIRE(C >= 1 && C <= kMtMaxC, "%s: C=%d outside [1,%d]", who, C, kMtMaxC);
-    ECG_REQUIRE(prob && y && order && place && workspace, "%s: null pointer", who);
-    ECG_REQUIRE(aligned_to(prob, 4) && aligned_to(y, 4) && aligned_to(order, 4) && aligned_to(place, 4) && aligned_to(workspace, 4),
-                "%s: a base is not 4-byte aligned", who);
-    unsigned *packed = metrics_ws_base(workspace);
-    const int Np = metrics_padded(N);
-    int *half = reinterpret_cast<int *>(packed + (size_t)C * Np);   // C * Np * 4 is a multiple of 16
-    hipLaunchKernelGGL(metrics_pack_kernel, dim3(cdiv(Np, kMtThreads), C), dim3(kMtThreads), 0, as_stream(stream), prob, y, order,
-                       packed, N, C, Np, 0.0f);
-    if (int rc = check_launch("metrics_pack_kernel")) return rc;
-    hipLaunchKernelGGL(metrics_place_kernel, dim3(C), dim3(kMtThreads), 0, as_stream(stream), packed, half, place, N, Np);
-    return check_launch("metrics_place_kernel");
+    MT_CHECK(metrics_sizes(who, N, C));
+    MT_CHECK(metrics_bases(who, {}, "", {prob, y, order, place, workspace}));
+    const MtWorkspace packed = metrics_ws(workspace, N);
+    int *half = reinterpret_cast<int *>(packed.base + (size_t)C * packed.Np);   // C * Np * 4 is a multiple of 16
+    MT_CHECK(metrics_pack(prob, y, order, packed, N, C, 0.0f, stream));
+    return MT_LAUNCH(metrics_place_kernel, dim3(C), stream, packed.base, half, place, N, packed.Np);
 }
 
 ECG_API int ecg_metrics_paired_sums(const int *place, const float *prob, const float *y, long long *single, long long *pair,
                                     void *workspace, int N, int C, int M, float threshold, ecg_stream_t stream) {
     const char *who = "metrics_paired_sums";
-    ECG_REQUIRE(N >= 1 && N <= kMtMaxN, "%s: N=%d outside [1,%d]", who, N, kMtMaxN);
-    ECG_REQUIRE(C >= 1 && C <= kMtMaxC, "%s: C=%d outside [1,%d]", who, C, kMtMaxC);
-    ECG_REQUIRE(M >= 1 && M <= kPsMaxM, "%s: M=%d outside [1,%d]", who, M, kPsMaxM);
+    MT_CHECK(metrics_sizes(who, N, C));
+    MT_CHECK(metrics_limit(who, "M", M, kPsMaxM));
     ECG_REQUIRE(threshold == threshold, "%s: threshold is NaN", who);
-    ECG_REQUIRE(place && prob && y && single && pair && workspace, "%s: null pointer", who);
-    ECG_REQUIRE(aligned_to(single, 8) && aligned_to(pair, 8), "%s: single and pair must be 8-byte aligned", who);
-    ECG_REQUIRE(aligned_to(place, 4) && aligned_to(prob, 4) && aligned_to(y, 4) && aligned_to(workspace, 4),
-                "%s: a base is not 4-byte aligned", who);
-    long long *part = reinterpret_cast<long long *>(metrics_ws_base(workspace));
+    MT_CHECK(metrics_bases(who, {single, pair}, "single and pair", {place, prob, y, workspace}));
+    long long *part = reinterpret_cast<long long *>(metrics_ws(workspace, N).base);
     const int S = metrics_pair_slices(N);
-    hipLaunchKernelGGL(metrics_pair_part_kernel, dim3(M * M, C, S), dim3(kMtThreads), 0, as_stream(stream), place, prob, y, part,
-                       N, C, M, threshold);
-    if (int rc = check_launch("metrics_pair_part_kernel")) return rc;
-    hipLaunchKernelGGL(metrics_pair_finish_kernel, dim3(cdiv((long long)C * M * M, kMtThreads)), dim3(kMtThreads), 0,
-                       as_stream(stream), part, single, pair, C, M, S);
-    return check_launch("metrics_pair_finish_kernel");
+    MT_CHECK(MT_LAUNCH(metrics_pair_part_kernel, dim3(M * M, C, S), stream, place, prob, y, part, N, C, M, threshold));
+    return MT_LAUNCH(metrics_pair_finish_kernel, metrics_elementwise(C, M * M), stream, part, single, pair, C, M, S);
 }

@@ -18,6 +18,7 @@ along the ranks by four rules (best F1, Youden's J, a target sensitivity, a targ
 calibration table as integers.  `operating_from_points` and `calibration_from_tables` turn them into ratios;
 `operating_points`, `select_thresholds`, `tuned_metrics` and `calibration` are the user calls, with bootstrap bounds on request.
 """
+import math
 from fractions import Fraction
 
 import numpy as np
@@ -35,11 +36,12 @@ def slab():
     return int(L.query("ecg_metrics_slab"))
 
 
-def _device_matrix(who, name, t, dtype):
+def _device_matrix(who, name, t, dtype, ndim=2):
     if not (torch.is_tensor(t) and t.is_cuda):
         raise L.EcgHipError(f"{who}: a CPU tensor reached the HIP metrics step; {name} must be on the GPU")
-    if t.dtype != dtype or t.dim() != 2:
-        raise L.EcgHipError(f"{who}: {name} must be {dtype} with two dimensions, got {t.dtype} {tuple(t.shape)}")
+    if t.dtype != dtype or t.dim() != ndim:
+        raise L.EcgHipError(f"{who}: {name} must be {dtype} with {('two', 'three')[ndim - 2]} dimensions, got {t.dtype} "
+                            f"{tuple(t.shape)}")
     if not t.is_contiguous():
         raise L.EcgHipError(f"{who}: {name} must be contiguous")
     return t
@@ -58,6 +60,17 @@ def _pair_checked(who, prob, y, weights):
             raise L.EcgHipError(f"{who}: weights must be [B, N={prob.shape[0]}], got {tuple(weights.shape)}")
         B = weights.shape[0]
     return prob, y, weights, B
+
+
+def _order_checked(who, prob, order):
+    """order int32 [C, N] for prob [N, C]: metrics_order(prob) when None, else checked."""
+    N, C = prob.shape
+    if order is None:
+        order = metrics_order(prob)[0]
+    order = _device_matrix(who, "order", order, torch.int32)
+    if tuple(order.shape) != (C, N):
+        raise L.EcgHipError(f"{who}: order must be [C={C}, N={N}], got {tuple(order.shape)}")
+    return order
 
 
 def _workspace(nbytes, device):
@@ -83,11 +96,7 @@ def metrics_counts(prob, y, order=None, weights=None, threshold=0.5, curve=False
     who = "metrics_counts"
     prob, y, weights, B = _pair_checked(who, prob, y, weights)
     N, C = prob.shape
-    if order is None:
-        order = metrics_order(prob)[0]
-    order = _device_matrix(who, "order", order, torch.int32)
-    if tuple(order.shape) != (C, N):
-        raise L.EcgHipError(f"{who}: order must be [C={C}, N={N}], got {tuple(order.shape)}")
+    order = _order_checked(who, prob, order)
     fields = torch.empty((B, C, len(FIELDS)), dtype=torch.int64, device=prob.device)
     ap = torch.empty((B, C), dtype=torch.float64, device=prob.device)
     cv = torch.empty((B, C, N, 2), dtype=torch.int32, device=prob.device) if curve else None
@@ -127,10 +136,27 @@ def summarize(fields, ap):
             "auroc_per_class": auroc, "auprc_per_class": auprc, "f1_per_class": f1}
 
 
+_WORDS = {torch.int64: lambda t: t, torch.int32: lambda t: t.to(torch.int64), torch.float64: lambda t: t.view(torch.int64),
+          torch.float32: lambda t: t.view(torch.int32).to(torch.int64)}
+_UNWORDS = {torch.int64: lambda a: a, torch.int32: lambda a: a.astype(np.int32), torch.float64: lambda a: a.view(np.float64),
+            torch.float32: lambda a: a.astype(np.int32).view(np.float32)}
+
+
+def _read_once(*tensors):
+    """The tensors as numpy arrays of their shapes and dtypes after ONE device read — what every "one host read" of a user
+    call is.  They travel as one int64 vector (_WORDS): int64 as it is, int32 widened, float64 as its bit pattern, float32
+    as its bit pattern through int32, so no NaN payload, signed zero or denormal changes on the way."""
+    host = torch.cat([_WORDS[t.dtype](t).reshape(-1) for t in tensors]).cpu().numpy()    # the one read
+    out, at = [], 0
+    for t in tensors:
+        out.append(_UNWORDS[t.dtype](host[at:at + t.numel()]).reshape(tuple(t.shape)))
+        at += t.numel()
+    return out
+
+
 def _one_read(fields, ap):
-    """(fields, ap) on the host after ONE device read: the doubles travel as their int64 bit patterns beside the fields."""
-    both = torch.cat([fields, ap.view(torch.int64).unsqueeze(-1)], dim=-1).cpu().numpy()
-    return both[..., :len(FIELDS)], np.ascontiguousarray(both[..., len(FIELDS)]).view(np.float64)
+    """(fields, ap) of metrics_counts on the host after one device read: _read_once under its earlier name."""
+    return _read_once(fields, ap)
 
 
 def _inputs(y_true, y_prob):
@@ -158,7 +184,7 @@ def compute_metrics_device(y_true, y_prob, threshold=0.5):
     `threshold` may be one value per class ([C] tensor or sequence, e.g. select_thresholds' result): F1 is then taken at
     those, from one more call (metrics_confusion)."""
     y, p = _inputs(y_true, y_prob)
-    s = summarize(*_one_read(*_counts_at(p, y, None, threshold)))
+    s = summarize(*_read_once(*_counts_at(p, y, None, threshold)))
     return {k: (float(v[0]) if k in MACRO_KEYS else v[0]) for k, v in s.items()}
 
 
@@ -185,22 +211,44 @@ def bootstrap_metrics(y_true, y_prob, n_boot=1000, seed=0, threshold=0.5, alpha=
     per key).  `threshold` may be one value per class, as for compute_metrics_device."""
     y, p = _inputs(y_true, y_prob)
     w = bootstrap_weights(p.shape[0], int(n_boot), seed, p.device)
-    s = summarize(*_one_read(*_counts_at(p, y, w, threshold)))
+    s = summarize(*_read_once(*_counts_at(p, y, w, threshold)))
     out = {"n_nan": {}, "replicates": {}}
-    q = (100.0 * alpha / 2, 100.0 * (1 - alpha / 2))
     for k, v in s.items():
-        point, reps = v[0], v[1:]
-        nan = np.isnan(reps)
+        out[k], out["n_nan"][k], out["replicates"][k] = _interval(k, v, alpha)
+    return out
+
+
+def _boot_rows(n_boot, N, seed, device):
+    """(n_boot as a count >= 0, bootstrap_weights' n_boot + 1 rows or None for no bootstrap) — what every n_boot= of a user
+    call means."""
+    n_boot = max(int(n_boot), 0)
+    return n_boot, (bootstrap_weights(N, n_boot, seed, device) if n_boot > 0 else None)
+
+
+def _percentiles(reps, alpha):
+    """THE percentile rule of every bootstrap here: (lo, hi, n_nan) of replicates [n_boot, ...] along axis 0, lo and hi the
+    alpha/2 and 1 - alpha/2 percentiles over the replicates that are not NaN (NaN when none is left), n_nan how many were
+    left out."""
+    q = (100.0 * alpha / 2, 100.0 * (1 - alpha / 2))
+    nan = np.isnan(reps)
+    with np.errstate(invalid="ignore"):                     # a threshold of +inf among the replicates
+        if not nan.any():                                   # nothing to leave out: every column in one call
+            lo, hi = np.percentile(reps, q, axis=0)
+            return lo, hi, np.zeros(reps.shape[1:], np.int64)
         cols = reps.reshape(reps.shape[0], -1)
         bounds = np.array([np.percentile(col[~np.isnan(col)], q) if (~np.isnan(col)).any() else (np.nan, np.nan)
                            for col in cols.T]).reshape(reps.shape[1:] + (2,))
-        lo, hi = bounds[..., 0], bounds[..., 1]
-        scalar = k in MACRO_KEYS
-        out[k] = {"point": float(point) if scalar else point, "lo": float(lo) if scalar else lo,
-                  "hi": float(hi) if scalar else hi}
-        out["n_nan"][k] = int(nan.sum()) if scalar else nan.sum(0)
-        out["replicates"][k] = reps
-    return out
+    return bounds[..., 0], bounds[..., 1], nan.sum(0)
+
+
+def _interval(key, values, alpha):
+    """values [1 + n_boot, ...], row 0 the point value -> ({"point", "lo", "hi"}, n_nan, replicates) of one key, Python
+    scalars for MACRO_KEYS."""
+    point, reps = values[0], values[1:]
+    lo, hi, n_nan = _percentiles(reps, alpha)
+    if key in MACRO_KEYS:
+        return {"point": float(point), "lo": float(lo), "hi": float(hi)}, int(n_nan), reps
+    return {"point": point, "lo": lo, "hi": hi}, n_nan, reps
 
 
 SINGLE_FIELDS = ("u2", "pos", "neg")
@@ -215,16 +263,9 @@ def metrics_placements(prob, y, order=None):
     twice the positives that score above it plus the ties, -1 for a row whose label is neither 0 nor 1 (ecg_metrics_placements).
     place / (2 NEG) and place / (2 POS) are DeLong's structural components."""
     who = "metrics_placements"
-    prob = _device_matrix(who, "prob", prob, torch.float32)
-    y = _device_matrix(who, "y", y, torch.float32)
-    if y.shape != prob.shape:
-        raise L.EcgHipError(f"{who}: y {tuple(y.shape)} and prob {tuple(prob.shape)} differ in shape")
+    prob, y, _, _ = _pair_checked(who, prob, y, None)
     N, C = prob.shape
-    if order is None:
-        order = metrics_order(prob)[0]
-    order = _device_matrix(who, "order", order, torch.int32)
-    if tuple(order.shape) != (C, N):
-        raise L.EcgHipError(f"{who}: order must be [C={C}, N={N}], got {tuple(order.shape)}")
+    order = _order_checked(who, prob, order)
     place = torch.empty((C, N), dtype=torch.int32, device=prob.device)
     ws = _workspace(L.query("ecg_metrics_placements_workspace_bytes", N, C), prob.device)
     L.call("ecg_metrics_placements", L.ptr(prob), L.ptr(y), L.ptr(order), L.ptr(place), L.ptr(ws), N, C, L.stream())
@@ -238,13 +279,8 @@ def metrics_paired_sums(place, probs, y, threshold=0.5):
     who = "metrics_paired_sums"
     y = _device_matrix(who, "y", y, torch.float32)
     N, C = y.shape
-    for name, t, dtype in (("place", place, torch.int32), ("probs", probs, torch.float32)):
-        if not (torch.is_tensor(t) and t.is_cuda):
-            raise L.EcgHipError(f"{who}: a CPU tensor reached the HIP metrics step; {name} must be on the GPU")
-        if t.dtype != dtype or t.dim() != 3:
-            raise L.EcgHipError(f"{who}: {name} must be {dtype} with three dimensions, got {t.dtype} {tuple(t.shape)}")
-        if not t.is_contiguous():
-            raise L.EcgHipError(f"{who}: {name} must be contiguous")
+    place = _device_matrix(who, "place", place, torch.int32, 3)
+    probs = _device_matrix(who, "probs", probs, torch.float32, 3)
     M = probs.shape[0]
     if tuple(probs.shape) != (M, N, C) or tuple(place.shape) != (M, C, N):
         raise L.EcgHipError(f"{who}: probs must be [M, N={N}, C={C}] and place [M, C={C}, N={N}], got {tuple(probs.shape)} "
@@ -273,7 +309,6 @@ def delong_from_sums(single, pair):
     delta = theta_k - theta_l, z = delta / sqrt(var), p = erfc(|z| / sqrt(2)) (two-sided).  theta is NaN when m == 0 or
     n == 0 (summarize's rule); cov, var, z and p are NaN when m < 2 or n < 2, and z and p also when var == 0 (two models
     that rank the rows alike)."""
-    import math
     s, q = _host(single, np.int64), _host(pair, np.int64)
     C, M = s.shape[0], s.shape[1]
     nan = float("nan")
@@ -314,7 +349,6 @@ def mcnemar_from_sums(pair):
     on thousands of rows are about equally often right alone, so the middle is a few hundred terms where the tail is
     thousands: one big-integer step per term either way, never one binomial coefficient from scratch per term.  (k, l) and
     (l, k) share their value."""
-    import math
     q = _host(pair, np.int64)
     out = np.ones(q.shape[:-1], np.float64)
     seen = {}
@@ -341,15 +375,6 @@ def mcnemar_from_sums(pair):
                 seen[(n, lo)] = _ratio(num, 1 << n)         # below 1: at least one middle term is missing from it
         out[idx] = seen[(n, lo)]
     return out
-
-
-def _percentiles(reps, alpha):
-    """(lo, hi, n_nan) of replicates [n_boot, ...] along axis 0, NaN replicates left out — bootstrap_metrics' rule."""
-    q = (100.0 * alpha / 2, 100.0 * (1 - alpha / 2))
-    cols = reps.reshape(reps.shape[0], -1)
-    bounds = np.array([np.percentile(col[~np.isnan(col)], q) if (~np.isnan(col)).any() else (np.nan, np.nan)
-                       for col in cols.T]).reshape(reps.shape[1:] + (2,))
-    return bounds[..., 0], bounds[..., 1], np.isnan(reps).sum(0)
 
 
 def compare_models(y_true, probs, names=None, threshold=0.5, n_boot=0, seed=0, alpha=0.05):
@@ -389,27 +414,16 @@ def compare_models(y_true, probs, names=None, threshold=0.5, n_boot=0, seed=0, a
     if any(p.shape != y.shape for p in ps):
         raise L.EcgHipError(f"compare_models: every model needs probabilities of y_true's shape {tuple(y.shape)}, got "
                             f"{[tuple(p.shape) for p in ps]}")
-    w = bootstrap_weights(N, int(n_boot), seed, y.device) if n_boot > 0 else None
-    B = 1 + max(int(n_boot), 0)
-    flat, places = [], []
+    n_boot, w = _boot_rows(n_boot, N, seed, y.device)
+    per_model, places = [], []
     for p in ps:
         order, nonfinite = metrics_order(p)
-        fields, ap = metrics_counts(p, y, order=order, weights=w, threshold=threshold)
+        per_model += [*metrics_counts(p, y, order=order, weights=w, threshold=threshold), nonfinite]
         places.append(metrics_placements(p, y, order=order))
-        flat += [fields.reshape(-1), ap.view(torch.int64).reshape(-1), nonfinite.to(torch.int64)]
     single, pair = metrics_paired_sums(torch.stack(places), torch.stack(ps), y, threshold=threshold)
-    host = torch.cat(flat + [single.reshape(-1), pair.reshape(-1)]).cpu().numpy()      # the one read
-    per, at = B * C * len(FIELDS) + B * C + C, 0
-    summaries, nonf = [], np.empty((M, C), np.int64)
-    for k in range(M):
-        blk = host[k * per:(k + 1) * per]
-        f = blk[:B * C * len(FIELDS)].reshape(B, C, len(FIELDS))
-        a = np.ascontiguousarray(blk[B * C * len(FIELDS):B * C * (len(FIELDS) + 1)]).view(np.float64).reshape(B, C)
-        nonf[k] = blk[B * C * (len(FIELDS) + 1):]
-        summaries.append(summarize(f, a))
-    at = M * per
-    s_host = host[at:at + single.numel()].reshape(single.shape)
-    q_host = host[at + single.numel():].reshape(pair.shape)
+    *per_model, s_host, q_host = _read_once(*per_model, single, pair)
+    summaries = [summarize(per_model[3 * k], per_model[3 * k + 1]) for k in range(M)]
+    nonf = np.stack(per_model[2::3]).astype(np.int64)
     dl, mc = delong_from_sums(s_host, q_host), mcnemar_from_sums(q_host)
     out = {"names": names, "nonfinite": nonf, "pairs": {},
            "models": {nm: {k: (float(v[0]) if k in MACRO_KEYS else v[0]) for k, v in s.items()} for nm, s in zip(names, summaries)}}
@@ -425,13 +439,8 @@ def compare_models(y_true, probs, names=None, threshold=0.5, n_boot=0, seed=0, a
             if n_boot > 0:
                 d["bootstrap"], d["n_nan"], d["replicates"] = {}, {}, {}
                 for key in summaries[k]:
-                    diff = summaries[k][key] - summaries[l][key]
-                    lo, hi, n_nan = _percentiles(diff[1:], alpha)
-                    scalar = key in MACRO_KEYS
-                    d["bootstrap"][key] = {"point": float(diff[0]) if scalar else diff[0], "lo": float(lo) if scalar else lo,
-                                           "hi": float(hi) if scalar else hi}
-                    d["n_nan"][key] = int(n_nan) if scalar else n_nan
-                    d["replicates"][key] = diff[1:]
+                    d["bootstrap"][key], d["n_nan"][key], d["replicates"][key] = _interval(
+                        key, summaries[k][key] - summaries[l][key], alpha)
             out["pairs"][(names[k], names[l])] = d
     return out
 
@@ -470,11 +479,7 @@ def metrics_operating(prob, y, order=None, weights=None, sensitivity=(9, 10), sp
     who = "metrics_operating"
     prob, y, weights, B = _pair_checked(who, prob, y, weights)
     N, C = prob.shape
-    if order is None:
-        order = metrics_order(prob)[0]
-    order = _device_matrix(who, "order", order, torch.int32)
-    if tuple(order.shape) != (C, N):
-        raise L.EcgHipError(f"{who}: order must be [C={C}, N={N}], got {tuple(order.shape)}")
+    order = _order_checked(who, prob, order)
     sn, sd = _target(who, "sensitivity", sensitivity)
     pn, pd = _target(who, "specificity", specificity)
     points = torch.empty((B, C, len(RULES), 4), dtype=torch.int64, device=prob.device)
@@ -594,11 +599,7 @@ def operating_from_points(points, totals, prob):
     one integer ratio: "f1" = 2tp / (tp + fp + POS) (0 where that is 0 / 0), "sensitivity" = tp / POS, "specificity" =
     (NEG - fp) / NEG, "youden" = (tp NEG - fp POS) / (POS NEG) (NaN where the class has no positives / negatives)."""
     if torch.is_tensor(points):
-        thr = _gather_thresholds(points, prob)
-        n_p, n_t = points.numel(), totals.numel()
-        host = torch.cat([points.reshape(-1), totals.reshape(-1), thr.reshape(-1).view(torch.int32).to(torch.int64)]).cpu().numpy()
-        pts, tots = host[:n_p].reshape(points.shape), host[n_p:n_p + n_t].reshape(totals.shape)
-        thr = host[n_p + n_t:].astype(np.int32).view(np.float32).reshape(points.shape[:-1])
+        pts, tots, thr = _read_once(points, totals, _gather_thresholds(points, prob))
     else:
         pts, tots, pr = np.asarray(points, np.int64), np.asarray(totals, np.int64), np.asarray(prob, np.float32)
         row = pts[..., OP_ROW]
@@ -611,7 +612,7 @@ def operating_from_points(points, totals, prob):
 
 def _with_bounds(values, alpha, n_boot):
     """values: dict of arrays whose axis 0 is the weight row -> row 0 as the point values; with n_boot > 0 also "bootstrap"
-    {key: {"lo", "hi"}}, "n_nan" and "replicates" per key, by bootstrap_metrics' percentile rule."""
+    {key: {"lo", "hi"}}, "n_nan" and "replicates" per key, by the percentile rule (_percentiles)."""
     out = {k: v[0] for k, v in values.items()}
     if n_boot > 0:
         out["bootstrap"], out["n_nan"], out["replicates"] = {}, {}, {}
@@ -619,12 +620,7 @@ def _with_bounds(values, alpha, n_boot):
             if v.dtype.kind != "f":
                 continue
             reps = v[1:].astype(np.float64)
-            if np.isnan(reps).any():
-                lo, hi, n_nan = _percentiles(reps, alpha)
-            else:                                           # nothing to leave out: every column in one call
-                with np.errstate(invalid="ignore"):         # a threshold of +inf among the replicates
-                    lo, hi = np.percentile(reps, (100.0 * alpha / 2, 100.0 * (1 - alpha / 2)), axis=0)
-                n_nan = np.zeros(reps.shape[1:], np.int64)
+            lo, hi, n_nan = _percentiles(reps, alpha)
             out["bootstrap"][k], out["n_nan"][k], out["replicates"][k] = {"lo": lo, "hi": hi}, n_nan, reps
     return out
 
@@ -636,12 +632,8 @@ def calibration(y_true, y_prob, n_bins=10, n_boot=0, seed=0, alpha=0.05):
     (row 0 is the point value) and "bootstrap" holds {"lo", "hi"} per key (percentiles alpha/2 and 1 - alpha/2 over the
     replicates that are not NaN), with "n_nan" and "replicates" beside it."""
     y, p = _inputs(y_true, y_prob)
-    n_boot = max(int(n_boot), 0)
-    w = bootstrap_weights(p.shape[0], n_boot, seed, p.device) if n_boot > 0 else None
-    bins, tot = metrics_reliability(p, y, n_bins=n_bins, weights=w)
-    host = torch.cat([bins.reshape(-1), tot.reshape(-1)]).cpu().numpy()     # the one read
-    out = _with_bounds(calibration_from_tables(host[:bins.numel()].reshape(bins.shape), host[bins.numel():].reshape(tot.shape)),
-                       alpha, n_boot)
+    n_boot, w = _boot_rows(n_boot, p.shape[0], seed, p.device)
+    out = _with_bounds(calibration_from_tables(*_read_once(*metrics_reliability(p, y, n_bins=n_bins, weights=w))), alpha, n_boot)
     out["n_bins"] = int(n_bins)
     return out
 
@@ -692,8 +684,7 @@ def operating_points(y_true, y_prob, rules=("f1", "youden", ("sensitivity", 0.9)
     "replicates" for threshold, f1, sensitivity, specificity and youden."""
     who = "operating_points"
     y, p = _inputs(y_true, y_prob)
-    n_boot = max(int(n_boot), 0)
-    w = bootstrap_weights(p.shape[0], n_boot, seed, p.device) if n_boot > 0 else None
+    n_boot, w = _boot_rows(n_boot, p.shape[0], seed, p.device)
     names, where, calls = _operating_calls(who, p, y, rules, w)
     res = operating_from_points(torch.stack([c[0] for c in calls]), torch.stack([c[1] for c in calls]), p)   # [calls, B, C, 4]
     return {name: _with_bounds({k: v[call][..., idx] for k, v in res.items()}, alpha, n_boot)
@@ -732,13 +723,10 @@ def tuned_metrics(y_val, p_val, y_test, p_test, rule="f1", n_boot=0, seed=0, alp
     y, p = _inputs(y_test, p_test)
     if p.shape[1] != thr.numel():
         raise L.EcgHipError(f"tuned_metrics: the validation rows have {thr.numel()} classes, the test rows {p.shape[1]}")
-    n_boot = max(int(n_boot), 0)
-    w = bootstrap_weights(p.shape[0], n_boot, seed, p.device) if n_boot > 0 else None
-    conf = metrics_confusion(p, y, thr.unsqueeze(0), weights=w)[:, 0]                      # [B, C, 4]
-    host = torch.cat([conf.reshape(-1), thr.view(torch.int32).to(torch.int64)]).cpu().numpy()  # the one read
-    c = host[:conf.numel()].reshape(conf.shape)
-    out = _with_bounds(tuned_from_confusion(c), alpha, n_boot)
-    out["thresholds"], out["confusion"] = host[conf.numel():].astype(np.int32).view(np.float32), c[0]
+    n_boot, w = _boot_rows(n_boot, p.shape[0], seed, p.device)
+    conf, thr = _read_once(metrics_confusion(p, y, thr.unsqueeze(0), weights=w)[:, 0], thr)   # [B, C, 4]; [C]
+    out = _with_bounds(tuned_from_confusion(conf), alpha, n_boot)
+    out["thresholds"], out["confusion"] = thr, conf[0]
     return out
 
 

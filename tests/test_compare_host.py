@@ -5,7 +5,6 @@ delong_from_sums and mcnemar_from_sums give, bit for bit, what the restatement's
 points refuse every size outside their limits before any launch, asked with NULL pointers."""
 import ctypes
 import math
-import os
 from fractions import Fraction
 
 import numpy as np
@@ -13,14 +12,11 @@ import pytest
 
 import compare_ref as cr
 import metrics_ref as mr
+from metrics_util import load_lib, same_bits
 
 from ecg_hip.metrics import delong_from_sums, mcnemar_from_sums      # absent before this stage existed
 
 F = Fraction
-
-
-def same_bits(a, b):
-    return np.array_equal(np.asarray(a, np.float64).view(np.int64), np.asarray(b, np.float64).view(np.int64))
 
 
 # scores of model A, of model B, labels; then by hand: the placements of A and B, U2 of each, Cov[A,A], Cov[B,B], Cov[A,B]
@@ -184,11 +180,7 @@ def test_restatement_agrees_with_the_classic_form(kind, N):
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as g
-    from ecg_hip import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        g.build()
-    return _lib.load()
+    return load_lib()
 
 
 def test_limits_are_refused_before_any_launch(lib):

@@ -12,10 +12,10 @@ import pytest
 import torch
 
 import compare_ref as cr
+from metrics_util import ROOT, metrics_module, same_bits
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = (1, 2, 63, 64, 65, 1023, 1024, 1025, 2049, 4097)
 CS = (1, 5, 7)
 MS = (1, 2, 3)
@@ -25,8 +25,7 @@ SENTINEL = -7
 
 @pytest.fixture(scope="module")
 def M():
-    from ecg_hip import metrics
-    return metrics
+    return metrics_module()
 
 
 def _cases():
@@ -52,10 +51,6 @@ def case_data(case):
     a, y = cr.scores(kind, N, C, rng), cr.labels(lab, N, C, rng)
     probs = np.stack([a, cr.related(rel, a, kind, rng), cr.scores(kind, N, C, rng)][:nm])
     return y, probs, cr.compare(y, probs, thr)
-
-
-def same_bits(a, b):
-    return np.array_equal(np.asarray(a, np.float64).view(np.int64), np.asarray(b, np.float64).view(np.int64))
 
 
 def test_cases_cover_what_they_claim_and_are_not_vacuous():

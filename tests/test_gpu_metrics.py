@@ -4,19 +4,17 @@ tests/test_metrics_host.py).  Shapes are the smallest that can still go wrong: a
 average-precision sum and several of them, 1 000 ranks (just under one chunk of the scan), 4 097 (two tiles of the order
 kernel's key stream, five chunks of the scan)."""
 import functools
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import metrics_ref as mr
+from metrics_util import header_slab, metrics_module, same_bits, tol
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SLAB = int(re.search(r"#define ECG_METRICS_SLAB (\d+)", open(os.path.join(ROOT, "include", "ecg_hip.h")).read()).group(1))
+SLAB = header_slab()
 SIZES = sorted({1, 2, 63, 64, 65, SLAB - 1, SLAB, SLAB + 1, 3 * SLAB + 1, 1000, 4097})
 KINDS = ("equal", "q3", "untied", "zeros", "denormal", "nonfinite")
 LABELS = ("mixed", "all0", "all1")
@@ -24,15 +22,10 @@ WEIGHTS = (None, 1, 3, 70)
 THRESHOLDS = (0.5, 0.3, 0.0, 1.0)
 
 
-def tol(n):
-    return n * 2.0 ** -50
-
-
 @pytest.fixture(scope="module")
 def M():
-    from ecg_hip import metrics
-    assert metrics.slab() == SLAB
-    return metrics
+    assert metrics_module().slab() == SLAB
+    return metrics_module()
 
 
 def make_scores(kind, N, C, rng):
@@ -103,10 +96,6 @@ def case_data(case):
     w = make_weights(B, N, y, rng)
     o, nonf = mr.order(p)
     return p, y, w, o, nonf, mr.counts(p, y, o, w, thr, SLAB)
-
-
-def same_bits(a, b):
-    return np.array_equal(np.asarray(a, np.float64).view(np.int64), np.asarray(b, np.float64).view(np.int64))
 
 
 def check(M, p_dev, y_dev, w_dev, thr, want):

@@ -13,6 +13,7 @@ import torch
 
 import metrics_ref as mr
 import operating_ref as opr
+from metrics_util import ROOT, dev, host, metrics_module, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -28,8 +29,7 @@ TARGETS = ((0, 1), (1, 1), (9, 10), (999999, 1000000))
 
 @pytest.fixture(scope="module")
 def M():
-    from ecg_hip import metrics
-    return metrics
+    return metrics_module()
 
 
 def make_scores(kind, N, C, rng):
@@ -120,14 +120,6 @@ def case_data(case):
     pool = np.concatenate([finite[:8], np.array([0.5, 0.0, -0.0, 1.0, np.nan, np.inf, -np.inf, 0.3], np.float32)])
     thr = rng.choice(pool, (T, C)).astype(np.float32)
     return p, y, w, o, (points, totals), thr, opr.confusion(p, y, thr, w), opr.reliability(p, y, w, nb)
-
-
-def dev(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def host(t):
-    return t.cpu().numpy()
 
 
 def check(M, case, p_d, y_d, w_d, data):
@@ -242,10 +234,6 @@ def test_side_stream_offset_views_and_refusals(M):
 
 
 # ---- the user calls
-def same_bits(a, b):
-    return np.array_equal(np.asarray(a, np.float64).view(np.int64), np.asarray(b, np.float64).view(np.int64))
-
-
 N_BOOT, SEED = 12, 3
 RULES = ("f1", "youden", ("sensitivity", 0.9), ("specificity", 0.9))
 NAMES = ("f1", "youden", "sensitivity@0.9", "specificity@0.9")
@@ -375,7 +363,7 @@ def test_calibrate_predictions_tool_on_merged_csvs(M, tmp_path):
     import json
     import os
     import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
     try:
         import calibrate_predictions as tool
     finally:

@@ -4,34 +4,23 @@ roundings each), F1 with ==, the ROC and precision-recall curves at group ends w
 gives what the reference's compute_metrics gives on the edge cases, NaN-ness included.  (3) The entry points refuse every
 size outside their limits before any launch, asked with NULL pointers."""
 import ctypes
-import os
-import re
 import warnings
 
 import numpy as np
 import pytest
 
 import metrics_ref as mr
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from metrics_util import header_slab, load_lib, metrics_module, same_bits, tol
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as g
-    from ecg_hip import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        g.build()
-    return _lib.load()
+    return load_lib()
 
 
 @pytest.fixture(scope="module")
 def slab(lib):
     return lib.ecg_metrics_slab()
-
-
-def tol(n):
-    return n * 2.0 ** -50
 
 
 def scores(kind, N, C, rng):
@@ -199,9 +188,8 @@ def test_limits_are_refused_before_any_launch(lib):
 
 
 def test_slab_is_the_headers(lib):
-    text = open(os.path.join(ROOT, "include", "ecg_hip.h")).read()
-    assert lib.ecg_metrics_slab() == int(re.search(r"#define ECG_METRICS_SLAB (\d+)", text).group(1))
-    from ecg_hip import metrics as M
+    assert lib.ecg_metrics_slab() == header_slab()
+    M = metrics_module()
     assert M.slab() == lib.ecg_metrics_slab() and len(M.FIELDS) == mr.FIELDS
 
 
@@ -216,3 +204,64 @@ def test_wrappers_refuse_cpu_tensors_and_are_reachable_from_functional():
         F.metrics_counts(torch.zeros(4, 2), torch.zeros(4, 2))
     with pytest.raises(EcgHipError, match="CUDA tensors"):
         M.compute_metrics_device(torch.zeros(4, 2), torch.zeros(4, 2))
+
+
+def _literal_percentiles(reps, alpha):
+    """The percentile rule column by column: NaN replicates left out, NaN bounds when none is left."""
+    q = (100.0 * alpha / 2, 100.0 * (1 - alpha / 2))
+    flat = reps.reshape(reps.shape[0], -1)
+    lo, hi, n_nan = np.empty(flat.shape[1]), np.empty(flat.shape[1]), np.empty(flat.shape[1], np.int64)
+    for j in range(flat.shape[1]):
+        kept = flat[:, j][~np.isnan(flat[:, j])]
+        with np.errstate(invalid="ignore"):                                     # +inf among the values
+            lo[j], hi[j] = np.percentile(kept, q) if kept.size else (np.nan, np.nan)
+        n_nan[j] = flat.shape[0] - kept.size
+    return lo.reshape(reps.shape[1:]), hi.reshape(reps.shape[1:]), n_nan.reshape(reps.shape[1:])
+
+
+def test_percentiles_fast_path_and_column_path_agree_by_bits():
+    for shape in ((50,), (50, 5), (50, 5, 4)):
+        _check_percentiles(metrics_module(), shape, np.random.default_rng(17))
+
+
+def _check_percentiles(M, shape, rng):
+    clean = rng.random(shape)
+    holes = np.where(rng.random(shape) < 0.2, np.nan, clean)                    # NaN in some columns (the vector: some entries)
+    holes[0] = clean[0]
+    lost = holes.copy()
+    lost.reshape(shape[0], -1)[:, -1] = np.nan                                  # one column all NaN
+    inf = clean.copy()
+    inf.reshape(shape[0], -1)[rng.integers(0, shape[0], 7), rng.integers(0, inf[0].size, 7)] = np.inf
+    inf_holes = np.where(np.isnan(holes), np.nan, inf)
+    for name, reps in (("clean", clean), ("holes", holes), ("lost", lost), ("inf", inf), ("inf_holes", inf_holes)):
+        assert np.isnan(reps).any() == (name not in ("clean", "inf"))            # the first and fourth take the fast path
+        for alpha in (0.05, 0.5):
+            got, want = M._percentiles(reps, alpha), _literal_percentiles(reps, alpha)
+            for g, w in zip(got[:2], want[:2]):
+                assert np.shape(g) == shape[1:] and np.asarray(g).dtype == np.float64, name
+                assert same_bits(g, w), (name, alpha)
+            assert np.array_equal(got[2], want[2]) and np.asarray(got[2]).dtype == np.int64, name
+    assert np.isnan(M._percentiles(lost, 0.05)[0].reshape(-1)[-1]) and M._percentiles(lost, 0.05)[2].reshape(-1)[-1] == shape[0]
+
+
+def test_read_once_round_trips_bit_patterns_on_cpu_tensors():
+    import torch
+    M = metrics_module()
+    i64 = np.array([[2 ** 62, -2 ** 62, -1], [0, 2 ** 63 - 1, -2 ** 63]], np.int64)
+    i32 = np.array([-1, 2 ** 31 - 1, -2 ** 31, 0, 7], np.int32)
+    f64 = np.array([0x8000000000000000, 0x7ff8000000abcdef, 0xfff0000000000001, 1, 0x3ff0000000000001], np.uint64).view(np.float64)
+    f32 = np.array([[0x7f800000, 0x80000000], [0x7fc12345, 0xff800001], [0x3f800001, 1]], np.uint32).view(np.float32)
+    assert f64[0] == 0 and np.signbit(f64[0]) and np.isnan(f64[1:3]).all() and 0 < f64[3] < 2.3e-308   # -0.0, NaN payloads, a denormal
+    assert np.isposinf(f32[0, 0]) and np.isnan(f32[1]).all() and f32[2, 0] == np.nextafter(np.float32(1), np.float32(2))
+    arrays = [i64, f32, np.empty((0, 3), np.float64), i32, f64, np.empty(0, np.float32), f64.reshape(5, 1, 1), i32[:1].reshape(())]
+    calls = []
+    real = torch.Tensor.cpu
+    torch.Tensor.cpu = lambda t, *a, **k: calls.append(1) or real(t, *a, **k)
+    try:
+        got = M._read_once(*[torch.from_numpy(np.array(a)) for a in arrays])
+    finally:
+        torch.Tensor.cpu = real
+    assert len(calls) == 1 and len(got) == len(arrays)
+    for g, a in zip(got, arrays):
+        assert isinstance(g, np.ndarray) and g.dtype == a.dtype and g.shape == a.shape
+        assert g.tobytes() == a.tobytes()

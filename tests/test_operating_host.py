@@ -6,7 +6,6 @@ with no score on a bin edge (asserted, none left out), and the Brier score is br
 (4) calibration_from_tables and operating_from_points give the bits of the same ratios taken in Fractions.  (5) The entry
 points refuse every size outside their limits before any launch, asked with NULL pointers."""
 import ctypes
-import os
 import warnings
 from fractions import Fraction
 
@@ -15,22 +14,14 @@ import pytest
 
 import metrics_ref as mr
 import operating_ref as opr
+from metrics_util import load_lib, same_bits
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NINE_TENTHS = (9, 10)
 
 
 @pytest.fixture(scope="module")
 def lib():
-    import __graft_entry__ as g
-    from ecg_hip import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        g.build()
-    return _lib.load()
-
-
-def same_bits(a, b):
-    return np.array_equal(np.asarray(a, np.float64).view(np.int64), np.asarray(b, np.float64).view(np.int64))
+    return load_lib()
 
 
 @pytest.mark.parametrize("name", sorted(opr.HAND))
